@@ -12,7 +12,7 @@ on data already resident in HBM: V(s), V(s'), GAE over the 2^20 transitions, log
 repeat x 16 = 160 minibatch gradient steps (forward, loss, backward, grad-clip, Adam).
 value = minibatch gradient steps per second over the whole job (all ranks), preprocessing included.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak|both]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak|both] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (N > 1, one rank per GPU)
     (`python bench.py --gpus N` without WORLD_SIZE in the environment starts that launcher itself)
 
@@ -21,7 +21,12 @@ sub-buffers are sharded over the ranks by env id (`shard_envs`), glob
 65,536 / N rows per rank per gradient step, 160 gradient steps per update() whatever N; per step the flat
 fp32 gradient + loss parts (11,089 floats) are all-reduced.  The weak-scaling figure (every rank its own
 2^20-transition rollout and a 65,536-row local minibatch: the per-GPU work of N = 1) is measured in the same
-run and printed beside it (`weak_scaling`).
+--full run and printed beside it (`weak_scaling`).
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given and prints the
+line.  Everything else the benchmark measures or checks (CPU / ROCm-eager baselines, per-kernel and roofline figures, GAE scans,
+the strong-scaling projection, the H2D / recompute_advantage / hook-level legs, the other workloads; at N > 1 the weak
+leg beside the strong one and the exchange timing) needs --full.
 """
 from __future__ import annotations
 
@@ -149,6 +154,8 @@ class Learner:
         self.perm_seed = 1234 + 7919 * rank
         self._lib = _lib
         self.ws = _lib.default_workspace(device.index)
+        self.keep_last = False            # --dump-outputs: hold on to what the last update_once() computed
+        self.last = None
         self.dp = None
         self._ar = allreduce
         self.exchange = exchange
@@ -184,8 +191,27 @@ class Learner:
         perms = [self.next_perm() for _ in range(REPEAT)]
         if self.world == 1 and not os.environ.get("TS_BENCH_FORCE_DP"):    # (env: time the DP host path at N = 1)
             losses, steps = self.eng.update(b, self.minibatch, REPEAT, perms)
-            return losses, steps
-        return self._dp().update(b, self.minibatch, REPEAT, perms)
+        else:
+            losses, steps = self._dp().update(b, self.minibatch, REPEAT, perms)
+        if self.keep_last:
+            self.last = (b, losses)
+        return losses, steps
+
+
+def dump_outputs(learner, out_dir):
+    """--dump-outputs DIR: what the last timed update() handed its caller, one DIR/<name>.npy each (~17 MB at N = 1; rank 0's
+    shard at N > 1) -- the per-step losses, the trained parameters, Adam's moments, the return statistics and the
+    preprocessed batch (V(s), returns, advantages, log pi_old of every transition).  Same arguments, same inputs: the
+    rollout, the initial weights and the permutation keys are all seeded."""
+    b, losses = learner.last
+    eng = learner.eng
+    arrays = {"losses": losses, "params": eng.params, "adam_m": eng.adam_m, "adam_v": eng.adam_v,
+              "ret_rms": torch.tensor(eng.ret_rms, dtype=torch.float64),
+              "v_s": b["v_s"], "returns": b["returns"], "adv": b["adv"], "logp_old": b["logp_old"]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
 
 
 def make_exchange(device, rank, world):
@@ -644,20 +670,29 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--scaling", default="both", choices=["strong", "weak", "both"],
                     help="N > 1: strong = one 2^20-transition rollout sharded over the ranks, global minibatch 65536 (BASELINE "
-                         "configs[3]); weak = a 2^20 rollout and 65536 rows per rank; both (default) = strong is `value`, the weak "
-                         "figure is measured in the same run and printed beside it.  N = 1: the two are the same workload.")
+                         "configs[3]); weak = a 2^20 rollout and 65536 rows per rank; both (default) = strong is `value`, and with "
+                         "--full the weak figure is measured in the same run and printed beside it.  N = 1: the two are the same workload.")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--selftest-rounds", type=int, default=1000,
                     help="N > 1: all-reduces of random payloads checked against torch.distributed before the timed legs "
                          "(a mismatch on any rank drops the native exchange on every rank)")
     ap.add_argument("--no-extras", action="store_true", help="skip the ROCm-eager baseline, the hook-level leg, the H2D "
                     "measurement and the other workloads (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: CPU / ROCm-eager baselines, per-kernel and "
+                         "roofline figures, GAE scans, the strong-scaling projection, the H2D / recompute_advantage / "
+                         "hook-level legs, the other workloads; N > 1: the second scaling leg and the exchange timing "
+                         "(--no-cpu-baseline / --no-extras trim this as before)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--workload", default="ppo",
                     choices=["ppo", "dqn", "sac", "ppo_atari", "td3", "ddpg", "dsac", "qrdqn", "c51", "rainbow", "npg", "trpo", "redq", "ppo_discrete", "reinforce", "drqn"],
                     help="ppo = BASELINE.json's metric on C2 (default); dqn / sac = the C3 / C5 rows (bench_dqn.py, "
                          "bench_sac.py); ppo_atari = the north star's Atari-shape PPO (bench_ppo_cnn.py); the rest = "
                          "the SURVEY 8f rows and BASELINE configs[0] (bench_next.py)")
     args = ap.parse_args()
+    if args.workload != "ppo" and args.dump_outputs:
+        raise SystemExit("--dump-outputs: the PPO workload only")
     if args.workload != "ppo":
         import importlib
 
@@ -737,21 +772,23 @@ def main():
                 pass
             xch["ar"], xch["name"] = None, "torch.distributed all_reduce (RCCL)"
             xch["note"] = "the native exchange failed the pre-flight self-test; every leg runs on torch.distributed"
-    legs = ["strong", "weak"] if (args.scaling == "both" and world > 1) else [("strong" if args.scaling == "both" else args.scaling)]
+    legs = (["strong", "weak"] if (args.full and args.scaling == "both" and world > 1)
+            else [("strong" if args.scaling == "both" else args.scaling)])
 
-    def timed_leg(scaling):
+    def timed_leg(scaling, keep_last=False):
         """W warm-up + exactly K timed update()s, barrier + synchronize on both sides, MAX over the ranks.  If the native
         exchange reports a failed hand-off on ANY rank (bounded spin of the one-shot path: never seen on one device, unproven
         across xGMI), every rank drops it and the leg is measured again on torch.distributed -- a slower number instead of
         no number."""
-        out = _timed_leg(scaling)
+        out = _timed_leg(scaling, keep_last)
         if out is None:
-            out = _timed_leg(scaling)
+            out = _timed_leg(scaling, keep_last)
         return out
 
-    def _timed_leg(scaling):
+    def _timed_leg(scaling, keep_last=False):
         ar, exchange = xch["ar"], xch["name"]
         learner = Learner(device, rank, world, scaling, allreduce=ar, exchange=exchange)
+        learner.keep_last = keep_last
         bench_init.warm_clocks(device)        # idle clocks -> load clocks before the W warm-up steps (not an update step)
         for _ in range(args.warmup):
             learner.update_once()
@@ -787,8 +824,11 @@ def main():
                 return None
         return learner, el, total, [float(x) for x in losses[-1].tolist()]
 
-    learner, elapsed, total_steps, final_loss = timed_leg(legs[0])
+    learner, elapsed, total_steps, final_loss = timed_leg(legs[0], keep_last=bool(args.dump_outputs))
     head = legs[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(learner, args.dump_outputs)
+        learner.keep_last, learner.last = False, None
     # strong: `total_steps` gradient steps of the GLOBAL minibatch; weak: every rank ran that many on its own 65,536 rows
     value = total_steps / elapsed * (world if head == "weak" else 1)
     beside = None
@@ -801,7 +841,7 @@ def main():
         torch.cuda.empty_cache()
         learner = keep
     ar, exchange = xch["ar"], xch["name"]
-    exchange_us = time_exchange(device, world, ar, learner.eng.P + 4)
+    exchange_us = time_exchange(device, world, ar, learner.eng.P + 4) if args.full else None
     rccl_ranks = None
     if ar is not None:
         rccl_ranks = {"communicator": ar.ranks()[0], "rccl_reported": ar.ranks()[1]}
@@ -813,7 +853,7 @@ def main():
     # per-kernel durations with HIP events on the launch stream, one more (rank-local) update()
     roof, extra = None, {}
     n_chunks = learner.n_trans // learner.minibatch
-    if rank == 0:
+    if rank == 0 and args.full:
         b = learner.preprocess(local_only=True)
         torch.cuda.synchronize()
         # every world size: rank 0 times the kernels of one local update() on its own shard (no collective inside)
@@ -868,9 +908,9 @@ def main():
         extra["preprocess_transitions_per_s"] = 3 * learner.n_trans / (time.perf_counter() - t1)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline()
-    if rank == 0 and world == 1 and not args.no_extras and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and not args.no_cpu_baseline:
         t_h2d = h2d_seconds(device)
         t_update = elapsed / args.steps
         extra["value_incl_h2d"] = {"value": total_steps / args.steps / (t_update + t_h2d), "unit": "update-steps/s",
@@ -909,7 +949,7 @@ def main():
             "roofline": roof, "cpu_baseline": cpu, "final_losses": final_loss,
         }
         if world > 1:
-            out["exchange_us"] = exchange_us
+            out["exchange_us"] = exchange_us           # (--full only; None otherwise)
             out["exchange_ranks"] = rccl_ranks
             out["exchange_selftest"] = selftest
             if xch["note"]:

@@ -1,13 +1,14 @@
 #!/bin/bash
 # Final evidence run (under gpurun): bench lines + rocprofv3 kernel stats for every workload -> gpurun_out/final/
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 O=$GRAFT_REPO_ROOT/gpurun_out/final; mkdir -p $O
 cd $GRAFT_REPO_ROOT
-( time python bench.py ) > $O/bench_n1.json 2> $O/bench_n1.time
+( time python bench.py --full ) > $O/bench_n1.json 2> $O/bench_n1.time
 python bench.py --workload dqn > $O/bench_dqn.json 2>> $O/err.txt
 python bench.py --workload sac > $O/bench_sac.json 2>> $O/err.txt
 python bench.py --workload ppo_atari > $O/bench_ppo_atari.json 2>> $O/err.txt
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $O/prof_ppo -o ppo -- python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_under_rocprofv3.json 2>> $O/err.txt
+rocprofv3 --kernel-trace --stats -d $O/prof_ppo -o ppo -- python $REPO/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $O/bench_under_rocprofv3.json 2>> $O/err.txt
 rocprofv3 --kernel-trace --stats -d $O/prof_dqn -o dqn -- python $GRAFT_REPO_ROOT/bench_dqn.py --steps 20 --no-cpu-baseline > $O/dqn_under_rocprofv3.json 2>> $O/err.txt
 rocprofv3 --kernel-trace --stats -d $O/prof_sac -o sac -- python $GRAFT_REPO_ROOT/bench_sac.py --steps 20 --no-cpu-baseline > $O/sac_under_rocprofv3.json 2>> $O/err.txt
 rocprofv3 --kernel-trace --stats -d $O/prof_atari -o atari -- python $GRAFT_REPO_ROOT/bench_ppo_cnn.py --repeat 1 --no-cpu-baseline > $O/atari_under_rocprofv3.json 2>> $O/err.txt

@@ -278,7 +278,7 @@ def test_bench_two_ranks_dry_run_on_one_gpu():
     ts_ppo_dp_step.  Checks the N > 1 code path end to end (one rollout sharded by env id, shard-local preprocessing with
     global return statistics, the data-parallel update on 32,768-row local minibatches, max-over-ranks timing, the weak leg
     beside it, one JSON line from rank 0) -- not a measurement."""
-    d = _bench_dry_run(["--gpus", "2", "--steps", "1", "--warmup", "1"], launcher=2, timeout=600)
+    d = _bench_dry_run(["--gpus", "2", "--steps", "1", "--warmup", "1", "--full"], launcher=2, timeout=600)
     assert d["n_gpus"] == 2 and d["steps"] == 1 and d["scaling"] == "strong" and d["value"] > 0
     assert d["config"]["gradient_steps_per_step"] == 160 and d["config"]["transitions_per_step"] == 1 << 20
     assert d["config"]["parallelism"] == "dp2" and "one-shot" in d["config"]["exchange"]
@@ -293,9 +293,31 @@ def test_bench_eight_ranks_spawns_itself_on_one_gpu():
     """`python bench.py --gpus 8` without a launcher: bench.py starts torch.distributed.run itself.  Eight IPC peers on one
     device exercise the 8-way rank-ordered sum of the one-shot all-reduce and the 64-sub-buffer shards / 8,192-row local
     minibatches of BASELINE configs[3] (strong leg only, to bound the time eight time-sharing ranks need)."""
-    d = _bench_dry_run(["--gpus", "8", "--steps", "1", "--warmup", "1", "--scaling", "strong"], launcher=0, timeout=900)
+    d = _bench_dry_run(["--gpus", "8", "--steps", "1", "--warmup", "1", "--scaling", "strong", "--full"], launcher=0, timeout=900)
     assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["value"] > 0
     assert d["config"]["gradient_steps_per_step"] == 160 and "8192 rows per rank" in d["config"]["workload"]
     assert "64 sub-buffers per rank" in d["config"]["workload"]
     assert d["exchange_ranks"]["communicator"] == 8 and d["exchange_us"] > 0
     assert all(abs(x) < 1e3 for x in d["final_losses"])
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1` without --full: the headline line alone (no leg beside it), exactly --steps timed update()s, and
+    --dump-outputs writes what the last one computed -- float32 / float64 arrays, 64 MB at most, its losses those of the line."""
+    import os
+
+    import numpy as np
+
+    d = _bench_dry_run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)], launcher=0, timeout=300)
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["config"]["gradient_steps_per_step"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["unit"] == "update-steps/s"
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    assert not {"kernel_us", "roofline_gae", "strong_scaling_projection", "other_workloads", "hook_level"} & set(d)
+    names = sorted(f[:-4] for f in os.listdir(tmp_path))
+    assert names == sorted(["losses", "params", "adam_m", "adam_v", "ret_rms", "v_s", "returns", "adv", "logp_old"])
+    out = {n: np.load(os.path.join(tmp_path, n + ".npy")) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert out["losses"].shape == (160, 4) and np.array_equal(out["losses"][-1], np.float32(d["final_losses"]))
+    assert out["params"].shape == out["adam_m"].shape == out["adam_v"].shape and out["v_s"].shape == (1 << 20,)
