@@ -928,7 +928,8 @@ int ts_sac_layout_h(int64_t obs_dim, int64_t act_dim, int64_t hidden, int64_t* h
 /* Net(hidden_sizes=[h] * depth) for depth other than 2 (utils/net/common.py:246-369 takes any list; round 6): the number of
  * hidden layers is a property of the workspace too -- ts_mlp_set_trunk(ws, h, depth) (depth in [1, TS_MLP_MAX_HIDDEN_LAYERS];
  * 0 = 2) applies to every SAC / TD3 / DDPG / REDQ / DiscreteSAC entry point subsequently called with `ws`;
- * ts_mlp_set_hidden resets the depth to 2.  Flat vectors then hold depth + 1 wb matrices back to back:
+ * ts_mlp_set_hidden resets the depth to 2 (and the activation and the actor bound below to their defaults).  Flat vectors
+ * then hold depth + 1 wb matrices back to back:
  *   L1 [k + 1, h] | L2 .. Ldepth [h + 1, h] each | head [h + 1, head_cols]
  * (k = the input width rounded up to 32; head_cols = 64 for SAC's / REDQ's Gaussian actor, 32 otherwise) -- for depth 2
  * exactly the layouts above.  ts_mlp_layout: h_out[0] = k, h_out[1 + i] = offset of linear layer i (i = 0 .. depth; the
@@ -944,7 +945,7 @@ int ts_mlp_set_activation(ts_workspace* ws, int activation);
 /* ContinuousActorProbabilistic(unbounded=False) -- the class default, utils/net/continuous.py:194, 230-231: mu = max_action *
  * tanh(mu) in front of SAC's / REDQ's Gaussian (the examples pass unbounded=True).  A property of the workspace like the trunk:
  * applies to every ts_sac_* / ts_redq_* entry point subsequently called with `ws` -- forward, target, update (the gradient goes
- * back through max_action * (1 - tanh^2)).  0 = unbounded (the default). */
+ * back through max_action * (1 - tanh^2)).  0 = unbounded (the default; ts_mlp_set_hidden / ts_mlp_set_trunk reset to it). */
 int ts_sac_set_actor_bound(ts_workspace* ws, double max_action);
 int ts_mlp_layout(int64_t in_dim, int64_t hidden, int64_t depth, int64_t head_cols, int64_t* h_out);
 

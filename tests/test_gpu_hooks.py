@@ -16,6 +16,7 @@ from torch import nn
 
 from oracle import oracle as O
 from oracle import oracle_ppo as OP
+from tests import lazy_twins as LT
 from tests import standin as SI
 
 pytestmark = pytest.mark.gpu
@@ -46,14 +47,7 @@ def _oracle_params(algo):
     return OP.unflatten_params(flat.clone(), obs_dim, act_dim, hidden)
 
 
-def _fill(buf, T, obs_dim, act_dim, rng):
-    E = buf.buffer_num
-    obs = rng.normal(size=(T + 1, E, obs_dim)).astype(np.float32)
-    for t in range(T):
-        term = rng.random(E) < 0.03
-        buf.add(SI.Batch(obs=obs[t], act=rng.normal(size=(E, act_dim)).astype(np.float32),
-                         rew=rng.normal(size=E).astype(np.float32), terminated=term,
-                         truncated=(rng.random(E) < 0.02) & ~term, obs_next=obs[t + 1]))
+_fill = LT.fill_vector
 
 
 def _oracle_update(st, ocfg, buf, batch_size, repeat, perms):
@@ -477,24 +471,12 @@ def test_hip_sac_default_mode_equals_the_reference_exact_mode(monkeypatch):
     import copy
     import pickle
 
-    from tianshou_amd.integration import make_hip_sac
-
-    obs_dim, act_dim, E, B = 23, 5, 4, 64
-    HipSAC = make_hip_sac(ref=SI)
-
-    def build(**kw):
-        torch.manual_seed(11)
-        actor = SI.ContinuousActorProbabilistic(SI.Net(obs_dim, [256, 256], nn.ReLU), act_dim, unbounded=True, conditioned_sigma=True)
-        c1 = SI.ContinuousCritic(SI.Net(obs_dim + act_dim, [256, 256], nn.ReLU))
-        c2 = SI.ContinuousCritic(SI.Net(obs_dim + act_dim, [256, 256], nn.ReLU))
-        algo = HipSAC(policy=SI.Policy(actor), critic=c1, critic2=c2, lr=1e-3, tau=0.01, gamma=0.97,
-                      alpha=SI.AutoAlpha(-float(act_dim), -0.5, 3e-4), device="cuda", update_noise="torch", **kw).to("cuda")
-        algo.policy.is_within_training_step = True
-        return algo
+    obs_dim, act_dim, E, B = LT.SAC_OBS, LT.SAC_ACT, LT.SAC_ENVS, LT.SAC_BATCH
+    build = LT.sac_build                                           # (update_noise="torch": the reference's stream in both)
 
     ref, lazy = build(host_batch=True, write_back="eager"), build()
     assert lazy.__dict__["_hip_lazy"] and not ref.__dict__["_hip_lazy"]
-    bufs = [SI.VectorReplayBuffer(E * 200, E, obs_shape=(obs_dim,), act_shape=(act_dim,), seed=4) for _ in range(2)]
+    bufs = [LT.sac_buffer() for _ in range(2)]
     rng = [np.random.default_rng(9) for _ in range(2)]
     flat = lambda algo: torch.cat([p.detach().reshape(-1).float().cpu() for p in algo.parameters()])  # noqa: E731
     start = flat(lazy)
@@ -760,37 +742,13 @@ def test_hip_dqn_default_mode_equals_the_reference_exact_mode(layout):
     examples/atari/atari_dqn.py) -- there the two hooks of the default mode are ONE library call (ts_dqn_learn_rows: gathers, n-step
     returns and update for the indices and importance weights the host buffer drew) and must equal the reference-exact mode's
     separate calls bit for bit."""
-    from tianshou_amd.integration import make_hip_dqn
-
-    c, h, w, A, E, size, B = 4, 44, 36, 3, 4, 40, 32
-    HipDQN = make_hip_dqn(ref=SI)
-
-    def build(**kw):
-        torch.manual_seed(5)
-        model = SI.DQNet(c, h, w, A)
-        with torch.no_grad():
-            model.net[0][0].weight.mul_(1.0 / 255.0)
-        algo = HipDQN(policy=SI.DiscreteQLearningPolicy(model), lr=1e-4, gamma=0.97, n_step_return_horizon=3, target_update_freq=2,
-                      is_double=True, huber_loss_delta=None, device="cuda", **kw).to("cuda")
-        algo.policy.is_within_training_step = True
-        return algo
+    c, h, w, B = LT.DQN_C, LT.DQN_H, LT.DQN_W, LT.DQN_BATCH
+    build, fill = LT.dqn_build, LT.dqn_fill
 
     ref, lazy = build(host_batch=True, write_back="eager"), build()
     assert lazy.__dict__["_hip_lazy"] and not ref.__dict__["_hip_lazy"]
-    bufs = [SI.PrioritizedVectorReplayBuffer(E * size, E, obs_shape=(h, w), act_shape=(), obs_dtype=np.uint8, act_dtype=np.int64,
-                                             seed=2, stack_num=c, alpha=0.6, beta=0.4) for _ in range(2)]
+    bufs = [LT.dqn_buffer(layout) for _ in range(2)]                 # (atari_frames: ignore_obs_next=True)
     rngs = [np.random.default_rng(3) for _ in range(2)]
-
-    def fill(buf, rng, n):
-        for _ in range(n):
-            term = rng.random(E) < 0.08
-            buf.add(SI.Batch(obs=rng.integers(0, 256, (E, h, w)).astype(np.uint8), act=rng.integers(0, A, E),
-                             rew=rng.normal(size=E), terminated=term, truncated=(rng.random(E) < 0.03) & ~term,
-                             obs_next=rng.integers(0, 256, (E, h, w)).astype(np.uint8)))
-
-    if layout == "atari_frames":
-        for b in bufs:
-            b._meta = SI._Meta(("obs", "act", "rew", "terminated", "truncated", "done"))        # ignore_obs_next=True
     made = []
     orig = bufs[1].sample
     bufs[1].sample = lambda bs: (made.append(bs), orig(bs))[1]          # the default mode must not ask for the host batch

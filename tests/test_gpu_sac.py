@@ -339,6 +339,36 @@ def test_bounded_actor_vs_oracle(hidden, obs_dim, act_dim, B):
         assert e_gpu < max(1e-5, 2 * e_ref), (key, e_gpu, e_ref)
 
 
+def test_set_hidden_resets_the_actor_bound():
+    """C ABI: `ts_mlp_set_hidden` starts the workspace's trunk settings over -- width, depth 2, ReLU and an UNBOUNDED actor.  A
+    direct C caller that sets a width after another engine's `ts_sac_set_actor_bound(ws, 2.0)` gets the unbounded actor of
+    examples/mujoco/mujoco_sac.py, not a tanh bound it never asked for: `ts_sac_policy_forward` against float64 torch."""
+    from tianshou_amd import _lib
+
+    obs_dim, act_dim, B = 23, 5, 96
+    eng, (actor, _, _) = make_engine(obs_dim, act_dim, 7, OS.SACConfig())
+    lib, ws = _lib.load(), _lib.Workspace(0)
+    _lib.check(lib.ts_sac_set_actor_bound(ws.handle, _lib.f64(2.0)))
+    _lib.check(lib.ts_mlp_set_hidden(ws.handle, _lib.i64(256)))
+    g = torch.Generator().manual_seed(3)
+    obs, noise = torch.randn(B, obs_dim, generator=g), torch.randn(B, act_dim, generator=g)
+    act = torch.empty((B, act_dim), dtype=torch.float32, device="cuda")
+    logp = torch.empty(B, dtype=torch.float32, device="cuda")
+    obs_d, noise_d = obs.cuda(), noise.cuda()
+    _lib.check(lib.ts_sac_policy_forward(ws.handle, _lib.ptr(eng.actor), _lib.ptr(obs_d), _lib.ptr(noise_d), _lib.i64(B),
+                                         _lib.i64(obs_dim), _lib.i64(act_dim), _lib.ptr(act), _lib.ptr(logp), None,
+                                         _lib.current_stream(torch.device("cuda"))))
+    torch.cuda.synchronize()
+    p64 = {k: v.double() for k, v in actor.items()}
+    r_act = OS.policy_forward(p64, obs.double(), noise.double(), 0.0)[0]
+    b_act = OS.policy_forward(p64, obs.double(), noise.double(), 2.0)[0]
+    assert rel_err(b_act, r_act) > 1e-3                                 # the bound would show
+    assert rel_err(act.cpu(), r_act) < 1e-5
+    # (log pi as test_policy_and_target_q_vs_oracle checks it: log(1 - tanh^2) of a nearly saturated action is ill-conditioned)
+    r_logp = OS.policy_forward(actor, obs, noise, 0.0)[1]
+    np.testing.assert_allclose(logp.cpu().numpy(), r_logp.flatten().numpy(), rtol=1e-5, atol=1e-5 * act_dim)
+
+
 def test_twin_critics_on_two_streams_with_generation_2():
     """hidden = 512 is not on the fused-MLP path, so the twin critics run their backward chains concurrently on the caller's
     stream and the workspace's side stream; with the second-generation kernels forced on, each chain transposes its

@@ -410,6 +410,10 @@ def test_hip_ppo_update_orchestration_with_engine_double(monkeypatch):
 # ------------------------------------------------------------------------------------ DQN / SAC subclasses
 @pytest.fixture(scope="module")
 def dqn_algo():
+    return _make_dqn_algo()
+
+
+def _make_dqn_algo():
     ref_shim.install()
     import gymnasium as gym
 
@@ -426,6 +430,10 @@ def dqn_algo():
 
 @pytest.fixture(scope="module")
 def sac_algo():
+    return _make_sac_algo()
+
+
+def _make_sac_algo():
     ref_shim.install()
     import gymnasium as gym
 
@@ -647,36 +655,65 @@ def _fill(buf, n, obs_shape, act, dtype=np.float32):
                       obs_next=np.zeros((2, *obs_shape), dtype)))
 
 
+class _FakeSAC:
+    """tianshou_amd.sac.SACEngine's interface on the CPU: every update adds 1 to the actor, 0.5 to its first Adam moment,
+    0.25 to log alpha, 0.125 to log alpha's first Adam moment and 0.125 to the lagged critics."""
+
+    def __init__(self, obs_dim, act_dim, actor, c1, c2, cfg, hidden=256, depth=2, max_action=0.0, activation="relu"):
+        assert hidden == 256
+        self.hidden = hidden
+        self.obs_dim, self.act_dim, self.cfg, self.adam_step = obs_dim, act_dim, cfg, 0
+        self.actor, self.critic1, self.critic2 = actor.clone(), c1.clone(), c2.clone()
+        self.critic1_old, self.critic2_old = c1.clone(), c2.clone()
+        _zeros_like_all(self, ("actor", "critic1", "critic2"))
+        self.log_alpha, self.log_alpha_m, self.log_alpha_v = torch.zeros(1), torch.zeros(1), torch.zeros(1)
+
+    def preprocess(self, m, idx, noise):
+        assert noise.shape == (idx.numel(), self.act_dim) and m.obs_next is not None
+        return torch.zeros(idx.numel())
+
+    def update_with_batch(self, obs, act, ret, noise, weight=None):
+        assert obs.shape == (8, self.obs_dim) and act.shape == (8, self.act_dim)
+        self.adam_step += 1
+        self.actor += 1.0
+        self.actor_m += 0.5
+        self.log_alpha += 0.25
+        self.log_alpha_m += 0.125
+        self.critic1_old += 0.125
+        return torch.tensor([1.0, 2.0, 3.0, 4.0, 5.0]), torch.ones(8)
+
+
+class _FakeDQN:
+    """tianshou_amd.dqn.DQNEngine's interface on the CPU: every update adds 2 to the parameters, 0.5 to the lagged network's and
+    0.25 to the second Adam moment."""
+
+    def __init__(self, c, h, w, n_act, flat, cfg):
+        self.c, self.h, self.w, self.n_act, self.cfg = c, h, w, n_act, cfg
+        self.params, self.params_old = flat.clone(), flat.clone()
+        self.adam_m, self.adam_v, self.adam_step, self.iter = torch.zeros_like(flat), torch.zeros_like(flat), 0, 0
+
+    def preprocess_with_obs(self, m, frames, idx, stack, obs_next_frames=None, prefetch=True):
+        assert frames.dtype == torch.uint8 and stack == 1 and obs_next_frames is not None and prefetch
+        return frames[idx].permute(0, 2, 3, 1), torch.zeros(idx.numel())
+
+    def update_with_batch(self, obs, act, ret, weight=None):
+        assert obs.shape == (8, 84, 84, 4) and obs.dtype == torch.uint8
+        self.adam_step += 1
+        self.iter += 1
+        self.params += 2.0
+        self.params_old += 0.5
+        self.adam_v += 0.25
+        return torch.tensor([0.75]), torch.arange(8, dtype=torch.float32)
+
+
 def test_hip_sac_wrapper_runs_with_engine_double(sac_algo, monkeypatch):
     from tianshou.algorithm.modelfree.sac import SACTrainingStats
     from tianshou.data import VectorReplayBuffer
     from tianshou.utils.torch_utils import policy_within_training_step
     import tianshou_amd.sac as S
 
-    class FakeSAC:
-        def __init__(self, obs_dim, act_dim, actor, c1, c2, cfg, hidden=256, depth=2, max_action=0.0, activation="relu"):
-            assert hidden == 256
-            self.hidden = hidden
-            self.obs_dim, self.act_dim, self.cfg, self.adam_step = obs_dim, act_dim, cfg, 0
-            self.actor, self.critic1, self.critic2 = actor.clone(), c1.clone(), c2.clone()
-            self.critic1_old, self.critic2_old = c1.clone(), c2.clone()
-            _zeros_like_all(self, ("actor", "critic1", "critic2"))
-            self.log_alpha, self.log_alpha_m, self.log_alpha_v = torch.zeros(1), torch.zeros(1), torch.zeros(1)
-
-        def preprocess(self, m, idx, noise):
-            assert noise.shape == (idx.numel(), self.act_dim) and m.obs_next is not None
-            return torch.zeros(idx.numel())
-
-        def update_with_batch(self, obs, act, ret, noise, weight=None):
-            assert obs.shape == (8, self.obs_dim) and act.shape == (8, self.act_dim)
-            self.adam_step += 1
-            self.actor += 1.0
-            self.actor_m += 0.5
-            self.log_alpha += 0.25
-            return torch.tensor([1.0, 2.0, 3.0, 4.0, 5.0]), torch.ones(8)
-
     _patch_for_cpu(monkeypatch)
-    monkeypatch.setattr(S, "SACEngine", FakeSAC)
+    monkeypatch.setattr(S, "SACEngine", _FakeSAC)
     buf = VectorReplayBuffer(32, 2)
     _fill(buf, 12, (11,), np.zeros((2, 3), np.float32))
     sac_algo._hip_engine = None
@@ -699,26 +736,8 @@ def test_hip_dqn_wrapper_runs_with_engine_double(dqn_algo, monkeypatch):
     from tianshou.utils.torch_utils import policy_within_training_step
     import tianshou_amd.dqn as D
 
-    class FakeDQN:
-        def __init__(self, c, h, w, n_act, flat, cfg):
-            self.c, self.h, self.w, self.n_act, self.cfg = c, h, w, n_act, cfg
-            self.params, self.params_old = flat.clone(), flat.clone()
-            self.adam_m, self.adam_v, self.adam_step, self.iter = torch.zeros_like(flat), torch.zeros_like(flat), 0, 0
-
-        def preprocess_with_obs(self, m, frames, idx, stack, obs_next_frames=None, prefetch=True):
-            assert frames.dtype == torch.uint8 and stack == 1 and obs_next_frames is not None and prefetch
-            return frames[idx].permute(0, 2, 3, 1), torch.zeros(idx.numel())
-
-        def update_with_batch(self, obs, act, ret, weight=None):
-            assert obs.shape == (8, 84, 84, 4) and obs.dtype == torch.uint8
-            self.adam_step += 1
-            self.iter += 1
-            self.params += 2.0
-            self.adam_v += 0.25
-            return torch.tensor([0.75]), torch.arange(8, dtype=torch.float32)
-
     _patch_for_cpu(monkeypatch)
-    monkeypatch.setattr(D, "DQNEngine", FakeDQN)
+    monkeypatch.setattr(D, "DQNEngine", _FakeDQN)
     monkeypatch.setattr(D, "gather_obs_nhwc", lambda frames, m, idx, stack, as_u8=False: frames[idx].permute(0, 2, 3, 1))
     buf = VectorReplayBuffer(32, 2)
     _fill(buf, 12, (4, 84, 84), np.zeros(2, np.int64), np.uint8)
@@ -1882,3 +1901,288 @@ def test_hip_sac_one_call_update_on_the_real_reference_classes(monkeypatch):
         two.update(buffer=buf2, sample_size=B)
     assert [c[0] for c in two._hip_engine.calls] == ["preprocess", "update_with_rows"]
     assert two._hip_engine.calls[0][2] == (B, act_dim) and two._hip_engine.calls[1][2] == (B, act_dim)
+
+
+# ------------------------------------------------------------------------------------ lazy write-back: state coherence (CPU doubles)
+# The CPU versions of tests/test_gpu_lazy_state.py's regressions: what a reader, `hip_invalidate()` and a checkpoint restore see
+# after lazy updates, on the real reference classes with the engine doubles above.
+def _lazy_twin(which, monkeypatch):
+    """-> (algorithm with the defaults: lazy write-back, index-only sampling; its buffer)."""
+    from tianshou.data import VectorReplayBuffer
+    import tianshou_amd.dqn as D
+    import tianshou_amd.sac as S
+
+    _patch_for_cpu(monkeypatch)
+    buf = VectorReplayBuffer(32, 2)
+    if which == "dqn":
+        monkeypatch.setattr(D, "DQNEngine", _FakeDQN)
+        monkeypatch.setattr(D, "gather_obs_nhwc", lambda frames, m, idx, stack, as_u8=False: frames[idx].permute(0, 2, 3, 1))
+        _fill(buf, 12, (4, 84, 84), np.zeros(2, np.int64), np.uint8)
+        algo = _make_dqn_algo()
+    else:
+        monkeypatch.setattr(S, "SACEngine", _FakeSAC)
+        _fill(buf, 12, (11,), np.zeros((2, 3), np.float32))
+        algo = _make_sac_algo()
+    assert algo.__dict__["_hip_lazy"]
+    return algo, buf
+
+
+def _run_updates(algo, buf, k):
+    from tianshou.utils.torch_utils import policy_within_training_step
+
+    with policy_within_training_step(algo.policy):
+        for _ in range(k):
+            algo.update(buffer=buf, sample_size=8)
+
+
+def _values(mod):
+    return [p.detach().clone() for p in mod.parameters()]
+
+
+_READERS = {
+    "algorithm_state_dict": lambda algo, mod: algo.state_dict(),
+    "policy_state_dict": lambda algo, mod: algo.policy.state_dict(),
+    "module_state_dict": lambda algo, mod: mod.state_dict(),
+    # (`copy.deepcopy` goes through the policy's `__reduce__` as pickling does; the shimmed gymnasium spaces are local classes)
+    "copy_policy": lambda algo, mod: __import__("copy").deepcopy(algo.policy),
+    "hip_sync": lambda algo, mod: algo.hip_sync(),
+}
+
+
+@pytest.mark.parametrize("reader", list(_READERS))
+@pytest.mark.parametrize("which", ["dqn", "sac"])
+def test_foreign_load_then_a_reader_keeps_what_was_loaded(which, reader, monkeypatch):
+    """Lazy updates pending, `load_state_dict(best)` on a sub-module, then a reader with no update in between: the loaded module
+    holds exactly `best`, every other module and the optimizer state hold what the engine learnt, and the next update continues
+    from `best` -- what eager write-back shows.  (Before: the reader wrote the engine's weights over the loaded ones.)"""
+    algo, buf = _lazy_twin(which, monkeypatch)
+    if which == "dqn":
+        mod, learner, lagged, opt = algo.policy.model, None, algo.model_old, algo.optim._optim
+        first = next(iter(mod.parameters()))
+    else:
+        mod, learner, lagged, opt = algo.critic, algo.policy.actor, algo.critic_old.module, algo.policy_optim._optim
+        first = next(iter(learner.parameters()))
+    learner0, lagged0 = (_values(learner) if learner is not None else None), _values(lagged)
+    _run_updates(algo, buf, 2)
+    best = {k: torch.full_like(v, 7.0) for k, v in mod.named_parameters()}       # (mod.state_dict() would be a reader)
+    mod.load_state_dict(best)
+    assert algo.__dict__["_hip_stale"]                               # updates still pending
+    _READERS[reader](algo, mod)
+    assert not algo.__dict__["_hip_stale"]
+    assert all(torch.equal(v, best[k]) for k, v in mod.state_dict().items())
+    lag = 0.5 if which == "dqn" else 0.125
+    assert all(torch.allclose(p, p0 + 2 * lag) for p, p0 in zip(_values(lagged), lagged0))      # the lagged network: learnt
+    st = opt.state[first]
+    assert float(st["step"]) == 2.0
+    if which == "dqn":
+        assert torch.allclose(st["exp_avg_sq"], torch.full_like(st["exp_avg_sq"], 0.5))
+    else:
+        assert all(torch.allclose(p, p0 + 2.0) for p, p0 in zip(_values(learner), learner0))
+        assert torch.allclose(st["exp_avg"], torch.full_like(st["exp_avg"], 1.0))
+        assert abs(float(algo.alpha._log_alpha) - 0.5) < 1e-6
+    _run_updates(algo, buf, 1)                                       # continues from `best` and from the learnt optimizer state
+    algo.hip_sync()
+    assert float(opt.state[first]["step"]) == 3.0
+    if which == "dqn":
+        assert all(torch.allclose(p, torch.full_like(p, 9.0)) for p in mod.parameters())
+    else:
+        assert all(torch.equal(v, best[k]) for k, v in mod.state_dict().items())
+        assert all(torch.allclose(p, p0 + 3.0) for p, p0 in zip(_values(learner), learner0))
+
+
+def test_hip_invalidate_with_updates_pending_raises_and_loses_nothing(monkeypatch):
+    """`hip_invalidate()` cannot tell a `.data` edit from the updates the engine still holds: with lazy updates pending it raises
+    and drops nothing.  `hip_sync()` then `hip_invalidate()` equals eager write-back's `hip_invalidate()`, and so does the next
+    update (rebuilt from the torch state: parameters and Adam state continue)."""
+    algo, buf = _lazy_twin("dqn", monkeypatch)
+    first = next(iter(algo.policy.model.parameters()))
+    before = first.detach().clone()
+    _run_updates(algo, buf, 2)
+    eng = algo.__dict__["_hip_engine_obj"]
+    with pytest.raises(RuntimeError, match="hip_sync"):
+        algo.hip_invalidate()
+    assert algo.__dict__["_hip_engine_obj"] is eng and algo.__dict__["_hip_stale"]            # nothing was dropped
+    assert torch.equal(first.detach(), before)
+    algo.hip_sync()
+    assert torch.allclose(first.detach(), before + 4.0)
+    algo.hip_invalidate()                                            # nothing pending now: drops the engine
+    assert algo.__dict__["_hip_engine_obj"] is None and torch.allclose(first.detach(), before + 4.0)
+    st = algo.optim._optim.state[first]
+    assert float(st["step"]) == 2.0 and torch.allclose(st["exp_avg_sq"], torch.full_like(st["exp_avg_sq"], 0.5))
+    _run_updates(algo, buf, 1)
+    assert algo.__dict__["_hip_engine_obj"] is not eng
+    algo.hip_sync()
+    st = algo.optim._optim.state[first]
+    assert torch.allclose(first.detach(), before + 6.0)
+    assert float(st["step"]) == 3.0 and torch.allclose(st["exp_avg_sq"], torch.full_like(st["exp_avg_sq"], 0.75))
+
+
+def test_hip_invalidate_without_the_optimizer_keeps_the_optimizer_state_the_caller_loaded(monkeypatch):
+    """`hip_invalidate(keep_optimizer=False)` after the caller replaced parameters (a sub-module load) AND the optimizer state:
+    nothing of the engine is written into torch.optim -- neither by the drop nor by the version check of the load.  With lazy
+    updates pending it raises without writing anything; after `hip_sync()` first, the caller's state is what the next update
+    starts from."""
+    algo, buf = _lazy_twin("dqn", monkeypatch)
+    model, opt = algo.policy.model, algo.optim._optim
+    sevens = {k: torch.full_like(v, 7.0) for k, v in model.named_parameters()}
+    _run_updates(algo, buf, 2)
+    model.load_state_dict(sevens)                                    # (no sync first: updates are pending)
+    opt.state.clear()
+    with pytest.raises(RuntimeError, match="hip_sync"):
+        algo.hip_invalidate(keep_optimizer=False)
+    assert not opt.state and all(torch.equal(p.detach(), sevens[k]) for k, p in model.named_parameters())   # nothing written
+    algo, buf = _lazy_twin("dqn", monkeypatch)                       # the recipe: hip_sync() before replacing the state
+    model, opt = algo.policy.model, algo.optim._optim
+    first = next(iter(model.parameters()))
+    old_before = _values(algo.model_old)
+    _run_updates(algo, buf, 2)
+    algo.hip_sync()
+    model.load_state_dict(sevens)
+    opt.state.clear()
+    algo.hip_invalidate(keep_optimizer=False)
+    assert algo.__dict__["_hip_engine_obj"] is None and not opt.state
+    assert all(torch.equal(p.detach(), sevens[k]) for k, p in model.named_parameters())
+    assert all(torch.allclose(p, p0 + 1.0) for p, p0 in zip(_values(algo.model_old), old_before))     # the lagged network: learnt
+    _run_updates(algo, buf, 1)                                       # the engine starts from the caller's (empty) optimizer state
+    algo.hip_sync()
+    st = opt.state[first]
+    assert float(st["step"]) == 1.0 and torch.allclose(st["exp_avg_sq"], torch.full_like(st["exp_avg_sq"], 0.25))
+    assert torch.allclose(first.detach(), torch.full_like(first, 9.0))
+
+
+def test_algorithm_load_with_updates_pending_keeps_what_the_checkpoint_does_not_hold(monkeypatch):
+    """`algorithm.load_state_dict(ckpt)` with lazy updates pending: everything the checkpoint holds is the checkpoint's, and
+    what it does not hold -- AutoAlpha's optimizer, which is outside `Algorithm._optimizers` (sac.py:193,
+    algorithm_base.py:523-543) -- keeps what the engine learnt, as under eager write-back (the load syncs first)."""
+    algo, buf = _lazy_twin("sac", monkeypatch)
+    ckpt = _make_sac_algo().state_dict()
+    _run_updates(algo, buf, 2)
+    assert algo.__dict__["_hip_stale"]
+    algo.load_state_dict(dict(ckpt))
+    sd = algo.state_dict()
+    for k, v in ckpt.items():
+        if isinstance(v, torch.Tensor):
+            assert torch.equal(sd[k], v), k
+    assert sd["_optimizers"] == ckpt["_optimizers"]                  # (the fresh algorithm's: no Adam state yet)
+    st = algo.alpha._optim.state[algo.alpha._log_alpha]
+    assert float(st["step"]) == 2.0 and torch.allclose(st["exp_avg"], torch.full_like(st["exp_avg"], 0.25))
+
+
+def test_data_edit_recipe_keeps_the_learning_and_the_edit(monkeypatch):
+    """The documented recipe for a `.data` edit under lazy write-back -- `hip_sync()`, the edit, `hip_invalidate()` -- keeps both
+    what the engine learnt and the edit; and the collector forward's flat copy of the torch parameters (used while no engine
+    exists, keyed on data pointers and version counters, which a `.data` edit changes neither of) is rebuilt after it."""
+    algo, buf = _lazy_twin("dqn", monkeypatch)
+    model = algo.policy.model
+    weight, bias = model.net[0][0].weight, model.net[0][0].bias
+    w0, b0 = weight.detach().clone(), bias.detach().clone()
+    _run_updates(algo, buf, 2)
+    algo.hip_sync()
+    bias.data.add_(5.0)
+    algo.hip_invalidate()
+    _run_updates(algo, buf, 1)
+    algo.hip_sync()
+    assert torch.allclose(weight.detach(), w0 + 6.0) and torch.allclose(bias.detach(), b0 + 11.0)
+    assert float(algo.optim._optim.state[weight]["step"]) == 3.0
+    algo.hip_invalidate()                                            # no engine from here on: the collector reads the torch modules
+    builds = []
+    flat = lambda: algo.policy._hip_cached([model], lambda: (builds.append(1), bias.detach().clone())[1])  # noqa: E731
+    v1 = flat()
+    assert torch.equal(flat(), v1) and len(builds) == 1              # cached while nothing changes
+    bias.data.add_(1.0)
+    algo.hip_invalidate()
+    assert torch.equal(flat(), v1 + 1.0) and len(builds) == 2
+
+
+def test_hip_ppo_extra_state_restores_in_either_order(monkeypatch):
+    """HipPPO's run state beside `state_dict()` -- the device-permutation key and the collector forward's sampling counter --
+    restored with `load_hip_extra_state()` before or after `load_state_dict()`: the same counters, and no "shuffle sequence
+    restarts" warning at the next update (before: loading the state dict second cleared the restored flag).  A checkpoint
+    without its extra state still warns; an extra state without the sampling counter (older builds) still loads."""
+    import warnings
+
+    import gymnasium as gym
+    from torch import nn
+    from torch.distributions import Independent, Normal
+
+    from tianshou.algorithm.modelfree.reinforce import ProbabilisticActorPolicy
+    from tianshou.algorithm.optim import AdamOptimizerFactory
+    from tianshou.utils.net.common import Net
+    from tianshou.utils.net.continuous import ContinuousActorProbabilistic, ContinuousCritic
+    import tianshou_amd.buffer as B
+    import tianshou_amd.integration as I
+
+    class FakePPO:
+        def __init__(self, obs_dim, act_dim, flat, cfg):
+            self.cfg, self.params, self.ret_rms = cfg, flat.clone(), [0.0, 1.0, 0.0]
+            self.adam_m, self.adam_v, self.adam_step = torch.zeros_like(flat), torch.zeros_like(flat), 0
+
+        def update(self, b, batch_size, repeat, perms):
+            self.adam_step += 1
+            return torch.zeros((1, 4)), 1
+
+        def check(self):
+            pass
+
+    monkeypatch.setattr(I, "PPOEngine", FakePPO)
+    monkeypatch.setattr(B, "random_permutation", lambda n, key, device: torch.randperm(n))
+
+    def build():
+        actor = ContinuousActorProbabilistic(preprocess_net=Net(state_shape=(17,), hidden_sizes=[64, 64], activation=nn.Tanh),
+                                             action_shape=(6,), unbounded=True)
+        critic = ContinuousCritic(preprocess_net=Net(state_shape=(17,), hidden_sizes=[64, 64], activation=nn.Tanh))
+        policy = ProbabilisticActorPolicy(actor=actor, dist_fn=lambda ls: Independent(Normal(*ls), 1), action_scaling=True,
+                                          action_bound_method="clip", action_space=gym.spaces.Box(low=-1.0, high=1.0, shape=(6,)))
+        algo = I.make_hip_ppo()(policy=policy, critic=critic, optim=AdamOptimizerFactory(lr=3e-4), device="cpu", perm_seed=3)
+        algo._hip_batch = {"obs": torch.zeros(16, 17)}
+        return algo
+
+    def update(algo):                                # the hook that consumes the key (the engine double stands for the kernels)
+        algo._update_with_batch(None, 8, 1)
+
+    a = build()
+    assert a.policy._hip_family == "gauss" and a.hip_extra_state()["policy_calls"] == 0
+    update(a)
+    a.policy.__dict__["_hip_rt_calls"] = 5           # five collector forwards with device sampling
+    sd, extra = a.state_dict(), a.hip_extra_state()
+    assert extra == {"perm_seed": 3, "updates": 1, "policy_calls": 5}
+    for order in ("extra_first", "state_dict_first"):
+        b = build()
+        if order == "extra_first":
+            b.load_hip_extra_state(extra)
+            b.load_state_dict(dict(sd))
+        else:
+            b.load_state_dict(dict(sd))
+            b.load_hip_extra_state(extra)
+        assert b.hip_extra_state() == extra, order
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")
+            update(b)
+        assert b._hip_updates == 2 and b._hip_engine.adam_step == 2, order
+    c = build()
+    c.load_state_dict(dict(sd))
+    with pytest.warns(UserWarning, match="device-permutation key"):
+        update(c)
+    d = build()
+    d.policy.__dict__["_hip_rt_calls"] = 2
+    d.load_hip_extra_state({"perm_seed": 3, "updates": 1})
+    assert d.hip_extra_state() == {"perm_seed": 3, "updates": 1, "policy_calls": 2}
+
+
+def test_hip_sac_extra_state_carries_both_noise_counters(monkeypatch):
+    """HipSAC's run state beside `state_dict()`: the update-noise counter of the engine's Philox stream and the collector forward's
+    sampling counter; restored in either order around `load_state_dict()`; an extra state without them leaves the counters."""
+    algo, buf = _lazy_twin("sac", monkeypatch)
+    algo._hip_noise_calls, algo.policy.__dict__["_hip_rt_calls"] = 12, 4
+    sd, extra = algo.state_dict(), algo.hip_extra_state()
+    assert extra == {"update_noise_calls": 12, "policy_calls": 4}
+    for first in (True, False):
+        b = _make_sac_algo()
+        if first:
+            b.load_hip_extra_state(extra)
+        b.load_state_dict(dict(sd))
+        if not first:
+            b.load_hip_extra_state(extra)
+        assert b.hip_extra_state() == extra
+    b.load_hip_extra_state({})
+    assert b.hip_extra_state() == extra

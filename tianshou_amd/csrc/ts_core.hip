@@ -193,6 +193,7 @@ int ts_mlp_set_hidden(ts_workspace* ws, int64_t hidden) {
     ws->mlp_hidden = (int)hidden;
     ws->mlp_depth = 0;
     ws->mlp_act_tanh = 0;
+    ws->sac_actor_bound = 0.f;          // (the trunk settings start over: unbounded, as depth and activation)
     return TS_OK;
 }
 

@@ -55,10 +55,14 @@ class _HipGlue:
     * `load_state_dict` on the algorithm replaces parameters / Adam moments / lagged networks / counters: the engine
       is dropped and rebuilt from the loaded torch state on the next update.  A load into a sub-module
       (`algorithm.policy.load_state_dict(best)`) replaces parameters only: it is noticed through the parameters'
-      version counters, the engine's Adam moments are first written into torch.optim and survive the rebuild.
+      version counters, the engine's Adam moments are first written into torch.optim and survive the rebuild.  Under lazy
+      write-back the same check runs in front of every reader (`hip_sync()`, `state_dict()`, pickling the policy): the
+      loaded module keeps what was loaded, every other module gets what the engine learnt.
     Only writes that bump a tensor's version counter are seen (`load_state_dict`, `param.copy_()`, in-place ops on the
     Parameter); writes through `param.data` (`param.data.copy_()`, optimizer-style `param.data.add_()`, `module.to()`) do
-    NOT bump it -- after such an edit call `algorithm.hip_invalidate()`.
+    NOT bump it -- call `algorithm.hip_sync()` before such an edit and `algorithm.hip_invalidate()` after it
+    (`hip_invalidate()` raises while lazy updates are pending).  A sub-module REPLACED after the engine was built
+    (`algorithm.policy.actor = new`) is not seen either: the same two calls go around the replacement.
     `_HIP_LR`: (engine cfg field, attribute path of the Algorithm.Optimizer wrapper that owns it)."""
     _HIP_LR: tuple = (("lr", "optim"),)
     _hip_dp_on = False            # classes whose constructor takes data_parallel= call _hip_dp_setup
@@ -159,7 +163,10 @@ class _HipGlue:
             self._hip_write_back()
 
     def hip_sync(self) -> None:
-        """Public: make the torch modules and optimizers current (no-op unless updates are pending under write_back="lazy")."""
+        """Public: make the torch modules and optimizers current (no-op unless updates are pending under write_back="lazy").
+        A foreign write since the last sync (`policy.load_state_dict(best)`) is honoured first: the `_hip_engine` property
+        writes what the engine learnt to every OTHER parameter, flushes the optimizer state and drops the engine."""
+        self._hip_engine                                  # noqa: B018 (the version check of the property)
         if self.__dict__.get("_hip_stale", False) and self.__dict__.get("_hip_engine_obj") is not None:
             self.__dict__["_hip_stale"] = False
             self.__dict__["_hip_in_update"] = True
@@ -273,16 +280,31 @@ class _HipGlue:
         self.__dict__["_hip_pdicts"] = self.__dict__["_hip_modules"] = None
         self.__dict__["_hip_stale"] = False
         self._hip_adam_dirty = False
+        # the collector forward's flat copy of the torch parameters is keyed on (data_ptr, _version): blind to `.data` edits too
+        pol = self.__dict__.get("_modules", {}).get("policy")
+        if pol is not None:
+            pol.__dict__.pop("_hip_rt_flat", None)
 
     def hip_invalidate(self, keep_optimizer: bool = True) -> None:
         """Public: the torch parameters were edited in a way the version check cannot see (`param.data` writes, `.to()`):
-        drop the engine so that the next update rebuilds it from the torch state.  keep_optimizer=True first writes the
-        engine's Adam moments / step counters into torch.optim (they survive the rebuild); False discards them (use after
-        replacing the optimizer state yourself)."""
+        drop the engine so that the next update (and the collector forward) rebuilds it from the torch state.
+        keep_optimizer=True first writes the engine's Adam moments / step counters into torch.optim (they survive the
+        rebuild); False discards them and writes nothing (use after replacing the optimizer state yourself).
+        Under lazy write-back the engine may hold updates the torch modules do not have yet, and an edit through `.data`
+        cannot be told apart from them: with updates pending this raises (nothing is dropped, nothing is written).  The
+        recipe is `hip_sync()`, then the edit, then `hip_invalidate()`; when the edit replaces the optimizer state too
+        (`optim.load_state_dict(o)`, then `hip_invalidate(keep_optimizer=False)`), `hip_sync()` comes before it, since
+        the sync writes the engine's moments into torch.optim."""
+        if keep_optimizer:
+            self._hip_engine                              # noqa: B018 (a version-visible foreign write is honoured first)
+        if self.__dict__.get("_hip_stale", False) and self.__dict__.get("_hip_engine_obj") is not None:
+            raise RuntimeError(f"{type(self).__name__}.hip_invalidate(): updates are pending in the engine (lazy write-back) and "
+                               "would be lost; call hip_sync() BEFORE editing parameters through `.data` or replacing the "
+                               "optimizer state, then hip_invalidate()")
         if keep_optimizer and self.__dict__.get("_hip_engine_obj") is not None:
             self.__dict__["_hip_versions"] = None
             self._hip_flush()
-        self._hip_invalidate()          # (pending lazy updates are dropped with the engine: the caller's edit of the torch state wins)
+        self._hip_invalidate()
 
     def _hip_flush(self) -> None:
         """Engine-side optimizer state -> torch.optim state; the default wrappers store it after every update."""
@@ -291,6 +313,12 @@ class _HipGlue:
         self.hip_sync()
         self._hip_flush()
         return super().state_dict(*args, **kwargs)
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        # lazy write-back: pending updates reach the torch state first, so that what the checkpoint does not replace keeps what
+        # the engine learnt, as under eager write-back (AutoAlpha's optimizer lives outside Algorithm._optimizers, sac.py:193)
+        self.hip_sync()
+        return super().load_state_dict(state_dict, *args, **kwargs)
 
     def _hip_refresh_lr(self) -> None:
         eng = self._hip_engine
@@ -311,6 +339,17 @@ class _HipGlue:
                 raise NotImplementedError(f"the HIP engine has one `{field}`; the optimizers sharing it disagree")
             setattr(eng.cfg, field, lr)
             opt._opt_called = True       # the engine performs this optimizer's step (LRScheduler.step's order check)
+
+
+def _policy_extra_state(algorithm) -> dict:
+    """The run state of the attached collector forward (tianshou_amd/policy.py) that no state_dict() holds: the call counter of
+    its device sampling noise.  Saved by `hip_extra_state()` so that a resumed run continues the noise sequence."""
+    return {"policy_calls": int(algorithm.policy.__dict__.get("_hip_rt_calls", 0))}
+
+
+def _load_policy_extra_state(algorithm, state: dict) -> None:
+    if "policy_calls" in state:                        # (extra states written before the counter was saved have none)
+        algorithm.policy.__dict__["_hip_rt_calls"] = int(state["policy_calls"])
 
 
 def optimizer_fields(opt) -> dict:
@@ -595,11 +634,13 @@ def make_hip_ppo(algo: str = "ppo", ref=None):
         # state_dict() stays in the reference's format (a HipPPO checkpoint loads into the reference PPO / A2C class with
         # strict=True, nested in a parent module or not); the (seed, update counter) pair of the device permutations is
         # saved / restored explicitly, e.g. torch.save({"model": algo.state_dict(), "hip": algo.hip_extra_state()}, f).
+        # The collector forward's sampling-noise counter (`sampling="device"`) travels with them.
         def hip_extra_state(self) -> dict:
-            return {"perm_seed": int(self._hip_perm_seed), "updates": int(self._hip_updates)}
+            return {"perm_seed": int(self._hip_perm_seed), "updates": int(self._hip_updates), **_policy_extra_state(self)}
 
         def load_hip_extra_state(self, state: dict) -> None:
             self._hip_perm_seed, self._hip_updates = int(state["perm_seed"]), int(state["updates"])
+            _load_policy_extra_state(self, state)
             self._hip_key_loaded = True
 
         def load_state_dict(self, state_dict, *args, **kwargs):
@@ -613,7 +654,8 @@ def make_hip_ppo(algo: str = "ppo", ref=None):
                     if k == "_hip_perm_state":
                         self._hip_perm_seed, self._hip_updates = int(st[0]), int(st[1])
             out = super().load_state_dict(state_dict, *args, **kwargs)
-            self._hip_key_loaded = "_hip_perm_state" in legacy        # (checked at the next update, see _update_with_batch)
+            if self.__dict__.get("_hip_key_loaded") is not True:          # (load_hip_extra_state() may come first)
+                self._hip_key_loaded = "_hip_perm_state" in legacy        # (checked at the next update, see _update_with_batch)
             return out
 
         def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
@@ -1716,6 +1758,17 @@ def make_hip_sac(ref=None):
             if self._hip_host_batch or buffer is None:
                 return super().update(buffer, sample_size)
             return self._hip_offpolicy_update(buffer, sample_size, Batch)
+
+        # The call counters of the two Philox streams (update noise, collector sampling noise) are run state outside the
+        # reference's state_dict() format: saved / restored beside it, as HipPPO's shuffle key, so that a resumed run continues
+        # both sequences instead of replaying them from call 1.
+        def hip_extra_state(self) -> dict:
+            return {"update_noise_calls": int(self._hip_noise_calls), **_policy_extra_state(self)}
+
+        def load_hip_extra_state(self, state: dict) -> None:
+            if "update_noise_calls" in state:
+                self._hip_noise_calls = int(state["update_noise_calls"])
+            _load_policy_extra_state(self, state)
 
         def _hip_rsample_noise(self, n, a):
             """eps of one Normal.rsample() call of the reference (sac.py:124-131): torch's host generator ("torch": the
