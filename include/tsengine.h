@@ -210,6 +210,12 @@ int ts_normal_fill(float* out, int64_t n, uint64_t seed, uint64_t offset, ts_str
  * caller does not supply the reference's): out float64[n], out[i] = the 53-bit double in [0, 1) of Philox-4x32-10 keyed by
  * `seed` at counter (i, `counter`) -- the draw ts_sample_indices_seeded makes for its buffer choice. */
 int ts_uniform_fill_f64(double* out, int64_t n, uint64_t seed, uint64_t counter, ts_stream_t stream);
+/* torch.rand(batch_size, sample_size) of the engine's own stream (the fractions ImplicitQuantileNetwork.forward draws,
+ * tianshou/utils/net/discrete.py:210, when the caller does not supply the reference's): out float32[n] in [0, 1), out[i] =
+ * the top 24 bits of word 0 of the Philox-4x32-10 block ts_uniform_fill_f64 uses at counter (i, `counter`), times 2^-24.
+ * Not torch's generator stream: every ts_iqn_* entry point takes its fractions as an input, so a seeded reference run is
+ * reproduced by passing its draws (the rule ts_normal_fill states). */
+int ts_uniform_fill_f32(float* out, int64_t n, uint64_t seed, uint64_t counter, ts_stream_t stream);
 
 /* ReplayBuffer.__getitem__ row gather (buffer_base.py:605-649): out[i,:] = src[index[i],:]
  * for a row of `row_bytes` bytes (any dtype).  16-byte vector path when row_bytes % 16 == 0
@@ -805,6 +811,63 @@ int ts_distq_update(ts_workspace* ws, float* params, float* adam_m, float* adam_
                     const void* obs_nhwc, int obs_u8, const int64_t* act, const float* returns, const float* next_dist,
                     const float* weight, int64_t B, const ts_distq_hparams* hp, float* prio_out, float* loss_out,
                     float* target_dist_out, float* grad_out, ts_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * IQN (tianshou/algorithm/modelfree/iqn.py) on ImplicitQuantileNetwork (tianshou/utils/net/discrete.py:163-216) with
+ * preprocess_net = DQNet(features_only=True), hidden_sizes = [512] (examples/atari/atari_iqn.py):
+ *   feat[b]  = the DQNet trunk's F = 64 * OH3 * OW3 features
+ *   phi[r]   = relu(cos(tau[r] * pi * (1 .. n_cos)) @ We + be)       r = b * N + n  (CosineEmbeddingNetwork, :144-160)
+ *   out[r]   = relu((feat[b] * phi[r]) @ W1 + b1) @ W2 + b2;   logits[b, a, n] = out[b * N + n, a];   Q = mean_n logits
+ * The fractions `tau` (device float32[B * N], row-major [B, N], in [0, 1)) are an INPUT of every entry point: the
+ * reference draws them with torch.rand inside the model (:210); pass its draws to reproduce it, or ts_uniform_fill_f32's.
+ * Flat parameters: conv1 | conv2 | conv3 (ts_dqn layout) | [We; be] [n_cos + 1, F] | [W1; b1] [F + 1, 512] | [W2; b2]
+ * [513, ld]; F in (h, w, c) order, ld = n_act rounded up to a multiple of 32, padding columns are (and stay) zero.
+ * Limits (TS_ERR_INVALID_ARG otherwise): 1 <= n_act <= 64, 2 <= N, N' <= 64, n_cos = 64, hidden 512.
+ * ------------------------------------------------------------------------------------------- */
+int64_t ts_iqn_param_count(int64_t c, int64_t h, int64_t w, int64_t n_act, int64_t n_cos);
+/* h_out9 (host): {F, ld, total, offsets of conv1, conv2, conv3, [We; be], [W1; b1], [W2; b2]} */
+int ts_iqn_layout(int64_t c, int64_t h, int64_t w, int64_t n_act, int64_t n_cos, int64_t* h_out9);
+
+/* The cosine-embedding kernels on their own (parity tests, benchmarks): x_out[b * N + n, :] = feat[b, :] * phi[b * N + n, :]
+ * from tau float32[B * N], feat float32[B, F], we_be float32[n_cos + 1, F] (F a multiple of 64); and its backward pass
+ * from dx float32[B * N, F]: dfeat_out[b, :] = 1{feat > 0} * sum_n dx * phi (the gradient conv3's backward pass takes),
+ * dwe_be_out float32[n_cos + 1, F] = [d We; d be].
+ * `route`: TS_IQN_ROUTE_DEFAULT = the route the network entry points take (the faster one as measured);
+ * _FUSED = the one-launch kernels of ts_iqn.hip; _UNFUSED = cosine kernel + the generic GEMM kernels + an elementwise pass
+ * (fewer than 16384 rows).  Both routes meet the same parity bar; each is deterministic on its own. */
+#define TS_IQN_ROUTE_DEFAULT 0
+#define TS_IQN_ROUTE_FUSED 1
+#define TS_IQN_ROUTE_UNFUSED 2
+int ts_iqn_embed_mul(ts_workspace* ws, const float* tau, const float* feat, const float* we_be, int64_t B, int64_t N,
+                     int64_t F, int64_t n_cos, int route, float* x_out, ts_stream_t stream);
+int ts_iqn_embed_mul_backward(ts_workspace* ws, const float* tau, const float* feat, const float* we_be, const float* dx,
+                              int64_t B, int64_t N, int64_t F, int64_t n_cos, int route, float* dfeat_out, float* dwe_be_out,
+                              ts_stream_t stream);
+
+/* ImplicitQuantileNetwork.forward + IQNPolicy.forward (iqn.py:72-100): logits_out float32[B, n_act, N], q_out
+ * float32[B, n_act] = mean over the N fractions, act_out int64[B] = the first maximum of q; each nullable. */
+int ts_iqn_forward(ts_workspace* ws, const float* params, int64_t c, int64_t h, int64_t w, int64_t n_act, int64_t n_cos,
+                   const void* obs_nhwc, int obs_u8, int64_t B, const float* tau, int64_t N, float* logits_out,
+                   float* q_out, int64_t* act_out, ts_stream_t stream);
+
+/* QRDQN._target_q (qrdqn.py:94-106) with IQNPolicy.forward's sample sizes: the greedy action of the online net on obs_next
+ * with tau_online float32[B * N]; the quantiles of that action under params_old with tau_target float32[B * N_target]
+ * -> out float32[B, N_target].  params_old == NULL (no target network): one pass serves both, tau_target / N_target are
+ * ignored and out is float32[B, N]. */
+int ts_iqn_next_dist(ts_workspace* ws, const float* params, const float* params_old, int64_t c, int64_t h, int64_t w,
+                     int64_t n_act, int64_t n_cos, const void* obs_next_nhwc, int obs_u8, int64_t B,
+                     const float* tau_online, int64_t N, const float* tau_target, int64_t N_target, float* out,
+                     ts_stream_t stream);
+
+/* IQN._update_with_batch (iqn.py:156-183) after the periodic sync: forward with tau float32[B * N], quantile Huber loss
+ * against returns float32[B, N_target] = batch.returns weighted by |tau - 1{d <= 0}|, backward, clip_grad_norm_ + Adam.
+ * weight float32[B] nullable; prio_out float32[B] = the new batch.weight (iqn.py:180); loss_out float32[1]; grad_out
+ * nullable: the flat gradient; hp->lr < 0: gradient only (hp->v_min / v_max unused).  act int64[B]: values outside
+ * [0, n_act) are clamped into it. */
+int ts_iqn_update(ts_workspace* ws, float* params, float* adam_m, float* adam_v, int64_t adam_step, int64_t c, int64_t h,
+                  int64_t w, int64_t n_act, int64_t n_cos, const void* obs_nhwc, int obs_u8, const int64_t* act,
+                  const float* returns, int64_t N_target, const float* tau, int64_t N, const float* weight, int64_t B,
+                  const ts_distq_hparams* hp, float* prio_out, float* loss_out, float* grad_out, ts_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Rainbow (tianshou/algorithm/modelfree/rainbow.py): C51 on RainbowNet (env/atari/atari_network.py:154-208) -- DQNet

@@ -51,3 +51,19 @@ def store_adam_state(opt: torch.optim.Optimizer, params: list[torch.nn.Parameter
 def params_by_keys(module: torch.nn.Module, keys) -> list[torch.nn.Parameter]:
     named = dict(module.named_parameters())
     return [named[k] for k in keys]
+
+
+def iqn_engine_state(eng) -> dict:
+    """Everything a resumed `iqn.IQNEngine` needs: flat tensors (host copies) and its counters -- the fraction counter
+    included, so that the resumed run continues the engine's own fraction stream instead of replaying it."""
+    cpu = lambda t: None if t is None else t.detach().cpu().clone()  # noqa: E731
+    return {"params": cpu(eng.params), "params_old": cpu(eng.params_old), "adam_m": cpu(eng.adam_m), "adam_v": cpu(eng.adam_v),
+            **eng.extra_state()}
+
+
+def load_iqn_engine_state(eng, state: dict) -> None:
+    for name in ("params", "adam_m", "adam_v"):
+        getattr(eng, name).copy_(state[name])
+    if eng.params_old is not None and state.get("params_old") is not None:
+        eng.params_old.copy_(state["params_old"])
+    eng.load_extra_state(state)

@@ -652,6 +652,15 @@ __global__ __launch_bounds__(256) void uniform_fill_f64_kernel(double* __restric
     if (i < n) out[i] = uniform53(seed, counter, i, 0);
 }
 
+// torch.rand's stand-in for the IQN fractions: 24 random bits -> float32 in [0, 1) (exact: k * 2^-24, k < 2^24)
+__global__ __launch_bounds__(256) void uniform_fill_f32_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t counter) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        uint32_t c[4] = {(uint32_t)i, (uint32_t)((uint64_t)i >> 32), (uint32_t)counter, (uint32_t)(counter >> 32)};
+        philox10(c, seed);
+        out[i] = (float)(c[0] >> 8) * (1.0f / 16777216.0f);
+    }
+}
+
 __global__ __launch_bounds__(256) void normal_fill_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t offset) {
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (4 * q >= n) return;
@@ -788,6 +797,15 @@ int ts_normal_fill(float* out, int64_t n, uint64_t seed, uint64_t offset, ts_str
     TS_REQUIRE(out != nullptr, TS_ERR_INVALID_ARG, "ts_normal_fill: out is NULL");
     hipLaunchKernelGGL(normal_fill_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, ts::as_stream(stream), out, n,
                        seed, offset);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+int ts_uniform_fill_f32(float* out, int64_t n, uint64_t seed, uint64_t counter, ts_stream_t stream) {
+    TS_REQUIRE(n >= 0, TS_ERR_INVALID_ARG, "ts_uniform_fill_f32: negative n");
+    if (n == 0) return TS_OK;
+    TS_REQUIRE(out != nullptr, TS_ERR_INVALID_ARG, "ts_uniform_fill_f32: out is NULL");
+    hipLaunchKernelGGL(uniform_fill_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ts::as_stream(stream), out, n, seed, counter);
     TS_LAUNCH_CHECK();
     return TS_OK;
 }

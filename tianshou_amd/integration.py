@@ -1535,6 +1535,152 @@ def make_hip_c51(ref=None):
     `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
     return _make_hip_distq("c51", ref)
 
+def make_hip_iqn(ref=None):
+    """Returns HipIQN(IQN): `_preprocess_batch` / `_update_with_batch` (dqn.py:257-275 with qrdqn.py:94-106, iqn.py:156-183) on
+    the engine (tianshou_amd/iqn.py).  Supported model: ImplicitQuantileNetwork(preprocess_net=DQNet(features_only=True),
+    hidden_sizes=[512], num_cosines=64) as examples/atari/atari_iqn.py builds it, Adam; buffer layouts as HipDQN.  The sample
+    sizes come from the policy (`online_sample_size`, `target_sample_size`).  The collector's `policy.forward` stays on torch.
+    `hip_taus`: a callable, or an iterator, that yields the fraction tensors [B, N] in the reference's call order (target pass:
+    online net, then lagged net if there is one; update pass: online net) -- a seeded reference run is replayed by passing
+    its draws; without it the engine draws from its own stream (`hip_seed`, counter saved by `hip_extra_state()`).
+    `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    from . import dqn as D
+    from . import iqn as I
+
+    SimpleLossTrainingStats = _ref(ref, "tianshou.algorithm.modelfree.reinforce", "SimpleLossTrainingStats")
+    Base = _ref(ref, "tianshou.algorithm.modelfree.iqn", "IQN")
+    supported = ("HipIQN: the model must be ImplicitQuantileNetwork(preprocess_net=DQNet(features_only=True), "
+                 "hidden_sizes=[512], num_cosines=64)")
+
+    class HipIQN(_HipGlue, Base):
+        def __init__(self, *args, device="cuda", hip_taus=None, hip_seed=0, **kwargs):
+            super().__init__(*args, **kwargs)
+            self._hip_device = torch.device(device)
+            self._hip_check_model()
+            _adam_of(self.optim)
+            self._hip_taus = hip_taus
+            self._hip_seed = int(hip_seed)
+            self._hip_tau_counter = 0
+            self._hip_engine = None
+            self._hip_glue_init()
+
+        def _hip_check_model(self) -> None:
+            sd = self.policy.model.state_dict()
+            if list(sd.keys()) != I.TIANSHOU_KEYS:
+                raise NotImplementedError(f"{supported}; got parameters {list(sd.keys())}")
+            shapes = [tuple(sd[k].shape) for k in I.TIANSHOU_KEYS]
+            convs_ok = (len(shapes[0]) == 4 and shapes[0][0] == 32 and shapes[0][2:] == (8, 8) and shapes[2] == (64, 32, 4, 4)
+                        and shapes[4] == (64, 64, 3, 3))
+            if not convs_ok:
+                raise NotImplementedError(f"{supported}; the preprocess_net is not the DQNet convolution trunk")
+            if shapes[6][0] != I.HIDDEN or shapes[8][1] != I.HIDDEN:
+                raise NotImplementedError(f"{supported}; got hidden width {shapes[6][0]}")
+            if shapes[10][1] != 64:
+                raise NotImplementedError(f"{supported}; got num_cosines = {shapes[10][1]}")
+            if not 1 <= shapes[8][0] <= 64:
+                raise NotImplementedError("HipIQN: 1 <= number of actions <= 64")
+            for name in ("online_sample_size", "target_sample_size"):
+                if not 2 <= int(getattr(self.policy, name)) <= 64:
+                    raise NotImplementedError(f"HipIQN: 2 <= policy.{name} <= 64")
+
+        # -- the fraction counter travels BESIDE the checkpoint (state_dict() stays in the reference's format) ----------
+        def hip_extra_state(self) -> dict:
+            eng = self.__dict__.get("_hip_engine_obj")
+            return {"tau_seed": int(self._hip_seed), "tau_counter": int(eng.tau_counter if eng is not None else self._hip_tau_counter)}
+
+        def load_hip_extra_state(self, state: dict) -> None:
+            self._hip_seed, self._hip_tau_counter = int(state["tau_seed"]), int(state["tau_counter"])
+            eng = self.__dict__.get("_hip_engine_obj")
+            if eng is not None:
+                eng.cfg.seed, eng.tau_counter = self._hip_seed, self._hip_tau_counter
+
+        def _hip_next_tau(self):
+            src = self._hip_taus
+            if src is None:
+                return None
+            t = src() if callable(src) else next(src)
+            return torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t, dtype=torch.float32,
+                                   device=self._hip_device)
+
+        def _engine(self, c, h, w):
+            if self._hip_engine is None:
+                sd = self.policy.model.state_dict()
+                n_act = int(sd[I.TIANSHOU_KEYS[8]].shape[0])
+                opt, g = _adam_of(self.optim)
+                cfg = I.IQNConfig(n_cos=64, sample_size=min(max(int(self.policy.sample_size), 2), 64),
+                                  online_sample_size=int(self.policy.online_sample_size),
+                                  target_sample_size=int(self.policy.target_sample_size), gamma=self.gamma, n_step=self.n_step,
+                                  target_update_freq=self.target_update_freq, lr=g["lr"], betas=tuple(g["betas"]),
+                                  adam_eps=g["eps"], max_grad_norm=self.optim._max_grad_norm, seed=self._hip_seed)
+                dev = self._hip_device
+                eng = I.IQNEngine(c, h, w, n_act, I.flat_from_torch([sd[k] for k in I.TIANSHOU_KEYS], c, h, w, n_act, 64, dev), cfg)
+                eng.iter = self._iter
+                eng.tau_counter = self._hip_tau_counter
+                ms, vs, step = adam_state(opt, params_by_keys(self.policy.model, I.TIANSHOU_KEYS))       # resume from a checkpoint
+                eng.adam_m = I.flat_from_torch(ms, c, h, w, n_act, 64, dev)
+                eng.adam_v = I.flat_from_torch(vs, c, h, w, n_act, 64, dev)
+                eng.adam_step = step
+                if eng.params_old is not None:
+                    old = getattr(self.model_old, "module", self.model_old).state_dict()       # EvalModeModuleWrapper
+                    eng.params_old = I.flat_from_torch([old[k] for k in I.TIANSHOU_KEYS], c, h, w, n_act, 64, dev)
+                self._hip_engine = eng
+            return self._hip_engine
+
+        @staticmethod
+        def _layout(buffer):
+            obs = np.asarray(buffer.obs)
+            stack = int(getattr(buffer, "stack_num", 1))
+            if stack > 1:
+                if obs.ndim != 3:
+                    raise NotImplementedError("HipIQN: frame stacking needs single [h, w] frames per slot")
+                return stack, obs.shape[1], obs.shape[2], stack
+            if obs.ndim != 4:
+                raise NotImplementedError("HipIQN: observations must be [c, h, w]")
+            return obs.shape[1], obs.shape[2], obs.shape[3], 1
+
+        def _preprocess_batch(self, batch, buffer, indices):
+            _require_gpu(self._hip_device, "HipIQN")
+            c, h, w, stack = self._layout(buffer)
+            eng = self._engine(c, h, w)
+            m = _mirror(self, buffer, self._hip_device)
+            idx = torch.as_tensor(np.asarray(indices, np.int64), device=self._hip_device)
+            tau_online = self._hip_next_tau()                                    # qrdqn.py:100 / :103
+            tau_target = self._hip_next_tau() if eng.params_old is not None else None      # qrdqn.py:101
+            batch.returns = eng.preprocess(m, m.obs, idx, stack, obs_next_frames=m.obs_next, tau_online=tau_online,
+                                           tau_target=tau_target)
+            self._hip_idx, self._hip_stack = idx, stack
+            self._hip_tau_counter = eng.tau_counter
+            if hasattr(batch, "weight"):
+                batch.weight = torch.as_tensor(np.asarray(batch.weight), dtype=torch.float32, device=self._hip_device)
+            return batch
+
+        def _update_with_batch(self, batch):
+            self._hip_refresh_lr()
+            eng, m = self._hip_engine, self._hip_mirror
+            idx, stack = self._hip_idx, self._hip_stack
+            weight = batch.pop("weight", None)
+            obs = D.gather_obs_nhwc(m.obs, m, idx, stack, as_u8=True)
+            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device)
+            loss, prio = eng.update_with_batch(obs, act, batch.returns, weight, tau=self._hip_next_tau())      # iqn.py:162
+            self._iter = eng.iter
+            self._hip_tau_counter = eng.tau_counter
+            batch.weight = prio                                                   # prio-buffer, iqn.py:180
+            dims = (eng.c, eng.h, eng.w, eng.n_act, eng.cfg.n_cos)
+            params = params_by_keys(self.policy.model, I.TIANSHOU_KEYS)
+            with torch.no_grad():
+                for p, t in zip(params, I.flat_to_torch(eng.params, *dims)):
+                    p.copy_(t)
+                if eng.params_old is not None:
+                    old_mod = getattr(self.model_old, "module", self.model_old)
+                    for p, t in zip(params_by_keys(old_mod, I.TIANSHOU_KEYS), I.flat_to_torch(eng.params_old, *dims)):
+                        p.copy_(t)
+            store_adam_state(self.optim._optim, params, I.flat_to_torch(eng.adam_m, *dims), I.flat_to_torch(eng.adam_v, *dims),
+                             eng.adam_step)
+            return SimpleLossTrainingStats(loss=float(loss.item()))
+
+    return HipIQN
+
+
 def make_hip_rainbow(ref=None):
     """Returns HipRainbow(RainbowDQN): `_preprocess_batch` / `_update_with_batch` (dqn.py:257-275, rainbow.py:93-101 ->
     c51.py:120-160) on the engine.  Supported model: RainbowNet(is_dueling=True, is_noisy=True)
