@@ -981,35 +981,31 @@ int ts_mlp_ppo_update(ts_workspace* ws, float* params, float* adam_m, float* ada
  * and stay zero.  h_out8 = {ka, kc, actor count, critic count, actor L2 offset, actor head offset,
  * critic L2 offset, critic head offset}.  act_dim <= 32. */
 int ts_sac_layout(int64_t obs_dim, int64_t act_dim, int64_t* h_out8);
-/* Net(hidden_sizes=[h, h]) with h other than 256 (utils/net/common.py:246-369 takes any): the hidden width is a property
- * of the WORKSPACE -- ts_mlp_set_hidden(ws, h) (h a multiple of 32 in [32, 1024]; 0 = 256) applies to every SAC / TD3 /
- * DDPG / REDQ entry point subsequently called with `ws`; the `_h` layout variants take it explicitly (no workspace there).
- * 256 runs on the fused three-layer kernels, other widths on the per-layer GEMM kernels; in the layouts above every
- * "256" / "257" then reads h / h + 1. */
-int ts_mlp_set_hidden(ts_workspace* ws, int64_t hidden);
-int ts_sac_layout_h(int64_t obs_dim, int64_t act_dim, int64_t hidden, int64_t* h_out8);
-/* Net(hidden_sizes=[h] * depth) for depth other than 2 (utils/net/common.py:246-369 takes any list; round 6): the number of
- * hidden layers is a property of the workspace too -- ts_mlp_set_trunk(ws, h, depth) (depth in [1, TS_MLP_MAX_HIDDEN_LAYERS];
- * 0 = 2) applies to every SAC / TD3 / DDPG / REDQ / DiscreteSAC entry point subsequently called with `ws`;
- * ts_mlp_set_hidden resets the depth to 2 (and the activation and the actor bound below to their defaults).  Flat vectors
- * then hold depth + 1 wb matrices back to back:
+/* Net(hidden_sizes=[h] * depth, activation=...) other than the examples' [256, 256] ReLU (utils/net/common.py:246-369 takes any
+ * list): every SAC / TD3 / DDPG / REDQ / DiscreteSAC entry point takes the trunk of its networks PER CALL, as a `const
+ * ts_mlp_trunk* trunk` behind its network-shape arguments; nothing about the networks is kept in the workspace.  trunk = NULL
+ * is the examples' networks: 256 wide, 2 hidden layers, ReLU, unbounded actor.  TS_NET_ACT_TANH is 0, so a zero-filled struct
+ * is a TANH trunk of the default width and depth -- pass NULL, or set `activation`, for the default ReLU one.  The `_h` layout
+ * variants take the width explicitly.  Flat vectors hold depth + 1 wb matrices back to back:
  *   L1 [k + 1, h] | L2 .. Ldepth [h + 1, h] each | head [h + 1, head_cols]
  * (k = the input width rounded up to 32; head_cols = 64 for SAC's / REDQ's Gaussian actor, 32 otherwise) -- for depth 2
- * exactly the layouts above.  ts_mlp_layout: h_out[0] = k, h_out[1 + i] = offset of linear layer i (i = 0 .. depth; the
- * head is layer `depth`), h_out[depth + 2] = the element count; h_out has depth + 3 entries.  Depth 2 at the widths the
- * fused three-layer kernels take runs on them; every other trunk runs layer by layer on the GEMM kernels (ReLU fused
- * into the forward GEMM's epilogue and into the input-gradient GEMM's mask). */
+ * exactly the layouts above, where every "256" / "257" then reads h / h + 1.  ts_mlp_layout: h_out[0] = k, h_out[1 + i] =
+ * offset of linear layer i (i = 0 .. depth; the head is layer `depth`), h_out[depth + 2] = the element count; h_out has
+ * depth + 3 entries.  Depth 2 ReLU at the widths the fused three-layer kernels take (256) runs on them; every other trunk
+ * runs layer by layer on the GEMM kernels (ReLU fused into the forward GEMM's epilogue and into the input-gradient GEMM's
+ * mask; tanh as a pass of its own). */
 #define TS_MLP_MAX_HIDDEN_LAYERS 6
-int ts_mlp_set_trunk(ts_workspace* ws, int64_t hidden, int64_t depth);
-/* Net(activation=nn.Tanh) in place of the default nn.ReLU (utils/net/common.py:246-369) for the same entry points: TS_NET_ACT_RELU
- * (default; ts_mlp_set_hidden / ts_mlp_set_trunk reset to it) or TS_NET_ACT_TANH after every hidden layer.  Tanh trunks always run
- * layer by layer (the fused three-layer kernels are ReLU). */
-int ts_mlp_set_activation(ts_workspace* ws, int activation);
-/* ContinuousActorProbabilistic(unbounded=False) -- the class default, utils/net/continuous.py:194, 230-231: mu = max_action *
- * tanh(mu) in front of SAC's / REDQ's Gaussian (the examples pass unbounded=True).  A property of the workspace like the trunk:
- * applies to every ts_sac_* / ts_redq_* entry point subsequently called with `ws` -- forward, target, update (the gradient goes
- * back through max_action * (1 - tanh^2)).  0 = unbounded (the default; ts_mlp_set_hidden / ts_mlp_set_trunk reset to it). */
-int ts_sac_set_actor_bound(ts_workspace* ws, double max_action);
+typedef struct ts_mlp_trunk {
+    int64_t hidden;      /* width of every hidden layer: a multiple of 32 in [32, 1024] (DiscreteSAC: [32, 2048]); 0 = 256 */
+    int32_t depth;       /* hidden layers: 1 .. TS_MLP_MAX_HIDDEN_LAYERS; 0 = 2 */
+    int32_t activation;  /* after every hidden layer: TS_NET_ACT_RELU or TS_NET_ACT_TANH, defined with ts_net_desc below
+                            (anything else: TS_ERR_UNSUPPORTED) */
+    double max_action;   /* ts_sac_* / ts_redq_* only (the others ignore it): > 0 = ContinuousActorProbabilistic(unbounded=False),
+                            the class default (utils/net/continuous.py:194, 230-231): mu = max_action * tanh(mu) in front of
+                            the Gaussian -- forward, target, update (the gradient goes back through max_action * (1 - tanh^2));
+                            0 = unbounded, as the examples pass */
+} ts_mlp_trunk;
+int ts_sac_layout_h(int64_t obs_dim, int64_t act_dim, int64_t hidden, int64_t* h_out8);
 int ts_mlp_layout(int64_t in_dim, int64_t hidden, int64_t depth, int64_t head_cols, int64_t* h_out);
 
 /* SACPolicy.forward (sac.py:108-131) with rsample() = loc + noise * scale; noise NULL = dist.mode
@@ -1017,20 +1013,20 @@ int ts_mlp_layout(int64_t in_dim, int64_t hidden, int64_t depth, int64_t head_co
  * (correct_log_prob_gaussian_tanh, sac.py:25-39); aux_out (nullable) float32[B, 3, act_dim] =
  * {a - mu, sigma, squashed}. */
 int ts_sac_policy_forward(ts_workspace* ws, const float* actor, const float* obs, const float* noise, int64_t B,
-                          int64_t obs_dim, int64_t act_dim, float* act_out, float* logp_out, float* aux_out,
-                          ts_stream_t stream);
+                          int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk, float* act_out, float* logp_out,
+                          float* aux_out, ts_stream_t stream);
 /* The same pass as the collector calls it (data/collector.py:735-741): mu_out / sigma_out (nullable) float32[B, act_dim] =
  * `logits` = (loc, scale) of the returned batch (sac.py:114, 125); no backward state is kept. */
 int ts_sac_policy_forward_logits(ts_workspace* ws, const float* actor, const float* obs, const float* noise, int64_t B,
-                                 int64_t obs_dim, int64_t act_dim, float* act_out, float* logp_out, float* mu_out,
-                                 float* sigma_out, ts_stream_t stream);
+                                 int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk, float* act_out, float* logp_out,
+                                 float* mu_out, float* sigma_out, ts_stream_t stream);
 
 /* ActorCriticOffPolicyAlgorithm._target_q + SAC._target_q_compute_value (ddpg.py:327-339, td3.py:94-102,
  * sac.py:290-296): a' ~ pi(s') with `noise`, min(Q1_old, Q2_old)(s', a') - alpha * log_prob -> out float32[B].
  * alpha = exp(*log_alpha) when log_alpha (device float32[1]) is given, else fixed_alpha. */
 int ts_sac_target_q(ts_workspace* ws, const float* actor, const float* critic1_old, const float* critic2_old,
                     const float* log_alpha, double fixed_alpha, const float* obs_next, const float* noise, int64_t B,
-                    int64_t obs_dim, int64_t act_dim, float* out, ts_stream_t stream);
+                    int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk, float* out, ts_stream_t stream);
 
 typedef struct ts_sac_state {  /* device pointers, all float32 */
     float *actor, *actor_m, *actor_v;
@@ -1056,8 +1052,8 @@ typedef struct ts_sac_hparams {
  * weight_out (nullable) float32[B] = (td1 + td2) / 2, the new PER weights (sac.py:306);
  * grads_out (nullable) = the three flat gradients {critic1, critic2, actor}. */
 int ts_sac_update(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, const float* obs, const float* act,
-                  const float* returns, const float* weight, const float* noise, int64_t B, int64_t obs_dim,
-                  int64_t act_dim, const ts_sac_hparams* hp, float* stats_out5, float* weight_out, float* grads_out,
+                  const float* returns, const float* weight, const float* noise, int64_t B, int64_t obs_dim, int64_t act_dim,
+                  const ts_mlp_trunk* trunk, const ts_sac_hparams* hp, float* stats_out5, float* weight_out, float* grads_out,
                   ts_stream_t stream);
 /* The same two operations reading their rows straight from the replay buffer's columns (row b of the minibatch = row rows[b] of
  * obs_buf / act_buf / obs_next_buf, float32 [slots, dim]; rew_buf float64 [slots], terminated_buf uint8 [slots]): the gathers
@@ -1069,11 +1065,11 @@ int ts_sac_update(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, c
 int ts_sac_returns_rows(ts_workspace* ws, const float* actor, const float* critic1_old, const float* critic2_old,
                         const float* log_alpha, double fixed_alpha, const float* obs_next_buf, const double* rew_buf,
                         const uint8_t* terminated_buf, const int64_t* rows, const float* noise, int64_t B, int64_t obs_dim,
-                        int64_t act_dim, double gamma, float* returns_out, ts_stream_t stream);
-int ts_sac_update_rows(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, const float* obs_buf, const float* act_buf,
-                       const int64_t* rows, const float* returns, const float* weight, const float* noise, int64_t B,
-                       int64_t obs_dim, int64_t act_dim, const ts_sac_hparams* hp, float* stats_out5, float* weight_out,
-                       ts_stream_t stream);
+                        int64_t act_dim, const ts_mlp_trunk* trunk, double gamma, float* returns_out, ts_stream_t stream);
+int ts_sac_update_rows(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, const float* obs_buf,
+                       const float* act_buf, const int64_t* rows, const float* returns, const float* weight,
+                       const float* noise, int64_t B, int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk,
+                       const ts_sac_hparams* hp, float* stats_out5, float* weight_out, ts_stream_t stream);
 /* One call per SAC update with n_step = 1 (round 6): OffPolicyAlgorithm.update's _preprocess_batch -> _update_with_batch
  * (algorithm_base.py:586-631; sac.py:281-336, ddpg.py:287-301, algorithm_base.py:785-817) = ts_sac_returns_rows(noise2[0]) followed
  * by ts_sac_update_rows(noise2[1]) on the same rows, bit-identical to the two calls (tests/test_gpu_sac.py).  On the one-launch
@@ -1093,8 +1089,9 @@ typedef struct ts_sac_replay {
 } ts_sac_replay;
 int ts_sac_learn_rows(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, const ts_sac_replay* replay,
                       const int64_t* rows, const float* weight, float* noise2, int fill_noise, uint64_t noise_seed,
-                      uint64_t noise_offset, int64_t B, int64_t obs_dim, int64_t act_dim, const ts_sac_hparams* hp, double gamma,
-                      float* returns_out, float* stats_out5, float* weight_out, ts_stream_t stream);
+                      uint64_t noise_offset, int64_t B, int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk,
+                      const ts_sac_hparams* hp, double gamma, float* returns_out, float* stats_out5, float* weight_out,
+                      ts_stream_t stream);
 
 /* One phase of ts_sac_update, for data-parallel replicas (tianshou_amd/distributed.py DataParallelSAC; the reference
  * has no distributed path): phase 1 = forward / loss / backward of both critics on the local batch,
@@ -1107,8 +1104,8 @@ int ts_sac_learn_rows(ts_workspace* ws, const ts_sac_state* st, int64_t adam_ste
  * bit-identical to ts_sac_update.  stats_out5 / weight_out as in ts_sac_update (each phase writes its own slots). */
 int ts_sac_update_phase(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, const float* obs, const float* act,
                         const float* returns, const float* weight, const float* noise, int64_t B, int64_t obs_dim,
-                        int64_t act_dim, const ts_sac_hparams* hp, int phase, float* stats_out5, float* weight_out,
-                        float* grads, ts_stream_t stream);
+                        int64_t act_dim, const ts_mlp_trunk* trunk, const ts_sac_hparams* hp, int phase, float* stats_out5,
+                        float* weight_out, float* grads, ts_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * DiscreteSAC (tianshou/algorithm/modelfree/discrete_sac.py): Categorical policy, twin critics that
@@ -1124,14 +1121,14 @@ int ts_dsac_layout(int64_t obs_dim, int64_t n_act, int64_t hidden, int64_t* h_ou
 
 /* DiscreteSACPolicy.forward (discrete_sac.py:53-67) up to the Categorical: logits_out float32[B, n_act]. */
 int ts_dsac_policy_forward(ts_workspace* ws, const float* actor, const float* obs, int64_t B, int64_t obs_dim,
-                           int64_t n_act, int64_t hidden, float* logits_out, ts_stream_t stream);
+                           int64_t n_act, const ts_mlp_trunk* trunk, float* logits_out, ts_stream_t stream);
 
 /* _target_q (ddpg.py:327-339) with _target_q_compute_value (discrete_sac.py:147-155):
  * out[b] = sum_a p(a|s') min(Q1_old, Q2_old)(s', a) + alpha H(p(.|s')); log_alpha (device, nullable) selects
  * alpha = exp(*log_alpha), else fixed_alpha. */
 int ts_dsac_target_q(ts_workspace* ws, const float* actor, const float* critic1_old, const float* critic2_old,
                      const float* log_alpha, double fixed_alpha, const float* obs_next, int64_t B, int64_t obs_dim,
-                     int64_t n_act, int64_t hidden, float* out, ts_stream_t stream);
+                     int64_t n_act, const ts_mlp_trunk* trunk, float* out, ts_stream_t stream);
 
 /* DiscreteSAC._update_with_batch (discrete_sac.py:157-196): critic 1 and 2 steps on (Q(s)[a] - returns)^2 * weight,
  * actor step on -(alpha H + sum_a p q).mean() with the updated critics, AutoAlpha.update(entropy) (sac.py:203-209),
@@ -1140,8 +1137,9 @@ int ts_dsac_target_q(ts_workspace* ws, const float* actor, const float* critic1_
  * weight_out (nullable) float32[B] = (td1 + td2) / 2 (discrete_sac.py:174);
  * grads_out (nullable) = the three flat gradients {critic1, critic2, actor}. */
 int ts_dsac_update(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, const float* obs, const int64_t* act,
-                   const float* returns, const float* weight, int64_t B, int64_t obs_dim, int64_t n_act, int64_t hidden,
-                   const ts_sac_hparams* hp, float* stats_out5, float* weight_out, float* grads_out, ts_stream_t stream);
+                   const float* returns, const float* weight, int64_t B, int64_t obs_dim, int64_t n_act,
+                   const ts_mlp_trunk* trunk, const ts_sac_hparams* hp, float* stats_out5, float* weight_out,
+                   float* grads_out, ts_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * REDQ (tianshou/algorithm/modelfree/redq.py): SAC's tanh-Gaussian policy + an ensemble of E critics whose
@@ -1154,7 +1152,8 @@ int ts_dsac_update(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, 
  * alpha * log_prob -> out float32[B]. */
 int ts_redq_target_q(ts_workspace* ws, const float* actor, const float* critics_old, int64_t E, const int32_t* h_subset,
                      int64_t S, int mean_mode, const float* log_alpha, double fixed_alpha, const float* obs_next,
-                     const float* noise, int64_t B, int64_t obs_dim, int64_t act_dim, float* out, ts_stream_t stream);
+                     const float* noise, int64_t B, int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk, float* out,
+                     ts_stream_t stream);
 
 typedef struct ts_redq_state {  /* device pointers, all float32 */
     float *actor, *actor_m, *actor_v;
@@ -1171,8 +1170,8 @@ typedef struct ts_redq_state {  /* device pointers, all float32 */
  * weight_out (nullable) float32[B] = mean_e td_e (redq.py:272); grads_out (nullable) = {E critic blocks, actor}. */
 int ts_redq_update(ts_workspace* ws, const ts_redq_state* st, int64_t E, int64_t critic_step, int64_t actor_step,
                    int do_actor, const float* obs, const float* act, const float* returns, const float* weight,
-                   const float* noise, int64_t B, int64_t obs_dim, int64_t act_dim, const ts_sac_hparams* hp,
-                   float* stats_out4, float* weight_out, float* grads_out, ts_stream_t stream);
+                   const float* noise, int64_t B, int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk,
+                   const ts_sac_hparams* hp, float* stats_out4, float* weight_out, float* grads_out, ts_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * NPG / TRPO (tianshou/algorithm/modelfree/npg.py, trpo.py) on the MuJoCo actor-critic of
@@ -1312,14 +1311,15 @@ int ts_td3_layout_h(int64_t obs_dim, int64_t act_dim, int64_t hidden, int64_t* h
 
 /* ContinuousDeterministicPolicy.forward (ddpg.py:162-180): act = max_action * tanh(actor(obs)). */
 int ts_td3_policy_forward(ts_workspace* ws, const float* actor, const float* obs, int64_t B, int64_t obs_dim,
-                          int64_t act_dim, double max_action, float* act_out, ts_stream_t stream);
+                          int64_t act_dim, const ts_mlp_trunk* trunk, double max_action, float* act_out, ts_stream_t stream);
 
 /* _target_q (ddpg.py:327-339) with the lagged actor: DDPG (critic2_old NULL, noise NULL; ddpg.py:397-399) or
  * TD3 (td3.py:94-102, 190-202): a' = actor_old(s') + clamp(noise * policy_noise, +-noise_clip) (noise_clip <= 0:
  * no clamp), min of the two lagged critics.  noise float32[B, act_dim] = the torch.randn draws. */
 int ts_td3_target_q(ts_workspace* ws, const float* actor_old, const float* critic1_old, const float* critic2_old,
                     const float* obs_next, const float* noise, int64_t B, int64_t obs_dim, int64_t act_dim,
-                    double max_action, double policy_noise, double noise_clip, float* out, ts_stream_t stream);
+                    const ts_mlp_trunk* trunk, double max_action, double policy_noise, double noise_clip, float* out,
+                    ts_stream_t stream);
 
 typedef struct ts_td3_state {  /* device pointers, float32; critic2* NULL = DDPG */
     float *actor, *actor_m, *actor_v;
@@ -1342,8 +1342,8 @@ typedef struct ts_td3_hparams {
  * stats_out3 = {actor_loss (written only when the actor is updated), critic1_loss, critic2_loss};
  * weight_out (nullable) = (td1 + td2) / 2 or td1; grads_out (nullable) = {critic1, critic2, actor} gradients. */
 int ts_td3_update(ts_workspace* ws, const ts_td3_state* st, int64_t critic_step, int64_t actor_step, const float* obs,
-                  const float* act, const float* returns, const float* weight, int64_t B, int64_t obs_dim,
-                  int64_t act_dim, const ts_td3_hparams* hp, float* stats_out3, float* weight_out, float* grads_out,
+                  const float* act, const float* returns, const float* weight, int64_t B, int64_t obs_dim, int64_t act_dim,
+                  const ts_mlp_trunk* trunk, const ts_td3_hparams* hp, float* stats_out3, float* weight_out, float* grads_out,
                   ts_stream_t stream);
 
 /* ---- data-parallel exchange ------------------------------------------------------------------

@@ -2060,7 +2060,7 @@ def gen_widths() -> None:
 
 def gen_depth() -> None:
     """Round 6: trunks of other depths than two hidden layers (Net(hidden_sizes=[...]) takes any list; the engines run them layer
-    by layer on the GEMM kernels, `ts_mlp_set_trunk`): SAC with a three-layer actor [64, 48, 32] and three-layer critics
+    by layer on the GEMM kernels, `ts_mlp_trunk.depth`): SAC with a three-layer actor [64, 48, 32] and three-layer critics
     [40, 56, 24] (unequal widths, none but one a multiple of 32: embedded by zero padding) and SAC with ONE hidden layer [96];
     TD3 with four layers; DDPG with one."""
     gen_sac("depth3", E=4, slots=32, steps=30, obs_dim=23, act_dim=5, batch=64, n_updates=3, seed=31, auto_alpha=True,

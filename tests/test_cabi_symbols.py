@@ -43,6 +43,25 @@ def test_argument_validation_without_gpu(lib):
     assert rc == _lib.TS_ERR_INVALID_ARG and b"power of two" in lib.ts_last_error()
 
 
+@pytest.mark.parametrize("hidden,depth", [(100, 2), (256, 7)])
+def test_trunk_validation_without_gpu(lib, hidden, depth):
+    """A `ts_mlp_trunk` is checked before any HIP call too: a width that is no multiple of 32 and a depth beyond
+    TS_MLP_MAX_HIDDEN_LAYERS fail as TS_ERR_INVALID_ARG on a workspace that has never touched a device (ts_workspace_create
+    only allocates host memory; the dummy pointers are never dereferenced)."""
+    from tianshou_amd import sac
+
+    ws = ctypes.c_void_p()
+    assert lib.ts_workspace_create(ctypes.byref(ws), 0, ctypes.c_size_t(0)) == 0
+    try:
+        dummy = ctypes.c_void_p(4096)
+        trunk = sac.MLPTrunk(hidden, depth, "relu", 0.0)
+        rc = lib.ts_sac_policy_forward(ws, dummy, dummy, dummy, ctypes.c_int64(1), ctypes.c_int64(8), ctypes.c_int64(2),
+                                       ctypes.byref(trunk), dummy, dummy, None, None)
+        assert rc == _lib.TS_ERR_INVALID_ARG
+    finally:
+        lib.ts_workspace_destroy(ws)
+
+
 def test_product_path_fails_loudly_without_library(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))
@@ -135,6 +154,7 @@ def test_ctypes_structures_match_the_header_structs():
 
     mirrors = {"ts_ppo_hparams": _lib.PPOHParams, "ts_dqn_hparams": dqn.DQNHParams, "ts_distq_hparams": distq.DistQHParams,
                "ts_rows_replay": drqn.RowsReplay, "ts_npg_hparams": npg.NPGHParams, "ts_sac_hparams": sac.SACHParams,
+               "ts_mlp_trunk": sac.MLPTrunk,
                "ts_sac_state": sac.SACStateC, "ts_sac_replay": sac.SACReplayC, "ts_redq_state": redq.REDQStateC, "ts_td3_hparams": td3.TD3HParams,
                "ts_td3_state": td3.TD3StateC, "ts_net_desc": _lib.NetDesc, "ts_frame_replay": _lib.FrameReplay}
     text = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)

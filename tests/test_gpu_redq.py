@@ -95,7 +95,7 @@ def test_update_gradients_vs_oracle(obs_dim, act_dim, B, E, auto, weighted):
 def test_other_hidden_widths_vs_oracle(hidden, obs_dim, act_dim, B, E):
     """Net / EnsembleLinear widths other than test_redq.py's 256 (utils/net/common.py:246-369 takes any hidden_sizes): two
     updates with the actor step (actor_delay = 1) against the oracle -- losses, PER weights, parameters -- on the per-layer
-    GEMM kernels; the width travels with every call (ts_mlp_set_hidden)."""
+    GEMM kernels; the width travels with every call (ts_mlp_trunk)."""
     from tianshou_amd import redq as RQ
     from tianshou_amd import sac as S
 

@@ -116,10 +116,10 @@ def test_sac_update_matches_reference_golden(tag):
     """(`widths`: actor Net[48, 80], critics Net[72, 40] in the reference; the engine runs them embedded in Net[96, 96] and every
     padding entry of parameters, lagged parameters and Adam moments stays exactly zero.  `depth3`: THREE hidden layers, actor
     [64, 48, 32] and critics [40, 56, 24] in Net[64] * 3; `depth1`: ONE hidden layer [96], fixed alpha, 2-step returns --
-    fixtures the unmodified reference wrote, gen_golden.py::gen_depth; the engine runs them layer by layer, ts_mlp_set_trunk.
+    fixtures the unmodified reference wrote, gen_golden.py::gen_depth; the engine runs them layer by layer, ts_mlp_trunk.depth.
     `bounded` / `bounded_depth3`: the class-default actor `unbounded=False` -- mu = max_action * tanh(mu), max_action 1.5 / 0.8,
-    ts_sac_set_actor_bound -- on Net[256, 256] (the fused kernels) and on actor [48, 64, 40] / critics [64, 32, 32].
-    `tanh`: Net(activation=nn.Tanh) trunks, actor [64, 48] / critics [40, 72] -- ts_mlp_set_activation.)"""
+    ts_mlp_trunk.max_action -- on Net[256, 256] (the fused kernels) and on actor [48, 64, 40] / critics [64, 32, 32].
+    `tanh`: Net(activation=nn.Tanh) trunks, actor [64, 48] / critics [40, 72] -- ts_mlp_trunk.activation.)"""
     from tianshou_amd import sac as S
     from tianshou_amd import widths as W
     from tianshou_amd.buffer import DeviceReplayBuffer
@@ -182,7 +182,7 @@ def test_update_other_shapes_vs_oracle(obs_dim, act_dim, B):
 @pytest.mark.parametrize("hidden,obs_dim,act_dim,B", [(128, 23, 5, 96), (96, 376, 17, 64), (512, 11, 3, 40)])
 def test_other_hidden_widths_vs_oracle(hidden, obs_dim, act_dim, B):
     """Net(hidden_sizes=[h, h]) with h other than the example's 256 (utils/net/common.py:246-369 takes any): the same update
-    on the per-layer GEMM kernels (ts_mlp_set_hidden), two updates against the oracle; a 256-wide engine sharing the
+    on the per-layer GEMM kernels (ts_mlp_trunk.hidden), two updates against the oracle; a 256-wide engine sharing the
     device's workspace is interleaved to show that the width travels with each call."""
     from tianshou_amd import sac as S
 
@@ -226,7 +226,7 @@ def test_other_depths_vs_oracle(hidden, obs_dim, act_dim, B):
 
 @pytest.mark.parametrize("hidden,obs_dim,act_dim,B", [(((256, 256), (256, 256)), 376, 17, 512), (((40, 72, 56), (32, 64, 32)), 11, 3, 65)])
 def test_tanh_trunks_vs_oracle(hidden, obs_dim, act_dim, B):
-    """Net(activation=nn.Tanh) trunks (ts_mlp_set_activation): the same checks as test_other_depths_vs_oracle -- at [256, 256] too,
+    """Net(activation=nn.Tanh) trunks (ts_mlp_trunk.activation): the same checks as test_other_depths_vs_oracle -- at [256, 256] too,
     where ReLU trunks take the fused kernels and tanh trunks the per-layer path."""
     with OS.activation("tanh"):
         _other_depths(hidden, obs_dim, act_dim, B, "tanh")
@@ -234,7 +234,7 @@ def test_tanh_trunks_vs_oracle(hidden, obs_dim, act_dim, B):
 
 def _other_depths(hidden, obs_dim, act_dim, B, activation):
     """Net(hidden_sizes=[...]) of 1, 3, 5 and 6 hidden layers (utils/net/common.py:246-369 takes any list; round 6): the update
-    runs layer by layer on the GEMM kernels (ts_mlp_set_trunk).  Gradients of the first update against the float64 yardstick
+    runs layer by layer on the GEMM kernels (ts_mlp_trunk.depth).  Gradients of the first update against the float64 yardstick
     as in test_update_gradients_vs_oracle, two more updates against the oracle, the policy / target entry points, and a
     two-layer engine on the same workspace in between (the depth travels with each call)."""
     from tianshou_amd import sac as S
@@ -303,7 +303,7 @@ def _other_depths(hidden, obs_dim, act_dim, B, activation):
 @pytest.mark.parametrize("hidden,obs_dim,act_dim,B", [(256, 376, 17, 1024), (((64, 32, 48), (32, 64, 32)), 23, 5, 130)])
 def test_bounded_actor_vs_oracle(hidden, obs_dim, act_dim, B):
     """ContinuousActorProbabilistic(unbounded=False) -- the class default: mu = max_action * tanh(mu), continuous.py:230-231 --
-    under SAC (ts_sac_set_actor_bound): the policy / target entry points, the three gradients against the float64 yardstick
+    under SAC (ts_mlp_trunk.max_action): the policy / target entry points, the three gradients against the float64 yardstick
     (the actor's goes back through max_action * (1 - tanh^2)), and an unbounded engine on the same workspace in between."""
     from tianshou_amd import sac as S
 
@@ -339,25 +339,32 @@ def test_bounded_actor_vs_oracle(hidden, obs_dim, act_dim, B):
         assert e_gpu < max(1e-5, 2 * e_ref), (key, e_gpu, e_ref)
 
 
-def test_set_hidden_resets_the_actor_bound():
-    """C ABI: `ts_mlp_set_hidden` starts the workspace's trunk settings over -- width, depth 2, ReLU and an UNBOUNDED actor.  A
-    direct C caller that sets a width after another engine's `ts_sac_set_actor_bound(ws, 2.0)` gets the unbounded actor of
-    examples/mujoco/mujoco_sac.py, not a tanh bound it never asked for: `ts_sac_policy_forward` against float64 torch."""
+def test_null_trunk_is_the_default_after_another_trunk():
+    """C ABI: the trunk travels with the call (`ts_mlp_trunk`), nothing of it stays in the workspace.  A direct C caller that
+    passes `trunk = NULL` after a call with a bounded (max_action 2.0) tanh trunk of three 64-wide layers on the SAME workspace
+    gets the unbounded Net[256, 256] ReLU actor of examples/mujoco/mujoco_sac.py, not a tanh bound it never asked for:
+    `ts_sac_policy_forward` against float64 torch."""
+    import ctypes as C
+
     from tianshou_amd import _lib
+    from tianshou_amd import sac as S
 
     obs_dim, act_dim, B = 23, 5, 96
     eng, (actor, _, _) = make_engine(obs_dim, act_dim, 7, OS.SACConfig())
     lib, ws = _lib.load(), _lib.Workspace(0)
-    _lib.check(lib.ts_sac_set_actor_bound(ws.handle, _lib.f64(2.0)))
-    _lib.check(lib.ts_mlp_set_hidden(ws.handle, _lib.i64(256)))
+    stream = _lib.current_stream(torch.device("cuda"))
+    other = S.MLPTrunk(64, 3, "tanh", 2.0)
+    other_actor = torch.randn(S.mlp_layout(obs_dim, 64, 3, 64)[1][-1], device="cuda") * 0.05
+    other_obs, other_logp = torch.randn(8, obs_dim, device="cuda"), torch.empty(8, dtype=torch.float32, device="cuda")
+    _lib.check(lib.ts_sac_policy_forward(ws.handle, _lib.ptr(other_actor), _lib.ptr(other_obs), None, _lib.i64(8), _lib.i64(obs_dim),
+                                         _lib.i64(act_dim), C.byref(other), None, _lib.ptr(other_logp), None, stream))
     g = torch.Generator().manual_seed(3)
     obs, noise = torch.randn(B, obs_dim, generator=g), torch.randn(B, act_dim, generator=g)
     act = torch.empty((B, act_dim), dtype=torch.float32, device="cuda")
     logp = torch.empty(B, dtype=torch.float32, device="cuda")
     obs_d, noise_d = obs.cuda(), noise.cuda()
     _lib.check(lib.ts_sac_policy_forward(ws.handle, _lib.ptr(eng.actor), _lib.ptr(obs_d), _lib.ptr(noise_d), _lib.i64(B),
-                                         _lib.i64(obs_dim), _lib.i64(act_dim), _lib.ptr(act), _lib.ptr(logp), None,
-                                         _lib.current_stream(torch.device("cuda"))))
+                                         _lib.i64(obs_dim), _lib.i64(act_dim), None, _lib.ptr(act), _lib.ptr(logp), None, stream))
     torch.cuda.synchronize()
     p64 = {k: v.double() for k, v in actor.items()}
     r_act = OS.policy_forward(p64, obs.double(), noise.double(), 0.0)[0]

@@ -79,16 +79,6 @@ struct ts_workspace {
     void* dg_tables;
     long long dg_key[16][16];
     int dg_next[2];
-    // hidden width of the Net[h, h] MLPs of the SAC / TD3 / DDPG / REDQ entry points called with this workspace
-    // (ts_mlp_set_hidden; 0 = 256, the width of examples/mujoco/mujoco_sac.py)
-    int mlp_hidden;
-    // number of hidden layers of those MLPs (ts_mlp_set_trunk; 0 = 2, the depth of the examples' nets)
-    int mlp_depth;
-    // 1: nn.Tanh after every hidden layer of those MLPs instead of Net's default nn.ReLU (ts_mlp_set_activation)
-    int mlp_act_tanh;
-    // max_action of a BOUNDED Gaussian actor (mu = max_action * tanh(mu), continuous.py:230-231) of the SAC / REDQ entry
-    // points (ts_sac_set_actor_bound; 0 = unbounded, the actors of the examples)
-    float sac_actor_bound;
     hipStream_t side;
     hipStream_t side2;           // second side stream (ts::side_streams): created together with `side`
     hipEvent_t side_ev[16];

@@ -184,42 +184,6 @@ int ts_workspace_side_stream(ts_workspace* ws, int which, ts_stream_t* stream_ou
     return TS_OK;
 }
 
-int ts_mlp_set_hidden(ts_workspace* ws, int64_t hidden) {
-    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_mlp_set_hidden: workspace is NULL");
-    // (the SAC / TD3 / DDPG / REDQ entry points take widths up to 1024 and check that themselves; DiscreteSAC's, which
-    // receive the width as an argument and read only the depth from the workspace, up to 2048)
-    TS_REQUIRE(hidden == 0 || (hidden >= 32 && hidden <= 2048 && hidden % 32 == 0), TS_ERR_INVALID_ARG,
-               "ts_mlp_set_hidden: 0 (default 256) or a multiple of 32 in [32, 2048], got %lld", (long long)hidden);
-    ws->mlp_hidden = (int)hidden;
-    ws->mlp_depth = 0;
-    ws->mlp_act_tanh = 0;
-    ws->sac_actor_bound = 0.f;          // (the trunk settings start over: unbounded, as depth and activation)
-    return TS_OK;
-}
-
-int ts_mlp_set_activation(ts_workspace* ws, int activation) {
-    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_mlp_set_activation: workspace is NULL");
-    TS_REQUIRE(activation == TS_NET_ACT_RELU || activation == TS_NET_ACT_TANH, TS_ERR_UNSUPPORTED,
-               "ts_mlp_set_activation: TS_NET_ACT_RELU or TS_NET_ACT_TANH");
-    ws->mlp_act_tanh = activation == TS_NET_ACT_TANH ? 1 : 0;
-    return TS_OK;
-}
-
-int ts_sac_set_actor_bound(ts_workspace* ws, double max_action) {
-    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_sac_set_actor_bound: workspace is NULL");
-    TS_REQUIRE(max_action >= 0.0 && max_action < 1e30, TS_ERR_INVALID_ARG, "ts_sac_set_actor_bound: max_action >= 0 (0 = unbounded)");
-    ws->sac_actor_bound = (float)max_action;
-    return TS_OK;
-}
-
-int ts_mlp_set_trunk(ts_workspace* ws, int64_t hidden, int64_t depth) {
-    TS_REQUIRE(depth == 0 || (depth >= 1 && depth <= TS_MLP_MAX_HIDDEN_LAYERS), TS_ERR_INVALID_ARG,
-               "ts_mlp_set_trunk: 0 (default 2) or 1 .. %d hidden layers, got %lld", TS_MLP_MAX_HIDDEN_LAYERS, (long long)depth);
-    if (int rc = ts_mlp_set_hidden(ws, hidden)) return rc;
-    ws->mlp_depth = (int)depth;
-    return TS_OK;
-}
-
 int ts_workspace_destroy(ts_workspace* ws) {
     if (!ws) return TS_OK;
     if (ws->learn_graphs && ws->learn_graphs_free) { (void)hipSetDevice(ws->device); ws->learn_graphs_free(ws->learn_graphs); }

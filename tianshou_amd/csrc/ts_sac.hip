@@ -40,7 +40,7 @@ constexpr float LOG_SQRT_2PI = 0.91893853320467274178f;
 
 inline int pad32(int x) { return (x + 31) / 32 * 32; }
 
-constexpr int MAXD = TS_MLP_MAX_HIDDEN_LAYERS;      // hidden layers of a trunk (ts_mlp_set_trunk)
+constexpr int MAXD = TS_MLP_MAX_HIDDEN_LAYERS;      // hidden layers of a trunk (ts_mlp_trunk.depth)
 constexpr int MAXL = MAXD + 1;                      // linear layers incl. the head
 
 struct Mlp {                  // in -> hid x depth -> head, ReLU between (depth 2 / width 256: the examples' nets)
@@ -56,7 +56,7 @@ struct Mlp {                  // in -> hid x depth -> head, ReLU between (depth 
 
 Mlp make_mlp(int B, int in_pad, int head_cols, int hid = HID, int depth = 2, int act = TS_NET_ACT_RELU) {
     Mlp m{};
-    if (depth < 1 || depth > MAXD) depth = 2;       // (validated by ts_mlp_set_trunk / the layout entry points)
+    if (depth < 1 || depth > MAXD) depth = 2;       // (validated by make_dims / the layout entry points)
     m.L = depth + 1;
     m.act = act == TS_NET_ACT_TANH ? TS_NET_ACT_TANH : TS_NET_ACT_RELU;
     int64_t o = 0;
@@ -1156,9 +1156,9 @@ struct Carve {
 
 struct Dims { int obs, act, ka, kc, hid, depth, fn; float bound; };     // fn: TS_NET_ACT_* of the trunks
 
-// hidden: width of the two hidden layers of every Net[h, h] of the SAC / TD3 / DDPG / REDQ entry points -- a property of
-// the workspace (ts_mlp_set_hidden; 0 = the examples' 256).  Any multiple of 32 up to 1024 runs: 256 on the fused
-// three-layer kernels of ts_mlp.hip, everything else on the per-layer GEMM kernels.
+// hidden: width of the hidden layers of every Net[h] * depth of the SAC / TD3 / DDPG / REDQ entry points (0 = the examples'
+// 256).  Any multiple of 32 up to 1024 runs: 256 on the fused three-layer kernels of ts_mlp.hip, everything else on the
+// per-layer GEMM kernels.
 int make_dims_h(int64_t obs_dim, int64_t act_dim, int64_t hidden, Dims* d, int64_t depth = 0) {
     TS_REQUIRE(obs_dim >= 1 && obs_dim <= 65536 && act_dim >= 1 && act_dim <= 32, TS_ERR_INVALID_ARG,
                "sac: obs_dim must be >= 1 and act_dim in [1, 32]");
@@ -1174,12 +1174,20 @@ int make_dims_h(int64_t obs_dim, int64_t act_dim, int64_t hidden, Dims* d, int64
     return TS_OK;
 }
 
-// hidden width and depth: properties of the workspace (ts_mlp_set_hidden / ts_mlp_set_trunk)
-int make_dims(const ts_workspace* ws, int64_t obs_dim, int64_t act_dim, Dims* d) {
-    if (int rc = make_dims_h(obs_dim, act_dim, ws ? ws->mlp_hidden : 0, d, ws ? ws->mlp_depth : 0)) return rc;
-    d->bound = ws ? ws->sac_actor_bound : 0.f;          // ts_sac_set_actor_bound (SAC's / REDQ's Gaussian actor only)
-    d->fn = ws && ws->mlp_act_tanh ? TS_NET_ACT_TANH : TS_NET_ACT_RELU;       // ts_mlp_set_activation
+int trunk_activation(const ts_mlp_trunk* t, int* fn) {
+    TS_REQUIRE(t->activation == TS_NET_ACT_RELU || t->activation == TS_NET_ACT_TANH, TS_ERR_UNSUPPORTED,
+               "ts_mlp_trunk: activation TS_NET_ACT_RELU or TS_NET_ACT_TANH");
+    *fn = t->activation;
     return TS_OK;
+}
+
+// the trunk travels with every call (ts_mlp_trunk); NULL = make_dims_h's defaults, the examples' nets
+int make_dims(const ts_mlp_trunk* t, int64_t obs_dim, int64_t act_dim, Dims* d) {
+    if (int rc = make_dims_h(obs_dim, act_dim, t ? t->hidden : 0, d, t ? t->depth : 0)) return rc;
+    if (!t) return TS_OK;
+    TS_REQUIRE(t->max_action >= 0.0 && t->max_action < 1e30, TS_ERR_INVALID_ARG, "ts_mlp_trunk: max_action >= 0 (0 = unbounded)");
+    d->bound = (float)t->max_action;          // SAC's / REDQ's Gaussian actor only
+    return trunk_activation(t, &d->fn);
 }
 
 Act take_act(Carve& c, int64_t B, int head_cols, int hid = HID, int depth = 2) {
@@ -1213,6 +1221,11 @@ int make_ddims(int64_t obs_dim, int64_t n_act, int64_t hidden, DDims* d, int64_t
     return TS_OK;
 }
 
+int make_ddims(const ts_mlp_trunk* t, int64_t obs_dim, int64_t n_act, DDims* d) {
+    if (int rc = make_ddims(obs_dim, n_act, t && t->hidden ? t->hidden : HID, d, t ? t->depth : 0)) return rc;
+    return t ? trunk_activation(t, &d->fn) : TS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1244,12 +1257,12 @@ int ts_sac_layout_h(int64_t obs_dim, int64_t act_dim, int64_t hidden, int64_t* h
 }
 
 int ts_sac_policy_forward(ts_workspace* ws, const float* actor, const float* obs, const float* noise, int64_t B,
-                          int64_t obs_dim, int64_t act_dim, float* act_out, float* logp_out, float* mu_sigma_out,
-                          ts_stream_t stream) {
+                          int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk, float* act_out, float* logp_out,
+                          float* mu_sigma_out, ts_stream_t stream) {
     TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_sac_policy_forward: workspace is NULL");
     TS_REQUIRE(B >= 1 && actor && obs && logp_out, TS_ERR_INVALID_ARG, "ts_sac_policy_forward: bad argument");
     Dims d;
-    if (int rc = make_dims(ws, obs_dim, act_dim, &d)) return rc;
+    if (int rc = make_dims(trunk, obs_dim, act_dim, &d)) return rc;
     hipStream_t s = ts::as_stream(stream);
     const Mlp ma = make_mlp((int)B, d.ka, 64, d.hid, d.depth, d.fn);
     if (int rc = ts::ws_reserve(ws, al(4 * B * d.ka) + 3 * hbytes(B, d) + al(4 * B * 3 * d.act) +
@@ -1273,12 +1286,12 @@ int ts_sac_policy_forward(ts_workspace* ws, const float* actor, const float* obs
 }
 
 int ts_sac_policy_forward_logits(ts_workspace* ws, const float* actor, const float* obs, const float* noise, int64_t B,
-                                 int64_t obs_dim, int64_t act_dim, float* act_out, float* logp_out, float* mu_out,
-                                 float* sigma_out, ts_stream_t stream) {
+                                 int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk, float* act_out, float* logp_out,
+                                 float* mu_out, float* sigma_out, ts_stream_t stream) {
     TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_sac_policy_forward_logits: workspace is NULL");
     TS_REQUIRE(B >= 1 && actor && obs && logp_out, TS_ERR_INVALID_ARG, "ts_sac_policy_forward_logits: bad argument");
     Dims d;
-    if (int rc = make_dims(ws, obs_dim, act_dim, &d)) return rc;
+    if (int rc = make_dims(trunk, obs_dim, act_dim, &d)) return rc;
     hipStream_t s = ts::as_stream(stream);
     const Mlp ma = make_mlp((int)B, d.ka, 64, d.hid, d.depth, d.fn);
     if (int rc = ts::ws_reserve(ws, al(4 * B * d.ka) + 3 * hbytes(B, d) + al(4 * split_floats(ma)) + 4096)) return rc;
@@ -1297,13 +1310,13 @@ int ts_sac_policy_forward_logits(ts_workspace* ws, const float* actor, const flo
 
 static int sac_target_impl(ts_workspace* ws, const float* actor, const float* critic1_old, const float* critic2_old,
                            const float* log_alpha, double fixed_alpha, const float* obs_next, const float* noise, int64_t B,
-                           int64_t obs_dim, int64_t act_dim, float* out, ts_stream_t stream, const int64_t* rows,
-                           const double* rew, const uint8_t* terminated, double gamma) {
+                           int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk, float* out, ts_stream_t stream,
+                           const int64_t* rows, const double* rew, const uint8_t* terminated, double gamma) {
     TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_sac_target_q: workspace is NULL");
     TS_REQUIRE(B >= 1 && actor && critic1_old && critic2_old && obs_next && noise && out, TS_ERR_INVALID_ARG,
                "ts_sac_target_q: bad argument");
     Dims d;
-    if (int rc = make_dims(ws, obs_dim, act_dim, &d)) return rc;
+    if (int rc = make_dims(trunk, obs_dim, act_dim, &d)) return rc;
     hipStream_t s = ts::as_stream(stream);
     const Mlp ma = make_mlp((int)B, d.ka, 64, d.hid, d.depth, d.fn), mc = make_mlp((int)B, d.kc, 32, d.hid, d.depth, d.fn);
     const size_t spl = std::max(split_floats(ma), split_floats(mc));
@@ -1344,18 +1357,18 @@ static int sac_target_impl(ts_workspace* ws, const float* actor, const float* cr
 
 int ts_sac_target_q(ts_workspace* ws, const float* actor, const float* critic1_old, const float* critic2_old,
                     const float* log_alpha, double fixed_alpha, const float* obs_next, const float* noise, int64_t B,
-                    int64_t obs_dim, int64_t act_dim, float* out, ts_stream_t stream) {
-    return sac_target_impl(ws, actor, critic1_old, critic2_old, log_alpha, fixed_alpha, obs_next, noise, B, obs_dim, act_dim, out,
+                    int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk, float* out, ts_stream_t stream) {
+    return sac_target_impl(ws, actor, critic1_old, critic2_old, log_alpha, fixed_alpha, obs_next, noise, B, obs_dim, act_dim, trunk, out,
                            stream, nullptr, nullptr, nullptr, 0.0);
 }
 
 int ts_sac_returns_rows(ts_workspace* ws, const float* actor, const float* critic1_old, const float* critic2_old,
                         const float* log_alpha, double fixed_alpha, const float* obs_next_buf, const double* rew_buf,
                         const uint8_t* terminated_buf, const int64_t* rows, const float* noise, int64_t B, int64_t obs_dim,
-                        int64_t act_dim, double gamma, float* returns_out, ts_stream_t stream) {
+                        int64_t act_dim, const ts_mlp_trunk* trunk, double gamma, float* returns_out, ts_stream_t stream) {
     TS_REQUIRE(obs_next_buf && rew_buf && terminated_buf && rows && returns_out, TS_ERR_INVALID_ARG,
                "ts_sac_returns_rows: NULL argument");
-    return sac_target_impl(ws, actor, critic1_old, critic2_old, log_alpha, fixed_alpha, obs_next_buf, noise, B, obs_dim, act_dim,
+    return sac_target_impl(ws, actor, critic1_old, critic2_old, log_alpha, fixed_alpha, obs_next_buf, noise, B, obs_dim, act_dim, trunk,
                            returns_out, stream, rows, rew_buf, terminated_buf, gamma);
 }
 
@@ -1381,8 +1394,9 @@ struct LearnExt {
 // single phases -> the exchange buffer: critic phases [critic1 | critic2], actor phases [actor | -mean(log_prob)].
 int sac_update_impl(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, const float* obs, const float* act,
                     const float* returns, const float* weight, const float* noise, int64_t B, int64_t obs_dim,
-                    int64_t act_dim, const ts_sac_hparams* hp, float* stats_out5, float* weight_out, float* grads,
-                    int phases, ts_stream_t stream, const int64_t* rows = nullptr, const LearnExt* ext = nullptr) {
+                    int64_t act_dim, const ts_mlp_trunk* trunk, const ts_sac_hparams* hp, float* stats_out5,
+                    float* weight_out, float* grads, int phases, ts_stream_t stream, const int64_t* rows = nullptr,
+                    const LearnExt* ext = nullptr) {
     float* const grads_out = phases == PH_ALL ? grads : nullptr;
     TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_sac_update: workspace is NULL");
     TS_REQUIRE(st && hp && obs && act && (returns || ext) && noise && stats_out5 && B >= 1 && adam_step >= 1,
@@ -1393,7 +1407,7 @@ int sac_update_impl(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step,
     TS_REQUIRE(!hp->auto_alpha || (st->log_alpha && st->log_alpha_m && st->log_alpha_v), TS_ERR_INVALID_ARG,
                "ts_sac_update: auto alpha needs log_alpha and its Adam moments");
     Dims d;
-    if (int rc = make_dims(ws, obs_dim, act_dim, &d)) return rc;
+    if (int rc = make_dims(trunk, obs_dim, act_dim, &d)) return rc;
     hipStream_t s = ts::as_stream(stream);
     const Mlp ma = make_mlp((int)B, d.ka, 64, d.hid, d.depth, d.fn), mc = make_mlp((int)B, d.kc, 32, d.hid, d.depth, d.fn);
     const size_t slab = std::max(slab_floats(ma), slab_floats(mc));
@@ -1658,26 +1672,27 @@ int sac_update_impl(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step,
 extern "C" {
 
 int ts_sac_update(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, const float* obs, const float* act,
-                  const float* returns, const float* weight, const float* noise, int64_t B, int64_t obs_dim,
-                  int64_t act_dim, const ts_sac_hparams* hp, float* stats_out5, float* weight_out, float* grads_out,
+                  const float* returns, const float* weight, const float* noise, int64_t B, int64_t obs_dim, int64_t act_dim,
+                  const ts_mlp_trunk* trunk, const ts_sac_hparams* hp, float* stats_out5, float* weight_out, float* grads_out,
                   ts_stream_t stream) {
-    return sac_update_impl(ws, st, adam_step, obs, act, returns, weight, noise, B, obs_dim, act_dim, hp, stats_out5,
+    return sac_update_impl(ws, st, adam_step, obs, act, returns, weight, noise, B, obs_dim, act_dim, trunk, hp, stats_out5,
                            weight_out, grads_out, PH_ALL, stream);
 }
 
-int ts_sac_update_rows(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, const float* obs_buf, const float* act_buf,
-                       const int64_t* rows, const float* returns, const float* weight, const float* noise, int64_t B,
-                       int64_t obs_dim, int64_t act_dim, const ts_sac_hparams* hp, float* stats_out5, float* weight_out,
-                       ts_stream_t stream) {
+int ts_sac_update_rows(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, const float* obs_buf,
+                       const float* act_buf, const int64_t* rows, const float* returns, const float* weight,
+                       const float* noise, int64_t B, int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk,
+                       const ts_sac_hparams* hp, float* stats_out5, float* weight_out, ts_stream_t stream) {
     TS_REQUIRE(rows != nullptr, TS_ERR_INVALID_ARG, "ts_sac_update_rows: rows is NULL");
-    return sac_update_impl(ws, st, adam_step, obs_buf, act_buf, returns, weight, noise, B, obs_dim, act_dim, hp, stats_out5,
+    return sac_update_impl(ws, st, adam_step, obs_buf, act_buf, returns, weight, noise, B, obs_dim, act_dim, trunk, hp, stats_out5,
                            weight_out, nullptr, PH_ALL, stream, rows);
 }
 
 int ts_sac_learn_rows(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, const ts_sac_replay* replay,
                       const int64_t* rows, const float* weight, float* noise2, int fill_noise, uint64_t noise_seed,
-                      uint64_t noise_offset, int64_t B, int64_t obs_dim, int64_t act_dim, const ts_sac_hparams* hp, double gamma,
-                      float* returns_out, float* stats_out5, float* weight_out, ts_stream_t stream) {
+                      uint64_t noise_offset, int64_t B, int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk,
+                      const ts_sac_hparams* hp, double gamma, float* returns_out, float* stats_out5, float* weight_out,
+                      ts_stream_t stream) {
     TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_sac_learn_rows: workspace is NULL");
     TS_REQUIRE(st && hp && replay && replay->obs && replay->act && replay->obs_next && replay->rew && replay->terminated && rows &&
                    noise2 && returns_out && stats_out5 && B >= 1 && adam_step >= 1,
@@ -1686,7 +1701,7 @@ int ts_sac_learn_rows(ts_workspace* ws, const ts_sac_state* st, int64_t adam_ste
     TS_REQUIRE(st->actor && st->critic1_old && st->critic2_old && (!hp->auto_alpha || st->log_alpha), TS_ERR_INVALID_ARG,
                "ts_sac_learn_rows: NULL state pointer");
     Dims d;
-    if (int rc = make_dims(ws, obs_dim, act_dim, &d)) return rc;
+    if (int rc = make_dims(trunk, obs_dim, act_dim, &d)) return rc;
     const Mlp mc = make_mlp((int)B, d.kc, 32, d.hid, d.depth, d.fn), ma = make_mlp((int)B, d.ka, 64, d.hid, d.depth, d.fn);
     float* noise_next = noise2;
     float* noise_upd = noise2 + B * act_dim;
@@ -1703,10 +1718,10 @@ int ts_sac_learn_rows(ts_workspace* ws, const ts_sac_state* st, int64_t adam_ste
             if (int rc = ts_normal_fill(noise2 + B * act_dim, B * act_dim, noise_seed, noise_offset + 1, stream)) return rc;
         }
         if (int rc = sac_target_impl(ws, st->actor, st->critic1_old, st->critic2_old, hp->auto_alpha ? st->log_alpha : nullptr, hp->alpha,
-                                     replay->obs_next, noise_next, B, obs_dim, act_dim, returns_out, stream, rows, replay->rew,
+                                     replay->obs_next, noise_next, B, obs_dim, act_dim, trunk, returns_out, stream, rows, replay->rew,
                                      replay->terminated, gamma))
             return rc;
-        return sac_update_impl(ws, st, adam_step, replay->obs, replay->act, returns_out, weight, noise_upd, B, obs_dim, act_dim, hp,
+        return sac_update_impl(ws, st, adam_step, replay->obs, replay->act, returns_out, weight, noise_upd, B, obs_dim, act_dim, trunk, hp,
                                stats_out5, weight_out, nullptr, PH_ALL, stream, rows);
     }
     LearnExt ext{};
@@ -1714,18 +1729,18 @@ int ts_sac_learn_rows(ts_workspace* ws, const ts_sac_state* st, int64_t adam_ste
     ext.noise_next = noise_next; ext.noise_fill = fill_noise ? noise2 : nullptr;
     ext.noise_halves = fill_noise == 2 ? 2 : 1; ext.noise_n = (fill_noise == 2 ? 1 : 2) * B * act_dim;
     ext.seed = noise_seed; ext.offset = noise_offset; ext.returns_out = returns_out;
-    return sac_update_impl(ws, st, adam_step, replay->obs, replay->act, nullptr, weight, noise_upd, B, obs_dim, act_dim, hp, stats_out5,
+    return sac_update_impl(ws, st, adam_step, replay->obs, replay->act, nullptr, weight, noise_upd, B, obs_dim, act_dim, trunk, hp, stats_out5,
                            weight_out, nullptr, PH_ALL, stream, rows, &ext);
 }
 
 int ts_sac_update_phase(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, const float* obs, const float* act,
                         const float* returns, const float* weight, const float* noise, int64_t B, int64_t obs_dim,
-                        int64_t act_dim, const ts_sac_hparams* hp, int phase, float* stats_out5, float* weight_out,
-                        float* grads, ts_stream_t stream) {
+                        int64_t act_dim, const ts_mlp_trunk* trunk, const ts_sac_hparams* hp, int phase, float* stats_out5,
+                        float* weight_out, float* grads, ts_stream_t stream) {
     TS_REQUIRE(phase == PH_CRITIC_GRAD || phase == PH_CRITIC_APPLY || phase == PH_ACTOR_GRAD || phase == PH_ACTOR_APPLY,
                TS_ERR_INVALID_ARG, "ts_sac_update_phase: phase must be 1, 2, 4 or 8");
     TS_REQUIRE(grads != nullptr, TS_ERR_INVALID_ARG, "ts_sac_update_phase: the exchange buffer is NULL");
-    return sac_update_impl(ws, st, adam_step, obs, act, returns, weight, noise, B, obs_dim, act_dim, hp, stats_out5,
+    return sac_update_impl(ws, st, adam_step, obs, act, returns, weight, noise, B, obs_dim, act_dim, trunk, hp, stats_out5,
                            weight_out, grads, phase, stream);
 }
 
@@ -1742,11 +1757,11 @@ int ts_td3_layout_h(int64_t obs_dim, int64_t act_dim, int64_t hidden, int64_t* h
 }
 
 int ts_td3_policy_forward(ts_workspace* ws, const float* actor, const float* obs, int64_t B, int64_t obs_dim,
-                          int64_t act_dim, double max_action, float* act_out, ts_stream_t stream) {
+                          int64_t act_dim, const ts_mlp_trunk* trunk, double max_action, float* act_out, ts_stream_t stream) {
     TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_td3_policy_forward: workspace is NULL");
     TS_REQUIRE(B >= 1 && actor && obs && act_out, TS_ERR_INVALID_ARG, "ts_td3_policy_forward: bad argument");
     Dims d;
-    if (int rc = make_dims(ws, obs_dim, act_dim, &d)) return rc;
+    if (int rc = make_dims(trunk, obs_dim, act_dim, &d)) return rc;
     hipStream_t s = ts::as_stream(stream);
     const Mlp ma = make_mlp((int)B, d.ka, 32, d.hid, d.depth, d.fn);
     if (int rc = ts::ws_reserve(ws, al(4 * B * d.ka) + 3 * hbytes(B, d) + al(4 * split_floats(ma)) + 4096)) return rc;
@@ -1766,11 +1781,12 @@ int ts_td3_policy_forward(ts_workspace* ws, const float* actor, const float* obs
 
 int ts_td3_target_q(ts_workspace* ws, const float* actor_old, const float* critic1_old, const float* critic2_old,
                     const float* obs_next, const float* noise, int64_t B, int64_t obs_dim, int64_t act_dim,
-                    double max_action, double policy_noise, double noise_clip, float* out, ts_stream_t stream) {
+                    const ts_mlp_trunk* trunk, double max_action, double policy_noise, double noise_clip, float* out,
+                    ts_stream_t stream) {
     TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_td3_target_q: workspace is NULL");
     TS_REQUIRE(B >= 1 && actor_old && critic1_old && obs_next && out, TS_ERR_INVALID_ARG, "ts_td3_target_q: bad argument");
     Dims d;
-    if (int rc = make_dims(ws, obs_dim, act_dim, &d)) return rc;
+    if (int rc = make_dims(trunk, obs_dim, act_dim, &d)) return rc;
     hipStream_t s = ts::as_stream(stream);
     const Mlp ma = make_mlp((int)B, d.ka, 32, d.hid, d.depth, d.fn), mc = make_mlp((int)B, d.kc, 32, d.hid, d.depth, d.fn);
     const size_t spl = std::max(split_floats(ma), split_floats(mc));
@@ -1812,8 +1828,8 @@ int ts_td3_target_q(ts_workspace* ws, const float* actor_old, const float* criti
 }
 
 int ts_td3_update(ts_workspace* ws, const ts_td3_state* st, int64_t critic_step, int64_t actor_step, const float* obs,
-                  const float* act, const float* returns, const float* weight, int64_t B, int64_t obs_dim,
-                  int64_t act_dim, const ts_td3_hparams* hp, float* stats_out3, float* weight_out, float* grads_out,
+                  const float* act, const float* returns, const float* weight, int64_t B, int64_t obs_dim, int64_t act_dim,
+                  const ts_mlp_trunk* trunk, const ts_td3_hparams* hp, float* stats_out3, float* weight_out, float* grads_out,
                   ts_stream_t stream) {
     TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_td3_update: workspace is NULL");
     TS_REQUIRE(st && hp && obs && act && returns && stats_out3 && B >= 1 && critic_step >= 1 && actor_step >= 1,
@@ -1824,7 +1840,7 @@ int ts_td3_update(ts_workspace* ws, const ts_td3_state* st, int64_t critic_step,
     TS_REQUIRE(!twin || (st->critic2_m && st->critic2_v && st->critic2_old), TS_ERR_INVALID_ARG,
                "ts_td3_update: incomplete second critic");
     Dims d;
-    if (int rc = make_dims(ws, obs_dim, act_dim, &d)) return rc;
+    if (int rc = make_dims(trunk, obs_dim, act_dim, &d)) return rc;
     hipStream_t s = ts::as_stream(stream), side;
     const Mlp ma = make_mlp((int)B, d.ka, 32, d.hid, d.depth, d.fn), mc = make_mlp((int)B, d.kc, 32, d.hid, d.depth, d.fn);
     if (int rc = twin_stream(ws, s, mc, &side)) return rc;
@@ -1964,12 +1980,11 @@ int ts_dsac_layout(int64_t obs_dim, int64_t n_act, int64_t hidden, int64_t* h_ou
 }
 
 int ts_dsac_policy_forward(ts_workspace* ws, const float* actor, const float* obs, int64_t B, int64_t obs_dim,
-                           int64_t n_act, int64_t hidden, float* logits_out, ts_stream_t stream) {
+                           int64_t n_act, const ts_mlp_trunk* trunk, float* logits_out, ts_stream_t stream) {
     TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_dsac_policy_forward: workspace is NULL");
     TS_REQUIRE(B >= 1 && actor && obs && logits_out, TS_ERR_INVALID_ARG, "ts_dsac_policy_forward: bad argument");
     DDims d;
-    if (int rc = make_ddims(obs_dim, n_act, hidden, &d, ws->mlp_depth)) return rc;
-    d.fn = ws->mlp_act_tanh ? TS_NET_ACT_TANH : TS_NET_ACT_RELU;
+    if (int rc = make_ddims(trunk, obs_dim, n_act, &d)) return rc;
     hipStream_t s = ts::as_stream(stream);
     const Mlp m = make_mlp((int)B, d.ka, d.hw, d.hid, d.depth, d.fn);
     if (int rc = ts::ws_reserve(ws, al(4 * B * d.ka) + 2 * hbytes(B, d) + al(4 * B * d.hw) + al(4 * split_floats(m)) + 4096))
@@ -1989,13 +2004,12 @@ int ts_dsac_policy_forward(ts_workspace* ws, const float* actor, const float* ob
 
 int ts_dsac_target_q(ts_workspace* ws, const float* actor, const float* critic1_old, const float* critic2_old,
                      const float* log_alpha, double fixed_alpha, const float* obs_next, int64_t B, int64_t obs_dim,
-                     int64_t n_act, int64_t hidden, float* out, ts_stream_t stream) {
+                     int64_t n_act, const ts_mlp_trunk* trunk, float* out, ts_stream_t stream) {
     TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_dsac_target_q: workspace is NULL");
     TS_REQUIRE(B >= 1 && actor && critic1_old && critic2_old && obs_next && out, TS_ERR_INVALID_ARG,
                "ts_dsac_target_q: bad argument");
     DDims d;
-    if (int rc = make_ddims(obs_dim, n_act, hidden, &d, ws->mlp_depth)) return rc;
-    d.fn = ws->mlp_act_tanh ? TS_NET_ACT_TANH : TS_NET_ACT_RELU;
+    if (int rc = make_ddims(trunk, obs_dim, n_act, &d)) return rc;
     hipStream_t s = ts::as_stream(stream), side;
     const Mlp m = make_mlp((int)B, d.ka, d.hw, d.hid, d.depth, d.fn);
     const size_t spl = split_floats(m);
@@ -2033,8 +2047,9 @@ int ts_dsac_target_q(ts_workspace* ws, const float* actor, const float* critic1_
 }
 
 int ts_dsac_update(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, const float* obs, const int64_t* act,
-                   const float* returns, const float* weight, int64_t B, int64_t obs_dim, int64_t n_act, int64_t hidden,
-                   const ts_sac_hparams* hp, float* stats_out5, float* weight_out, float* grads_out, ts_stream_t stream) {
+                   const float* returns, const float* weight, int64_t B, int64_t obs_dim, int64_t n_act,
+                   const ts_mlp_trunk* trunk, const ts_sac_hparams* hp, float* stats_out5, float* weight_out,
+                   float* grads_out, ts_stream_t stream) {
     TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_dsac_update: workspace is NULL");
     TS_REQUIRE(st && hp && obs && act && returns && stats_out5 && B >= 1 && adam_step >= 1, TS_ERR_INVALID_ARG,
                "ts_dsac_update: bad argument");
@@ -2044,8 +2059,7 @@ int ts_dsac_update(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, 
     TS_REQUIRE(!hp->auto_alpha || (st->log_alpha && st->log_alpha_m && st->log_alpha_v), TS_ERR_INVALID_ARG,
                "ts_dsac_update: auto alpha needs log_alpha and its Adam moments");
     DDims d;
-    if (int rc = make_ddims(obs_dim, n_act, hidden, &d, ws->mlp_depth)) return rc;
-    d.fn = ws->mlp_act_tanh ? TS_NET_ACT_TANH : TS_NET_ACT_RELU;
+    if (int rc = make_ddims(trunk, obs_dim, n_act, &d)) return rc;
     hipStream_t s = ts::as_stream(stream), side;
     const Mlp m = make_mlp((int)B, d.ka, d.hw, d.hid, d.depth, d.fn);
     const size_t slab = slab_floats(m), spl = split_floats(m);
@@ -2164,14 +2178,15 @@ int ts_dsac_update(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, 
 // ---- REDQ ----------------------------------------------------------------------------------------------------------
 int ts_redq_target_q(ts_workspace* ws, const float* actor, const float* critics_old, int64_t E, const int32_t* h_subset,
                      int64_t S, int mean_mode, const float* log_alpha, double fixed_alpha, const float* obs_next,
-                     const float* noise, int64_t B, int64_t obs_dim, int64_t act_dim, float* out, ts_stream_t stream) {
+                     const float* noise, int64_t B, int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk, float* out,
+                     ts_stream_t stream) {
     TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_redq_target_q: workspace is NULL");
     TS_REQUIRE(B >= 1 && E >= 1 && S >= 1 && S <= E && actor && critics_old && h_subset && obs_next && noise && out,
                TS_ERR_INVALID_ARG, "ts_redq_target_q: bad argument");
     for (int64_t k = 0; k < S; ++k)
         TS_REQUIRE(h_subset[k] >= 0 && h_subset[k] < E, TS_ERR_INVALID_ARG, "ts_redq_target_q: subset index out of range");
     Dims d;
-    if (int rc = make_dims(ws, obs_dim, act_dim, &d)) return rc;
+    if (int rc = make_dims(trunk, obs_dim, act_dim, &d)) return rc;
     hipStream_t s = ts::as_stream(stream), side;
     const Mlp ma = make_mlp((int)B, d.ka, 64, d.hid, d.depth, d.fn), mc = make_mlp((int)B, d.kc, 32, d.hid, d.depth, d.fn);
     const size_t spl = std::max(split_floats(ma), split_floats(mc));
@@ -2220,8 +2235,8 @@ int ts_redq_target_q(ts_workspace* ws, const float* actor, const float* critics_
 
 int ts_redq_update(ts_workspace* ws, const ts_redq_state* st, int64_t E, int64_t critic_step, int64_t actor_step,
                    int do_actor, const float* obs, const float* act, const float* returns, const float* weight,
-                   const float* noise, int64_t B, int64_t obs_dim, int64_t act_dim, const ts_sac_hparams* hp,
-                   float* stats_out4, float* weight_out, float* grads_out, ts_stream_t stream) {
+                   const float* noise, int64_t B, int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk,
+                   const ts_sac_hparams* hp, float* stats_out4, float* weight_out, float* grads_out, ts_stream_t stream) {
     TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_redq_update: workspace is NULL");
     TS_REQUIRE(st && hp && obs && act && returns && stats_out4 && B >= 1 && E >= 1 && E <= 64 && critic_step >= 1 &&
                    actor_step >= 1, TS_ERR_INVALID_ARG, "ts_redq_update: bad argument");
@@ -2231,7 +2246,7 @@ int ts_redq_update(ts_workspace* ws, const ts_redq_state* st, int64_t E, int64_t
     TS_REQUIRE(!hp->auto_alpha || (st->log_alpha && st->log_alpha_m && st->log_alpha_v), TS_ERR_INVALID_ARG,
                "ts_redq_update: auto alpha needs log_alpha and its Adam moments");
     Dims d;
-    if (int rc = make_dims(ws, obs_dim, act_dim, &d)) return rc;
+    if (int rc = make_dims(trunk, obs_dim, act_dim, &d)) return rc;
     hipStream_t s = ts::as_stream(stream), side;
     const Mlp ma = make_mlp((int)B, d.ka, 64, d.hid, d.depth, d.fn), mc = make_mlp((int)B, d.kc, 32, d.hid, d.depth, d.fn);
     const size_t slab = std::max(slab_floats(ma), slab_floats(mc)), spl = std::max(split_floats(ma), split_floats(mc));

@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from .buffer import DeviceReplayBuffer, _i64_dev, gather_rows
 from .returns import compute_nstep_return
-from .sac import SACConfig, SACStateC, keys_depth, mlp_layout, trunk_flat, trunk_keys, trunk_unflat, use_hidden  # noqa: F401
+from .sac import MLPTrunk, SACConfig, SACStateC, keys_depth, mlp_layout, trunk_flat, trunk_keys, trunk_unflat  # noqa: F401
 
 TIANSHOU_KEYS = ["preprocess.model.model.0.weight", "preprocess.model.model.0.bias",
                  "preprocess.model.model.2.weight", "preprocess.model.model.2.bias",
@@ -71,6 +71,7 @@ class DiscreteSACEngine:
         if not actor.is_cuda:
             raise RuntimeError("DiscreteSACEngine needs parameters on an MI355X (no CPU fallback)")
         self.depth, self.activation = int(depth), activation
+        self._trunk = MLPTrunk(hidden, depth, activation)
         lay = layout(obs_dim, n_act, hidden, self.depth)
         if any(t.numel() != lay["count"] for t in (actor, critic1, critic2)):
             raise ValueError("flat parameter vectors do not match ts_dsac_layout")
@@ -96,8 +97,7 @@ class DiscreteSACEngine:
         return t if shape is None else t.reshape(shape)
 
     def _dims(self):
-        use_hidden(self._ws, self.hidden, self.depth, 0.0, self.activation)          # (the entry points read the depth from the workspace)
-        return _lib.i64(self.obs_dim), _lib.i64(self.n_act), _lib.i64(self.hidden)
+        return _lib.i64(self.obs_dim), _lib.i64(self.n_act), C.byref(self._trunk)
 
     @property
     def alpha(self) -> torch.Tensor:

@@ -322,6 +322,8 @@ def _q_forward(policy, batch, state=None, model=None, **kwargs):
 # SACPolicy (sac.py:108-131) over the mujoco_sac.py actor
 # ---------------------------------------------------------------------------------------------------------------------
 def _sac_forward(policy, batch, state=None, **kwargs):
+    import ctypes as C
+
     from torch.distributions import Independent, Normal
 
     from . import sac as S
@@ -342,10 +344,10 @@ def _sac_forward(policy, batch, state=None, **kwargs):
     logp = torch.empty(n, dtype=torch.float32, device=dev)
     mu, sigma = torch.empty_like(act), torch.empty_like(act)
     ws = _lib.default_workspace(dev.index or 0)
-    S.use_hidden(ws, hid, depth, float(spec.get("max_action") or 0.0), spec.get("activation", "relu"))
+    trunk = S.MLPTrunk(hid, depth, spec.get("activation", "relu"), float(spec.get("max_action") or 0.0))
     _lib.check(_lib.load().ts_sac_policy_forward_logits(
-        ws.handle, _lib.ptr(actor), _lib.ptr(obs), _lib.ptr(noise), _lib.i64(n), _lib.i64(obs_dim), _lib.i64(a), _lib.ptr(act),
-        _lib.ptr(logp), _lib.ptr(mu), _lib.ptr(sigma), _lib.current_stream(dev)))
+        ws.handle, _lib.ptr(actor), _lib.ptr(obs), _lib.ptr(noise), _lib.i64(n), _lib.i64(obs_dim), _lib.i64(a),
+        C.byref(trunk), _lib.ptr(act), _lib.ptr(logp), _lib.ptr(mu), _lib.ptr(sigma), _lib.current_stream(dev)))
     return type(batch)(logits=(mu, sigma), act=act, state=None, dist=Independent(Normal(loc=mu, scale=sigma), 1),
                        log_prob=logp.unsqueeze(-1))
 

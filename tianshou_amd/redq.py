@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from .buffer import DeviceReplayBuffer, gather_rows
 from .returns import compute_nstep_return
-from .sac import SACConfig, SACEngine, critic_flat_from_torch, critic_flat_to_torch, layout, mlp_layout, use_hidden  # noqa: F401
+from .sac import MLPTrunk, SACConfig, SACEngine, critic_flat_from_torch, critic_flat_to_torch, layout, mlp_layout  # noqa: F401
 
 TIANSHOU_CRITIC_KEYS = ["preprocess.model.model.0.weight", "preprocess.model.model.0.bias_weights",
                         "preprocess.model.model.2.weight", "preprocess.model.model.2.bias_weights",
@@ -93,6 +93,7 @@ class REDQEngine:
         if cfg.target_mode not in ("min", "mean") or not 0 < cfg.subset_size <= cfg.ensemble_size <= 64:
             raise ValueError("target_mode must be 'min' or 'mean' and 0 < subset_size <= ensemble_size <= 64")
         self.depth, self.max_action, self.activation = int(depth), float(max_action), activation      # (as in SACEngine)
+        self._trunk = MLPTrunk(hidden, depth, activation, max_action)
         n_actor, n_critic = mlp_layout(obs_dim, hidden, self.depth, 64)[1][-1], mlp_layout(obs_dim + act_dim, hidden, self.depth, 32)[1][-1]
         if actor.numel() != n_actor or critics.numel() != cfg.ensemble_size * n_critic:
             raise ValueError("flat parameter vectors do not match ts_mlp_layout / the ensemble size")
@@ -124,12 +125,11 @@ class REDQEngine:
         if sub.size != self.cfg.subset_size:
             raise ValueError("subset must hold subset_size member indices")
         out = torch.empty(b, dtype=torch.float32, device=self.device)
-        use_hidden(self._ws, self.hidden, self.depth, self.max_action, self.activation)
         _lib.check(_lib.load().ts_redq_target_q(
             self._ws.handle, _lib.ptr(self.actor), _lib.ptr(self.critics_old), _lib.i64(self.cfg.ensemble_size),
             sub.ctypes.data_as(C.POINTER(C.c_int32)), _lib.i64(sub.size), C.c_int(int(self.cfg.target_mode == "mean")),
             _lib.ptr(self.log_alpha if self.cfg.auto_alpha else None), _lib.f64(self.cfg.alpha), _lib.ptr(obs_next),
-            _lib.ptr(noise), _lib.i64(b), _lib.i64(self.obs_dim), _lib.i64(self.act_dim), _lib.ptr(out),
+            _lib.ptr(noise), _lib.i64(b), _lib.i64(self.obs_dim), _lib.i64(self.act_dim), C.byref(self._trunk), _lib.ptr(out),
             _lib.current_stream(self.device)))
         return out
 
@@ -168,11 +168,10 @@ class REDQEngine:
         w_out = torch.empty(b, dtype=torch.float32, device=self.device)
         st = REDQStateC(*[getattr(self, n).data_ptr() for n, _ in REDQStateC._fields_])
         hp = self.cfg.to_c(lr_scale)
-        use_hidden(self._ws, self.hidden, self.depth, self.max_action, self.activation)
         _lib.check(_lib.load().ts_redq_update(
             self._ws.handle, C.byref(st), _lib.i64(self.cfg.ensemble_size), _lib.i64(self.critic_gradient_step),
             _lib.i64(max(self.actor_steps, 1)), C.c_int(int(do_actor)), _lib.ptr(obs), _lib.ptr(act), _lib.ptr(returns),
-            _lib.ptr(weight), _lib.ptr(noise), _lib.i64(b), _lib.i64(self.obs_dim), _lib.i64(self.act_dim), C.byref(hp),
+            _lib.ptr(weight), _lib.ptr(noise), _lib.i64(b), _lib.i64(self.obs_dim), _lib.i64(self.act_dim), C.byref(self._trunk), C.byref(hp),
             _lib.ptr(self._stats), _lib.ptr(w_out), _lib.ptr(grads_out), _lib.current_stream(self.device)))
         stats = self._stats.clone()
         stats[2] = self.alpha[0]                                                  # Alpha.value after this update

@@ -41,6 +41,21 @@ class SACHParams(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+ACTIVATIONS = {"relu": 1, "tanh": 0}      # TS_NET_ACT_* (include/tsengine.h)
+
+
+class MLPTrunk(C.Structure):
+    """struct ts_mlp_trunk (include/tsengine.h): the Net[hidden] * depth trunk of a SAC / TD3 / DDPG / REDQ / DiscreteSAC engine,
+    passed with every library call (max_action: the bound of SAC's / REDQ's Gaussian actor, 0 = unbounded)."""
+
+    _fields_ = [("hidden", C.c_int64), ("depth", C.c_int32), ("activation", C.c_int32), ("max_action", C.c_double)]
+
+    def __init__(self, hidden: int, depth: int = 2, activation: str = "relu", max_action: float = 0.0):
+        if activation not in ACTIVATIONS:
+            raise NotImplementedError("activation must be 'relu' (Net's default) or 'tanh'")
+        super().__init__(int(hidden), int(depth), ACTIVATIONS[activation], float(max_action))
+
+
 class SACStateC(C.Structure):
     """struct ts_sac_state (include/tsengine.h)."""
 
@@ -97,20 +112,6 @@ def mlp_layout(in_dim: int, hidden: int, depth: int, head_cols: int) -> tuple[in
     out = (C.c_int64 * (depth + 3))()
     _lib.check(_lib.load().ts_mlp_layout(_lib.i64(in_dim), _lib.i64(hidden), _lib.i64(depth), _lib.i64(head_cols), out))
     return int(out[0]), [int(v) for v in out[1:]]
-
-
-ACTIVATIONS = {"relu": 1, "tanh": 0}      # TS_NET_ACT_* (include/tsengine.h)
-
-
-def use_hidden(ws, hidden: int, depth: int = 2, max_action: float = 0.0, activation: str = "relu") -> None:
-    """Hidden width, depth and the Gaussian actor's tanh bound are properties of the workspace (ts_mlp_set_trunk,
-    ts_sac_set_actor_bound): every SAC / TD3 / DDPG / REDQ / DiscreteSAC engine sets its own before each call, since engines of
-    different networks may share the device's default workspace."""
-    lib = _lib.load()
-    _lib.check(lib.ts_mlp_set_trunk(ws.handle, _lib.i64(hidden), _lib.i64(depth)))
-    _lib.check(lib.ts_sac_set_actor_bound(ws.handle, _lib.f64(max_action)))
-    if activation != "relu":                  # (ts_mlp_set_trunk has just reset it to ReLU)
-        _lib.check(lib.ts_mlp_set_activation(ws.handle, C.c_int(ACTIVATIONS[activation])))
 
 
 def _l1(w: torch.Tensor, b: torch.Tensor, k_pad: int) -> torch.Tensor:
@@ -224,9 +225,8 @@ class SACEngine:
         0 = `unbounded=True` as in the examples."""
         if not actor.is_cuda:
             raise RuntimeError("SACEngine needs parameters on an MI355X (no CPU fallback)")
-        if activation not in ACTIVATIONS:
-            raise NotImplementedError("activation must be 'relu' (Net's default) or 'tanh'")
         self.hidden, self.depth, self.max_action, self.activation = int(hidden), int(depth), float(max_action), activation
+        self._trunk = MLPTrunk(hidden, depth, activation, max_action)
         n_actor, n_critic = mlp_layout(obs_dim, self.hidden, self.depth, 64)[1][-1], mlp_layout(obs_dim + act_dim, self.hidden, self.depth, 32)[1][-1]
         if actor.numel() != n_actor or critic1.numel() != n_critic or critic2.numel() != n_critic:
             raise ValueError("flat parameter vectors do not match ts_mlp_layout")
@@ -268,10 +268,9 @@ class SACEngine:
         noise = None if noise is None else self._f32(noise, (b, self.act_dim))
         act = torch.empty((b, self.act_dim), dtype=torch.float32, device=self.device)
         logp = torch.empty(b, dtype=torch.float32, device=self.device)
-        use_hidden(self._ws, self.hidden, self.depth, self.max_action, self.activation)
         _lib.check(_lib.load().ts_sac_policy_forward(
             self._ws.handle, _lib.ptr(self.actor), _lib.ptr(obs), _lib.ptr(noise), _lib.i64(b), _lib.i64(self.obs_dim),
-            _lib.i64(self.act_dim), _lib.ptr(act), _lib.ptr(logp), None, _lib.current_stream(self.device)))
+            _lib.i64(self.act_dim), C.byref(self._trunk), _lib.ptr(act), _lib.ptr(logp), None, _lib.current_stream(self.device)))
         return act, logp.unsqueeze(-1)
 
     # -- _target_q ---------------------------------------------------------------------------------------------
@@ -280,11 +279,10 @@ class SACEngine:
         b = obs_next.shape[0]
         noise = self._f32(noise, (b, self.act_dim))
         out = torch.empty(b, dtype=torch.float32, device=self.device)
-        use_hidden(self._ws, self.hidden, self.depth, self.max_action, self.activation)
         _lib.check(_lib.load().ts_sac_target_q(
             self._ws.handle, _lib.ptr(self.actor), _lib.ptr(self.critic1_old), _lib.ptr(self.critic2_old),
             _lib.ptr(self.log_alpha if self.cfg.auto_alpha else None), _lib.f64(self.cfg.alpha), _lib.ptr(obs_next),
-            _lib.ptr(noise), _lib.i64(b), _lib.i64(self.obs_dim), _lib.i64(self.act_dim), _lib.ptr(out),
+            _lib.ptr(noise), _lib.i64(b), _lib.i64(self.obs_dim), _lib.i64(self.act_dim), C.byref(self._trunk), _lib.ptr(out),
             _lib.current_stream(self.device)))
         return out
 
@@ -307,12 +305,11 @@ class SACEngine:
             b = idx.numel()
             noise = self._f32(noise, (b, self.act_dim))
             out = torch.empty(b, dtype=torch.float32, device=self.device)
-            use_hidden(self._ws, self.hidden, self.depth, self.max_action, self.activation)
             _lib.check(_lib.load().ts_sac_returns_rows(
                 self._ws.handle, _lib.ptr(self.actor), _lib.ptr(self.critic1_old), _lib.ptr(self.critic2_old),
                 _lib.ptr(self.log_alpha if self.cfg.auto_alpha else None), _lib.f64(self.cfg.alpha), _lib.ptr(buffer.obs_next),
                 _lib.ptr(buffer.rew), _lib.ptr(buffer.terminated), _lib.ptr(idx), _lib.ptr(noise), _lib.i64(b),
-                _lib.i64(self.obs_dim), _lib.i64(self.act_dim), _lib.f64(self.cfg.gamma), _lib.ptr(out),
+                _lib.i64(self.obs_dim), _lib.i64(self.act_dim), C.byref(self._trunk), _lib.f64(self.cfg.gamma), _lib.ptr(out),
                 _lib.current_stream(self.device)))
             return out
 
@@ -339,10 +336,9 @@ class SACEngine:
         stats = torch.empty(5, dtype=torch.float32, device=self.device)
         w_out = torch.empty(b, dtype=torch.float32, device=self.device)
         st, hp = self._state_c(), self.cfg.to_c(lr_scale)
-        use_hidden(self._ws, self.hidden, self.depth, self.max_action, self.activation)
         _lib.check(_lib.load().ts_sac_update(
             self._ws.handle, C.byref(st), _lib.i64(self.adam_step), _lib.ptr(obs), _lib.ptr(act), _lib.ptr(returns),
-            _lib.ptr(weight), _lib.ptr(noise), _lib.i64(b), _lib.i64(self.obs_dim), _lib.i64(self.act_dim),
+            _lib.ptr(weight), _lib.ptr(noise), _lib.i64(b), _lib.i64(self.obs_dim), _lib.i64(self.act_dim), C.byref(self._trunk),
             C.byref(hp), _lib.ptr(stats), _lib.ptr(w_out), _lib.ptr(grads_out), _lib.current_stream(self.device)))
         return stats, w_out
 
@@ -360,10 +356,9 @@ class SACEngine:
         stats = torch.empty(5, dtype=torch.float32, device=self.device)
         w_out = torch.empty(b, dtype=torch.float32, device=self.device)
         st, hp = self._state_c(), self.cfg.to_c(lr_scale)
-        use_hidden(self._ws, self.hidden, self.depth, self.max_action, self.activation)
         _lib.check(_lib.load().ts_sac_update_rows(
             self._ws.handle, C.byref(st), _lib.i64(self.adam_step), _lib.ptr(buffer.obs), _lib.ptr(buffer.act), _lib.ptr(idx),
-            _lib.ptr(returns), _lib.ptr(weight), _lib.ptr(noise), _lib.i64(b), _lib.i64(self.obs_dim), _lib.i64(self.act_dim),
+            _lib.ptr(returns), _lib.ptr(weight), _lib.ptr(noise), _lib.i64(b), _lib.i64(self.obs_dim), _lib.i64(self.act_dim), C.byref(self._trunk),
             C.byref(hp), _lib.ptr(stats), _lib.ptr(w_out), _lib.current_stream(self.device)))
         return stats, w_out
 
@@ -394,10 +389,9 @@ class SACEngine:
         st, hp = self._state_c(), self.cfg.to_c(lr_scale)
         rp = SACReplayC(buffer.obs.data_ptr(), buffer.act.data_ptr(), buffer.obs_next.data_ptr(), buffer.rew.data_ptr(),
                         buffer.terminated.data_ptr())
-        use_hidden(self._ws, self.hidden, self.depth, self.max_action, self.activation)
         _lib.check(_lib.load().ts_sac_learn_rows(
             self._ws.handle, C.byref(st), _lib.i64(self.adam_step), C.byref(rp), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(noise2),
-            C.c_int(fill), C.c_uint64(seed), C.c_uint64(off), _lib.i64(b), _lib.i64(self.obs_dim), _lib.i64(self.act_dim),
+            C.c_int(fill), C.c_uint64(seed), C.c_uint64(off), _lib.i64(b), _lib.i64(self.obs_dim), _lib.i64(self.act_dim), C.byref(self._trunk),
             C.byref(hp), _lib.f64(self.cfg.gamma), _lib.ptr(ret), _lib.ptr(stats), _lib.ptr(w_out), _lib.current_stream(self.device)))
         return stats, w_out, ret, noise2
 
@@ -423,9 +417,8 @@ class SACEngine:
 
     def update_phase(self, ctx: dict, phase: int, grads: torch.Tensor) -> None:
         st = self._state_c()
-        use_hidden(self._ws, self.hidden, self.depth, self.max_action, self.activation)
         _lib.check(_lib.load().ts_sac_update_phase(
             self._ws.handle, C.byref(st), _lib.i64(self.adam_step), _lib.ptr(ctx["obs"]), _lib.ptr(ctx["act"]),
             _lib.ptr(ctx["returns"]), _lib.ptr(ctx["weight"]), _lib.ptr(ctx["noise"]), _lib.i64(ctx["b"]),
-            _lib.i64(self.obs_dim), _lib.i64(self.act_dim), C.byref(ctx["hp"]), C.c_int(phase), _lib.ptr(ctx["stats"]),
+            _lib.i64(self.obs_dim), _lib.i64(self.act_dim), C.byref(self._trunk), C.byref(ctx["hp"]), C.c_int(phase), _lib.ptr(ctx["stats"]),
             _lib.ptr(ctx["w_out"]), _lib.ptr(grads), _lib.current_stream(self.device)))

@@ -17,8 +17,8 @@ from . import _lib
 from . import widths as W
 from .buffer import DeviceReplayBuffer, gather_rows
 from .returns import compute_nstep_return
-from .sac import (HID, _dense, _l1, critic_flat_from_torch, critic_flat_to_torch, critic_keys, mlp_layout,  # noqa: F401
-                  keys_depth, trunk_flat, trunk_keys, trunk_unflat, use_hidden)
+from .sac import (HID, MLPTrunk, _dense, _l1, critic_flat_from_torch, critic_flat_to_torch, critic_keys, mlp_layout,  # noqa: F401
+                  keys_depth, trunk_flat, trunk_keys, trunk_unflat)
 
 TIANSHOU_ACTOR_KEYS = ["preprocess.model.model.0.weight", "preprocess.model.model.0.bias",
                        "preprocess.model.model.2.weight", "preprocess.model.model.2.bias",
@@ -103,6 +103,7 @@ class TD3Engine:
         if cfg.twin != (critic2 is not None):
             raise ValueError("cfg.twin and critic2 disagree")
         self.hidden, self.depth, self.activation = int(hidden), int(depth), activation
+        self._trunk = MLPTrunk(hidden, depth, activation)
         if actor.numel() != mlp_layout(obs_dim, self.hidden, self.depth, 32)[1][-1] \
                 or critic1.numel() != mlp_layout(obs_dim + act_dim, self.hidden, self.depth, 32)[1][-1]:
             raise ValueError("flat parameter vectors do not match ts_mlp_layout")
@@ -126,10 +127,9 @@ class TD3Engine:
     def policy_forward(self, obs) -> torch.Tensor:
         obs = self._f32(obs)
         act = torch.empty((obs.shape[0], self.act_dim), dtype=torch.float32, device=self.device)
-        use_hidden(self._ws, self.hidden, self.depth, 0.0, self.activation)
         _lib.check(_lib.load().ts_td3_policy_forward(
             self._ws.handle, _lib.ptr(self.actor), _lib.ptr(obs), _lib.i64(obs.shape[0]), _lib.i64(self.obs_dim),
-            _lib.i64(self.act_dim), _lib.f64(self.cfg.max_action), _lib.ptr(act), _lib.current_stream(self.device)))
+            _lib.i64(self.act_dim), C.byref(self._trunk), _lib.f64(self.cfg.max_action), _lib.ptr(act), _lib.current_stream(self.device)))
         return act
 
     def target_q(self, obs_next, noise=None) -> torch.Tensor:
@@ -140,10 +140,9 @@ class TD3Engine:
             raise ValueError("TD3 needs the target-smoothing noise (the torch.randn draws of td3.py:196)")
         noise = self._f32(noise, (b, self.act_dim)) if cfg.twin else None
         out = torch.empty(b, dtype=torch.float32, device=self.device)
-        use_hidden(self._ws, self.hidden, self.depth, 0.0, self.activation)
         _lib.check(_lib.load().ts_td3_target_q(
             self._ws.handle, _lib.ptr(self.actor_old), _lib.ptr(self.critic1_old), _lib.ptr(self.critic2_old),
-            _lib.ptr(obs_next), _lib.ptr(noise), _lib.i64(b), _lib.i64(self.obs_dim), _lib.i64(self.act_dim),
+            _lib.ptr(obs_next), _lib.ptr(noise), _lib.i64(b), _lib.i64(self.obs_dim), _lib.i64(self.act_dim), C.byref(self._trunk),
             _lib.f64(cfg.max_action), _lib.f64(cfg.policy_noise), _lib.f64(cfg.noise_clip), _lib.ptr(out),
             _lib.current_stream(self.device)))
         return out
@@ -177,10 +176,9 @@ class TD3Engine:
         st = TD3StateC(*[None if getattr(self, n) is None else getattr(self, n).data_ptr() for n in names])
         hp = TD3HParams(cfg.actor_lr * lr_scale, cfg.critic_lr * lr_scale, cfg.betas[0], cfg.betas[1], cfg.adam_eps,
                         cfg.tau, cfg.max_action, int(upd), 0)
-        use_hidden(self._ws, self.hidden, self.depth, 0.0, self.activation)
         _lib.check(_lib.load().ts_td3_update(
             self._ws.handle, C.byref(st), _lib.i64(self.cnt), _lib.i64(max(self.actor_steps, 1)), _lib.ptr(obs),
             _lib.ptr(act), _lib.ptr(returns), _lib.ptr(weight), _lib.i64(b), _lib.i64(self.obs_dim),
-            _lib.i64(self.act_dim), C.byref(hp), _lib.ptr(self._stats), _lib.ptr(w_out), _lib.ptr(grads_out),
+            _lib.i64(self.act_dim), C.byref(self._trunk), C.byref(hp), _lib.ptr(self._stats), _lib.ptr(w_out), _lib.ptr(grads_out),
             _lib.current_stream(self.device)))
         return self._stats.clone(), w_out
