@@ -489,19 +489,12 @@ def test_row_indexed_entry_points_are_bit_identical(auto, weighted):
     sequence) == gather_rows + ts_sac_target_q + ts_nstep_return_fused, and ts_sac_update_rows == gather_rows + ts_sac_update:
     returns, statistics, PER weights, parameters and Adam moments bit for bit over three updates on a buffer with
     terminations and repeated indices."""
-    from tianshou_amd.buffer import DeviceReplayBuffer
+    from tests.sac_routes_common import random_replay_buffer
 
     obs_dim, act_dim, B, slots, E = 23, 5, 200, 4096, 4
     cfg = OS.SACConfig(auto_alpha=auto, log_alpha0=-0.2, alpha=0.15, target_entropy=-float(act_dim), actor_lr=3e-4,
                        critic_lr=1e-3, alpha_lr=1e-3, tau=0.02, n_step=1)
-    g = torch.Generator().manual_seed(3)
-    T = slots // E
-    off = np.arange(E + 1, dtype=np.int64) * T
-    buf = DeviceReplayBuffer(offset=off, last_index=off[:-1] + T - 1, lengths=np.full(E, T, np.int64),
-                             insertion=np.zeros(E, np.int64), rew=torch.randn(slots, generator=g).double().numpy(),
-                             terminated=(torch.rand(slots, generator=g) < 0.1).numpy(), truncated=np.zeros(slots, bool),
-                             obs=torch.randn(slots, obs_dim, generator=g).numpy(), act=(torch.rand(slots, act_dim, generator=g) * 2 - 1).numpy(),
-                             obs_next=torch.randn(slots, obs_dim, generator=g).numpy())
+    buf = random_replay_buffer(obs_dim, act_dim, slots, E)
     out = {}
     import os
     for mode in ("rows", "gather"):
@@ -537,19 +530,13 @@ def test_one_call_update_is_bit_identical(auto, weighted, hidden, activation, fi
     statistics, PER weights, every parameter vector, lagged critic and Adam moment bit for bit over four updates on a buffer with
     terminations and repeated indices.  Net[256, 256] ReLU rides on the fused sequence; three hidden layers / a tanh trunk run the
     two sequences back to back inside the call."""
-    from tianshou_amd.buffer import DeviceReplayBuffer, normal_noise
+    from tests.sac_routes_common import random_replay_buffer
+    from tianshou_amd.buffer import normal_noise
 
     obs_dim, act_dim, B, slots, E = 23, 5, 300, 4096, 4
     cfg = OS.SACConfig(auto_alpha=auto, log_alpha0=-0.2, alpha=0.15, target_entropy=-float(act_dim), actor_lr=3e-4,
                        critic_lr=1e-3, alpha_lr=1e-3, tau=0.02, n_step=1)
-    g = torch.Generator().manual_seed(3)
-    T = slots // E
-    off = np.arange(E + 1, dtype=np.int64) * T
-    buf = DeviceReplayBuffer(offset=off, last_index=off[:-1] + T - 1, lengths=np.full(E, T, np.int64),
-                             insertion=np.zeros(E, np.int64), rew=torch.randn(slots, generator=g).double().numpy(),
-                             terminated=(torch.rand(slots, generator=g) < 0.1).numpy(), truncated=np.zeros(slots, bool),
-                             obs=torch.randn(slots, obs_dim, generator=g).numpy(), act=(torch.rand(slots, act_dim, generator=g) * 2 - 1).numpy(),
-                             obs_next=torch.randn(slots, obs_dim, generator=g).numpy())
+    buf = random_replay_buffer(obs_dim, act_dim, slots, E)
     names = ("actor", "critic1", "critic2", "critic1_old", "critic2_old", "actor_m", "actor_v", "critic1_m", "critic1_v", "critic2_m",
              "critic2_v", "log_alpha")
     out = {}
