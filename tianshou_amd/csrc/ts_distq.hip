@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256) void qr_loss_kernel(const float* __restrict__ 
     float wl = 0.f, sl = 0.f;
     for (int i = threadIdx.x; i < N; i += 256) {
         const float theta = th[i], tau = tau_hat[i];
-        float li = 0.f, ai = 0.f, g = 0.f;
+        float li = 0.f, ai = 0.f, g = 0.f, gc = 0.f;       // gc: compensation of g (Kahan)
         for (int j = 0; j < N; ++j) {
             const float d = T[j] - theta, ad = fabsf(d);
             const bool quad = ad < 1.f;
@@ -185,7 +185,11 @@ __global__ __launch_bounds__(256) void qr_loss_kernel(const float* __restrict__ 
             const float w = fabsf(tau - (d <= 0.f ? 1.f : 0.f));
             li += l * w;
             ai += l;
-            g += w * (quad ? d : (d > 0.f ? 1.f : -1.f));
+            // in the linear region the N terms are all +-w: added one after the other they round the same way every time
+            // and the error grows with N (27 ulp of the sum at N = 255), so the gradient sum is compensated
+            const float y = w * (quad ? d : (d > 0.f ? 1.f : -1.f)) - gc, t = g + y;
+            gc = (t - g) - y;
+            g = t;
         }
         drow[a * N + i] = -g * scale;
         wl += li;
@@ -350,8 +354,9 @@ __global__ __launch_bounds__(256) void dueling_kernel(float* __restrict__ q, con
     float* row = q + b * ldq;
     float s = 0.f;
     for (int a = 0; a < A; ++a) s += row[a * N + j];
-    const float shift = v[b * ldv + j] - s / (float)A;
-    for (int a = 0; a < A; ++a) row[a * N + j] += shift;
+    // the reference's order, (q - mean) + v: at A == 1 the advantage cancels exactly and the logits are the value row
+    const float mean = s / (float)A, vj = v[b * ldv + j];
+    for (int a = 0; a < A; ++a) row[a * N + j] = (row[a * N + j] - mean) + vj;
 }
 
 // backward of dueling_kernel: dq = dl - mean_a dl (in place), dv = sum_a dl; padding columns of dv zeroed
