@@ -200,13 +200,14 @@ __global__ __launch_bounds__(NT, 1) void mlp_ppo_update_small_kernel(SmallArgs a
         }
         __syncthreads();
         // ---- heads: O[s][c] = sum_f H2[s][f] WH[f][c] + bh[c]; the four waves split (sample half) x (K half), the K
-        // halves meet in LDS (wave pairs (0, 2) and (1, 3))
+        // halves meet in LDS (wave pairs (0, 2) and (1, 3)).  The bias is added LAST, to the finished sum, as the GEMM path
+        // does (ts_conv.hip): an accumulator that starts at a large bias (a logit of 1e4 has float32 spacing 9.8e-4) rounds
+        // every one of its partial sums at the bias's spacing and ends several spacings from the exact value.
         {
             const int sm = wave & 1, kh = wave >> 1;
             const float* X = lds + L_H2 + (32 * sm + i) * P65 + 32 * kh + h;
             const float* W = lds + L_WH + (32 * kh + h) * P33 + i;
-            f32x16 acc = splat(kh == 0 ? lds[L_WH + HID * P33 + i] : 0.f);
-            acc = mma(acc, 32, [&](int k) { return X[k]; }, [&](int k) { return W[k * P33]; });
+            f32x16 acc = mma(splat(0.f), 32, [&](int k) { return X[k]; }, [&](int k) { return W[k * P33]; });
             float* O = lds + (kh == 0 ? L_O : L_DO) + (32 * sm) * P33 + i;       // second halves park in the dO array
 #pragma unroll
             for (int r = 0; r < 16; ++r) O[featF(r, h) * P33] = acc[r];
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(NT, 1) void mlp_ppo_update_small_kernel(SmallArgs a
             float* dd = lds + L_DO + lane * P33;
             const bool valid = lane < c.count;
             const float w = 1.f / (float)c.batch;
-            for (int j = 0; j <= A; ++j) o[j] = o[j] + dd[j];                    // the two K halves
+            for (int j = 0; j <= A; ++j) o[j] = (o[j] + dd[j]) + lds[L_WH + HID * P33 + j];      // the two K halves, then bh
             const float* hb = o;
             const int act = __float_as_int(lds[L_SC + 4 * CH + lane]);
             const float lse = logsumexp(hb, A);
