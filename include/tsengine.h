@@ -812,6 +812,17 @@ int ts_distq_update(ts_workspace* ws, float* params, float* adam_m, float* adam_
                     const float* weight, int64_t B, const ts_distq_hparams* hp, float* prio_out, float* loss_out,
                     float* target_dist_out, float* grad_out, ts_stream_t stream);
 
+/* DiscreteCQL._update_with_batch (tianshou/algorithm/imitation/discrete_cql.py:80-113) on QRDQNet: QRDQN's update with the
+ * conservative term  cql_loss = mean_b(logsumexp_a Q[b, a] - Q[b, act_b]),  Q[b, a] = mean_j x[b, a, j]  (the PER weight
+ * does not enter it), loss = qr_loss + min_q_weight * cql_loss.  Its gradient reaches the quantile columns of EVERY action.
+ * Arguments as ts_distq_update with kind = TS_DISTQ_QR (tau_hat = its `aux`); min_q_weight finite and >= 0;
+ * loss3_out float32[3] = [loss, qr_loss, cql_loss]; prio_out as QRDQN's.  ts_distq_forward / ts_distq_next_dist /
+ * ts_distq_param_count serve this learner unchanged.  hp->lr < 0: gradient only. */
+int ts_dcql_update(ts_workspace* ws, float* params, float* adam_m, float* adam_v, int64_t adam_step, int64_t c, int64_t h,
+                   int64_t w, int64_t n_act, int64_t n_atoms, const float* tau_hat, const void* obs_nhwc, int obs_u8,
+                   const int64_t* act, const float* returns, const float* weight, int64_t B, const ts_distq_hparams* hp,
+                   double min_q_weight, float* prio_out, float* loss3_out, float* grad_out, ts_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * IQN (tianshou/algorithm/modelfree/iqn.py) on ImplicitQuantileNetwork (tianshou/utils/net/discrete.py:163-216) with
  * preprocess_net = DQNet(features_only=True), hidden_sizes = [512] (examples/atari/atari_iqn.py):

@@ -1,4 +1,4 @@
-// ts_distq.hip -- distributional Q-learning (QRDQN, C51) on the Atari networks for gfx950.
+// ts_distq.hip -- distributional Q-learning (QRDQN, C51, Rainbow, DiscreteCQL) on the Atari networks for gfx950.
 //
 // Replaces, on device-resident NHWC observations:
 //   QRDQNet.forward / C51Net.forward          tianshou/env/atari/atari_network.py:227-235 / :141-151
@@ -8,6 +8,7 @@
 //                                             qrdqn.py:93-104, c51.py:123-132
 //   QRDQN._update_with_batch                  qrdqn.py:106-131 (quantile Huber loss, new priorities)
 //   C51._update_with_batch                    c51.py:133-160  (projection, cross entropy, new priorities)
+//   DiscreteCQL._update_with_batch            imitation/discrete_cql.py:80-113 (QRDQN's loss + the conservative term)
 //   Optimizer.step                            algorithm_base.py:484-500 (clip_grad_norm_ + Adam)
 // The network is DQNet with n_act * n_atoms outputs: the trunk, fc1 and the head all run on the fp32-MFMA
 // implicit-GEMM kernels of ts_conv.hip; this file adds the per-sample distribution kernels and the orchestration.
@@ -151,6 +152,26 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {      // al
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// The quantile-Huber terms of one theta_i against the N targets T_j (the inner sums of the QRDQN loss below), shared by
+// qr_loss_kernel and cql_loss_kernel:  li = sum_j l_ij w_ij,  ai = sum_j l_ij,  g = sum_j w_ij clamp(d_ij, -1, 1)
+__device__ __forceinline__ void qr_terms(const float* T, int N, float theta, float tau, float& li, float& ai, float& g) {
+    float gc = 0.f;                                        // gc: compensation of g (Kahan)
+    li = 0.f; ai = 0.f; g = 0.f;
+    for (int j = 0; j < N; ++j) {
+        const float d = T[j] - theta, ad = fabsf(d);
+        const bool quad = ad < 1.f;
+        const float l = quad ? 0.5f * d * d : ad - 0.5f;
+        const float w = fabsf(tau - (d <= 0.f ? 1.f : 0.f));
+        li += l * w;
+        ai += l;
+        // in the linear region the N terms are all +-w: added one after the other they round the same way every time
+        // and the error grows with N (27 ulp of the sum at N = 255), so the gradient sum is compensated
+        const float y = w * (quad ? d : (d > 0.f ? 1.f : -1.f)) - gc, t = g + y;
+        gc = (t - g) - y;
+        g = t;
+    }
+}
+
 // ---- QRDQN loss (qrdqn.py:111-128), one workgroup per sample:
 //   theta_i = x[b, act_b, i], T_j = returns[b, j], d_ij = T_j - theta_i
 //   l_ij = smooth_l1(d_ij), w_ij = |tau_hat_i - 1{d_ij <= 0}|
@@ -176,21 +197,8 @@ __global__ __launch_bounds__(256) void qr_loss_kernel(const float* __restrict__ 
         if (k / N != a) drow[k] = 0.f;
     float wl = 0.f, sl = 0.f;
     for (int i = threadIdx.x; i < N; i += 256) {
-        const float theta = th[i], tau = tau_hat[i];
-        float li = 0.f, ai = 0.f, g = 0.f, gc = 0.f;       // gc: compensation of g (Kahan)
-        for (int j = 0; j < N; ++j) {
-            const float d = T[j] - theta, ad = fabsf(d);
-            const bool quad = ad < 1.f;
-            const float l = quad ? 0.5f * d * d : ad - 0.5f;
-            const float w = fabsf(tau - (d <= 0.f ? 1.f : 0.f));
-            li += l * w;
-            ai += l;
-            // in the linear region the N terms are all +-w: added one after the other they round the same way every time
-            // and the error grows with N (27 ulp of the sum at N = 255), so the gradient sum is compensated
-            const float y = w * (quad ? d : (d > 0.f ? 1.f : -1.f)) - gc, t = g + y;
-            gc = (t - g) - y;
-            g = t;
-        }
+        float li, ai, g;
+        qr_terms(T, N, th[i], tau_hat[i], li, ai, g);
         drow[a * N + i] = -g * scale;
         wl += li;
         sl += ai;
@@ -201,6 +209,68 @@ __global__ __launch_bounds__(256) void qr_loss_kernel(const float* __restrict__ 
         const float huber = wl / (float)N;
         prio[b] = sl / (float)N;
         lw[b] = huber * wb;
+    }
+}
+
+// ---- DiscreteCQL loss (imitation/discrete_cql.py:80-113), one workgroup per sample: the QRDQN terms above on the dataset
+// action's row, plus
+//   q_a = mean_j x[b, a, j] (one wave per action, distq_head_kernel's order),  lse = m + log(sum_a exp(q_a - m)), m = max_a q_a
+//   cql_b = lse - q_act,   p_a = exp(q_a - m) / sum (the same exponentials),   loss = qr_loss + cql_w mean_b(cql_b)
+//   d loss / d x[b, a, j] = (cql_w / (B N)) (p_a - 1{a = act_b})  in EVERY live column, on top of the QRDQN gradient in the
+//   dataset action's columns; the padding columns get 0.  The PER weight does not enter the CQL term.
+__global__ __launch_bounds__(256) void cql_loss_kernel(const float* __restrict__ x, const int64_t* __restrict__ act,
+                                                       const float* __restrict__ ret, const float* __restrict__ weight,
+                                                       const float* __restrict__ tau_hat, int64_t B, int A, int N, int ld,
+                                                       float cql_w, float* __restrict__ d_head, float* __restrict__ prio,
+                                                       float* __restrict__ lw, float* __restrict__ cw) {
+    __shared__ float th[MAX_ATOMS], T[MAX_ATOMS], red[4], qa[MAX_ACT], pa[MAX_ACT];
+    const int64_t b = blockIdx.x;
+    const int a = (int)act[b];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* xrow = x + b * ld;
+    for (int j = threadIdx.x; j < N; j += 256) {
+        th[j] = xrow[a * N + j];
+        T[j] = ret[b * N + j];
+    }
+    for (int k = wave; k < A; k += 4) {
+        float s = 0.f;
+        for (int j = lane; j < N; j += 64) s += xrow[k * N + j];
+        s = wave_sum(s);
+        if (lane == 0) qa[k] = s / (float)N;
+    }
+    __syncthreads();
+    // A <= 64: one lane per action; every wave computes the same values in the same order
+    const float q = lane < A ? qa[lane] : -INFINITY;
+    const float m = wave_max(q);
+    const float e = lane < A ? expf(q - m) : 0.f;
+    const float se = wave_sum(e);
+    const float cql = (m + logf(se)) - qa[a];
+    if (wave == 0 && lane < A) pa[lane] = e / se;
+    __syncthreads();
+    const float wb = weight ? weight[b] : 1.f;
+    const float scale = wb / ((float)B * (float)N);
+    const float cs = cql_w / ((float)B * (float)N);
+    float* drow = d_head + b * ld;
+    for (int k = threadIdx.x; k < ld; k += 256) {
+        const int ka = k / N;
+        if (ka != a) drow[k] = ka < A ? cs * pa[ka] : 0.f;
+    }
+    const float ca = cs * (pa[a] - 1.f);
+    float wl = 0.f, sl = 0.f;
+    for (int i = threadIdx.x; i < N; i += 256) {
+        float li, ai, g;
+        qr_terms(T, N, th[i], tau_hat[i], li, ai, g);
+        drow[a * N + i] = -g * scale + ca;
+        wl += li;
+        sl += ai;
+    }
+    wl = block_sum_256(wl, red);
+    sl = block_sum_256(sl, red);
+    if (threadIdx.x == 0) {
+        const float huber = wl / (float)N;
+        prio[b] = sl / (float)N;
+        lw[b] = huber * wb;
+        cw[b] = cql;
     }
 }
 
@@ -259,6 +329,30 @@ __global__ __launch_bounds__(1024) void mean_kernel(const float* __restrict__ v,
         __syncthreads();
     }
     if (threadIdx.x == 0) *out = red[0] / (float)B;
+}
+
+// out3 = [qr_loss + cql_w cql_loss, qr_loss = mean_b lw[b], cql_loss = mean_b cw[b]]: both means in mean_kernel's order
+__global__ __launch_bounds__(1024) void cql_mean_kernel(const float* __restrict__ lw, const float* __restrict__ cw, int64_t B,
+                                                        float cql_w, float* __restrict__ out3) {
+    __shared__ float red[2][1024];
+    float s = 0.f, c = 0.f;
+    for (int64_t b = threadIdx.x; b < B; b += 1024) { s += lw[b]; c += cw[b]; }
+    red[0][threadIdx.x] = s;
+    red[1][threadIdx.x] = c;
+    __syncthreads();
+    for (int st = 512; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + st];
+            red[1][threadIdx.x] += red[1][threadIdx.x + st];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float qr = red[0][0] / (float)B, cq = red[1][0] / (float)B;
+        out3[0] = qr + cq * cql_w;
+        out3[1] = qr;
+        out3[2] = cq;
+    }
 }
 
 int net_forward(hipStream_t s, ts_workspace* ws, const Net& n, const float* params, const void* obs, bool obs_u8,
@@ -753,6 +847,63 @@ int ts_distq_update(ts_workspace* ws, float* params, float* adam_m, float* adam_
 
     // head, fc1, conv3, conv2, conv1: input gradients down the caller's stream, the weight gradients beside them on the
     // workspace's side streams (ts::chain_backward, as ts_dqn_update)
+    {
+        const float* x[5]; const float* wb[5]; float* g[5];
+        for (int i = 0; i < 5; ++i) {
+            x[i] = i == 0 ? static_cast<const float*>(obs_nhwc) : a.h[i - 1];
+            wb[i] = params + n.off[i];
+            g[i] = grad + n.off[i];
+        }
+        if (int rc = ts::chain_backward(s, ws, 5, n.l, x, dy, wb, slabs, g, obs_u8 != 0)) return rc;
+    }
+    if (hp->lr < 0.0) return TS_OK;
+    return ts::adam_step(s, params, adam_m, adam_v, grad, n.off[5], adam_step, hp->lr, hp->beta1, hp->beta2,
+                         hp->adam_eps, hp->max_grad_norm, norm_part);
+}
+
+// DiscreteCQL._update_with_batch (imitation/discrete_cql.py:80-113): ts_distq_update's QRDQN flow with cql_loss_kernel and the
+// three-scalar reduction in place of qr_loss_kernel and mean_kernel
+int ts_dcql_update(ts_workspace* ws, float* params, float* adam_m, float* adam_v, int64_t adam_step, int64_t c, int64_t h,
+                   int64_t w, int64_t n_act, int64_t n_atoms, const float* tau_hat, const void* obs_nhwc, int obs_u8,
+                   const int64_t* act, const float* returns, const float* weight, int64_t B, const ts_distq_hparams* hp,
+                   double min_q_weight, float* prio_out, float* loss3_out, float* grad_out, ts_stream_t stream) {
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_dcql_update: workspace is NULL");
+    TS_REQUIRE(B >= 1 && adam_step >= 1, TS_ERR_INVALID_ARG, "ts_dcql_update: bad batch size / step");
+    TS_REQUIRE(params && adam_m && adam_v && tau_hat && obs_nhwc && act && returns && hp && prio_out && loss3_out,
+               TS_ERR_INVALID_ARG, "ts_dcql_update: NULL argument");
+    TS_REQUIRE(min_q_weight >= 0.0 && min_q_weight <= 3.0e38, TS_ERR_INVALID_ARG,
+               "ts_dcql_update: min_q_weight must be finite and >= 0");
+    Net n;
+    if (int rc = make_net((int)B, (int)c, (int)h, (int)w, (int)n_act, (int)n_atoms, &n)) return rc;
+    hipStream_t s = ts::as_stream(stream);
+
+    // workspace: as ts_distq_update, with two per-sample vectors (lw, cw)
+    size_t slab[5], slab_all = 0;
+    for (int i = 0; i < 5; ++i) {
+        slab[i] = al(4 * (size_t)ts::conv_wgrad_splits(n.l[i]) * n.l[i].param_elems());
+        slab_all += slab[i];
+    }
+    size_t bytes = acts_bytes(n) + slab_all + al(4 * (size_t)n.off[5]) + 2 * al(4 * (size_t)B) + 4096;
+    for (int i = 0; i < 5; ++i) bytes += al(4 * (size_t)n.l[i].out_elems());
+    if (int rc = ts::ws_reserve(ws, bytes)) return rc;
+    Acts a;
+    char* p = carve_acts(n, static_cast<char*>(ws->base), &a);
+    float* dy[5];
+    for (int i = 0; i < 5; ++i) { dy[i] = reinterpret_cast<float*>(p); p += al(4 * (size_t)n.l[i].out_elems()); }
+    float* slabs[5];
+    for (int i = 0; i < 5; ++i) { slabs[i] = reinterpret_cast<float*>(p); p += slab[i]; }
+    float* grad = reinterpret_cast<float*>(p); p += al(4 * (size_t)n.off[5]);
+    float* lw = reinterpret_cast<float*>(p); p += al(4 * (size_t)B);
+    float* cw = reinterpret_cast<float*>(p); p += al(4 * (size_t)B);
+    float* norm_part = reinterpret_cast<float*>(p);
+    if (grad_out) grad = grad_out;
+
+    if (int rc = net_forward(s, ws, n, params, obs_nhwc, obs_u8 != 0, a)) return rc;
+    hipLaunchKernelGGL(cql_loss_kernel, dim3((unsigned)B), dim3(256), 0, s, a.h[4], act, returns, weight, tau_hat, B, n.n_act,
+                       n.n_atoms, n.ld, (float)min_q_weight, dy[4], prio_out, lw, cw);
+    hipLaunchKernelGGL(cql_mean_kernel, dim3(1), dim3(1024), 0, s, lw, cw, B, (float)min_q_weight, loss3_out);
+    TS_LAUNCH_CHECK();
+    if (int rc = ts::record_td(ws, s)) return rc;        // prio_out / loss3_out are written: ts_dqn_wait_td
     {
         const float* x[5]; const float* wb[5]; float* g[5];
         for (int i = 0; i < 5; ++i) {

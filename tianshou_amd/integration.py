@@ -1413,7 +1413,9 @@ def make_hip_drqn(ref=None):
 # ---------------------------------------------------------------------------------------------------
 # QRDQN (qrdqn.py) / C51 (c51.py) on QRDQNet / C51Net
 # ---------------------------------------------------------------------------------------------------
-def _make_hip_distq(kind: str, ref=None):
+def _make_hip_distq(kind: str, ref=None, cql: bool = False):
+    """`cql`: DiscreteCQL (imitation/discrete_cql.py), QRDQN with the conservative term -- the same hooks over
+    tianshou_amd.dcql.DiscreteCQLEngine, with `min_q_weight` and the three-number statistics."""
     from . import distq as Q
     from . import dqn as D
 
@@ -1424,6 +1426,12 @@ def _make_hip_distq(kind: str, ref=None):
     else:
         Base = _ref(ref, "tianshou.algorithm.modelfree.c51", "C51")
     who = "HipQRDQN" if kind == Q.QR else "HipC51"
+    if cql:
+        from . import dcql as CQ
+
+        Base = _ref(ref, "tianshou.algorithm.imitation.discrete_cql", "DiscreteCQL")
+        DiscreteCQLTrainingStats = _ref(ref, "tianshou.algorithm.imitation.discrete_cql", "DiscreteCQLTrainingStats")
+        who = "HipDiscreteCQL"
 
     class HipDistQ(_HipGlue, Base):
         def __init__(self, *args, device="cuda", **kwargs):
@@ -1447,14 +1455,18 @@ def _make_hip_distq(kind: str, ref=None):
                     raise NotImplementedError(f"{who}: head width {n_out} is not a multiple of {n_atoms} atoms")
                 n_act = n_out // n_atoms
                 opt, g = _adam_of(self.optim)
-                cfg = Q.DistQConfig(kind=kind, n_atoms=n_atoms, gamma=self.gamma, n_step=self.n_step,
-                                    target_update_freq=self.target_update_freq, lr=g["lr"], betas=tuple(g["betas"]),
-                                    adam_eps=g["eps"], max_grad_norm=self.optim._max_grad_norm,
-                                    v_min=float(getattr(self.policy, "v_min", -10.0)),
-                                    v_max=float(getattr(self.policy, "v_max", 10.0)))
+                fields = dict(kind=kind, n_atoms=n_atoms, gamma=self.gamma, n_step=self.n_step,
+                              target_update_freq=self.target_update_freq, lr=g["lr"], betas=tuple(g["betas"]),
+                              adam_eps=g["eps"], max_grad_norm=self.optim._max_grad_norm,
+                              v_min=float(getattr(self.policy, "v_min", -10.0)),
+                              v_max=float(getattr(self.policy, "v_max", 10.0)))
                 dev = self._hip_device
                 flat = Q.flat_from_torch([sd[k] for k in D.TIANSHOU_KEYS], c, h, w, n_act, n_atoms, dev)
-                eng = self._hip_engine = Q.DistQEngine(c, h, w, n_act, flat, cfg)
+                if cql:
+                    cfg = CQ.DiscreteCQLConfig(min_q_weight=float(self.min_q_weight), **fields)
+                    eng = self._hip_engine = CQ.DiscreteCQLEngine(c, h, w, n_act, flat, cfg)
+                else:
+                    eng = self._hip_engine = Q.DistQEngine(c, h, w, n_act, flat, Q.DistQConfig(**fields))
                 eng.iter = self._iter
                 ms, vs, step = adam_state(opt, list(self.policy.model.parameters()))       # resume from a checkpoint
                 eng.adam_m = Q.flat_from_torch(ms, c, h, w, n_act, n_atoms, dev)
@@ -1502,6 +1514,8 @@ def _make_hip_distq(kind: str, ref=None):
                 else:
                     obs_next = D.gather_obs_nhwc(m.obs, m, m.next(idx), stack, as_u8=True)
             act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device)
+            if cql:
+                eng.cfg.min_q_weight = float(self.min_q_weight)                   # read at every update, as the learning rate
             loss, prio = eng.update_with_batch(obs, act, batch.returns, weight, obs_next_nhwc=obs_next)
             self._iter = eng.iter
             batch.weight = prio                                                   # prio-buffer, qrdqn.py:128 / c51.py:157
@@ -1514,6 +1528,9 @@ def _make_hip_distq(kind: str, ref=None):
                         p.copy_(t)
             store_adam_state(self.optim._optim, list(self.policy.model.parameters()), Q.flat_to_torch(eng.adam_m, *dims),
                              Q.flat_to_torch(eng.adam_v, *dims), eng.adam_step)
+            if cql:
+                total, qr_loss, cql_loss = loss.tolist()                          # one transfer for the three numbers
+                return DiscreteCQLTrainingStats(loss=total, qr_loss=qr_loss, cql_loss=cql_loss)       # discrete_cql.py:109-113
             if kind == Q.QR:
                 return SimpleLossTrainingStats(loss=float(loss.item()))
             return LossSequenceTrainingStats(loss=float(loss.item()))            # as c51.py:160
@@ -1534,6 +1551,16 @@ def make_hip_c51(ref=None):
     Supported model: C51Net (atari_network.py:125-151) with C51Policy's support, Adam; buffer layouts as HipDQN.
     `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
     return _make_hip_distq("c51", ref)
+
+
+def make_hip_discrete_cql(ref=None):
+    """Returns HipDiscreteCQL(DiscreteCQL): `_preprocess_batch` / `_update_with_batch` (dqn.py:257-275 with qrdqn.py:93-104,
+    imitation/discrete_cql.py:80-113) on the engine (tianshou_amd/dcql.py).  Supported model: QRDQNet, Adam; buffer layouts as
+    HipDQN -- the offline case is a plain ReplayBuffer / VectorReplayBuffer without `weight`, a prioritized buffer works as well.
+    `min_q_weight` is read from the algorithm at every update; the statistics are DiscreteCQLTrainingStats(loss, qr_loss,
+    cql_loss).  `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    return _make_hip_distq("qr", ref, cql=True)
+
 
 def make_hip_iqn(ref=None):
     """Returns HipIQN(IQN): `_preprocess_batch` / `_update_with_batch` (dqn.py:257-275 with qrdqn.py:94-106, iqn.py:156-183) on
