@@ -114,3 +114,61 @@ def test_ts_dcql_update_validates_before_any_hip_call():
             assert b"min_q_weight" in lib.ts_last_error()
     finally:
         lib.ts_workspace_destroy(ws)
+
+
+@pytest.mark.skipif(not REAL, reason="reference not mounted")
+def test_hip_discrete_cql_wrapper_runs_with_engine_double(monkeypatch):
+    """One update() of HipDiscreteCQL over a CPU double of DiscreteCQLEngine (the pattern of tests/test_integration_shim.py):
+    the config with `min_q_weight`, the three statistics, and the write-back of parameters, lagged network and
+    Adam state."""
+    import numpy as np
+    from tianshou.algorithm.imitation.discrete_cql import DiscreteCQLTrainingStats
+    from tianshou.data import VectorReplayBuffer
+    from tianshou.env.atari.atari_network import QRDQNet
+    from tianshou.utils.torch_utils import policy_within_training_step
+    import tianshou_amd.dcql as CQ
+    import tianshou_amd.dqn as D
+    from tests.test_integration_shim import _fill, _patch_for_cpu
+
+    seen = {}
+
+    class FakeCQL:
+        def __init__(self, c, h, w, n_act, flat, cfg):
+            assert (c, h, w, n_act) == (4, 84, 84, 6) and (cfg.kind, cfg.n_atoms, cfg.min_q_weight) == ("qr", N_, 2.5)
+            assert (cfg.target_update_freq, cfg.lr) == (2, 1e-4)
+            assert flat.numel() == 8224 + 32832 + 36928 + 3137 * 512 + 513 * ((6 * N_ + 31) // 32 * 32)
+            self.c, self.h, self.w, self.n_act, self.cfg = c, h, w, n_act, cfg
+            self.params, self.params_old = flat.clone(), flat.clone()
+            self.adam_m, self.adam_v, self.adam_step, self.iter = torch.zeros_like(flat), torch.zeros_like(flat), 0, 0
+
+        def preprocess(self, m, frames, idx, stack, obs_next_frames=None):
+            assert frames.dtype == torch.uint8 and stack == 1 and obs_next_frames is not None
+            return torch.zeros((idx.numel(), N_))
+
+        def update_with_batch(self, obs, act, ret, weight=None, obs_next_nhwc=None):
+            assert obs.shape == (8, 84, 84, 4) and ret.shape == (8, N_) and obs_next_nhwc is None
+            seen["min_q_weight"] = self.cfg.min_q_weight
+            self.adam_step += 1
+            self.iter += 1
+            self.params += 2.0
+            self.params_old += 0.5
+            self.adam_m += 0.125
+            return torch.tensor([1.75, 0.5, 0.25]), torch.arange(8, dtype=torch.float32)
+
+    algo = _make(QRDQNet(c=4, h=84, w=84, action_shape=[6], num_quantiles=N_), min_q_weight=2.5, target_update_freq=2)
+    _patch_for_cpu(monkeypatch)
+    monkeypatch.setattr(CQ, "DiscreteCQLEngine", FakeCQL)
+    monkeypatch.setattr(D, "gather_obs_nhwc", lambda frames, m, idx, stack, as_u8=False: frames[idx].permute(0, 2, 3, 1))
+    buf = VectorReplayBuffer(32, 2)
+    _fill(buf, 12, (4, 84, 84), np.zeros(2, np.int64), np.uint8)
+    first = next(iter(algo.policy.model.parameters()))
+    old_first = next(iter(algo.model_old.parameters()))
+    before = first.detach().clone()
+    with policy_within_training_step(algo.policy):
+        stats = algo.update(buffer=buf, sample_size=8)
+    assert isinstance(stats, DiscreteCQLTrainingStats) and (stats.loss, stats.qr_loss, stats.cql_loss) == (1.75, 0.5, 0.25)
+    assert seen["min_q_weight"] == 2.5
+    assert torch.allclose(first.detach(), before + 2.0)                        # engine -> nn.Parameter
+    st = algo.optim._optim.state[first]
+    assert float(st["step"]) == 1.0 and torch.allclose(st["exp_avg"], torch.full_like(st["exp_avg"], 0.125))
+    assert old_first is not first and torch.allclose(old_first.detach(), before + 0.5)      # lagged network: its own values

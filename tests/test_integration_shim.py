@@ -1722,6 +1722,120 @@ def test_drqn_layout_converters_round_trip_on_cpu():
         assert torch.equal(w_ih[:hidden].t(), t[0]) and torch.equal(w_ih[hidden], t[2])
 
 
+# ------------------------------------------------------------------------------------ the Q-learning classes' one state path
+class _QDouble:
+    """What the five Q-learning class bodies (HipDQN, HipDRQN, HipQRDQN / HipC51 / HipDiscreteCQL, HipIQN, HipRainbow) use of
+    their engines, on the CPU: every update adds 2 to the parameters, 0.5 to the lagged network's and 0.125 / 0.25 to the two
+    Adam moments.  `built` (one list per test, see `_q_body`) collects the engines in the order they were constructed."""
+
+    def __init__(self, *args):                               # four dims, flat[, noise], cfg
+        self.c, self.h, self.w, self.n_act, flat = args[:5]
+        self.cfg = args[-1]
+        self.params, self.params_old = flat.clone(), flat.clone()
+        self.adam_m, self.adam_v = torch.zeros_like(flat), torch.zeros_like(flat)
+        self.adam_step = self.iter = self.tau_counter = 0
+        self.built.append(self)
+
+    def preprocess(self, *a, **k):
+        return torch.zeros(8, 1)
+
+    def preprocess_with_obs(self, *a, **k):
+        return torch.zeros(8, 1), torch.zeros(8)
+
+    def set_noise(self, *a):
+        pass
+
+    def update_with_batch(self, *a, **k):
+        self.adam_step += 1
+        self.iter += 1
+        self.params += 2.0
+        self.params_old += 0.5
+        self.adam_m += 0.125
+        self.adam_v += 0.25
+        return torch.tensor([0.5]), torch.arange(8, dtype=torch.float32)
+
+
+_Q_BODIES = ["dqn", "drqn", "distq", "iqn", "rainbow"]
+
+
+def _q_body(which, monkeypatch):
+    """-> (the algorithm of one class body with a `_QDouble` in place of its engine, a buffer to sample 8 of, the doubles built so
+    far, flat vector -> tensors in torch layout by the engine module's own converter)."""
+    from tianshou.data import VectorReplayBuffer
+    import tianshou_amd.distq as Q
+    import tianshou_amd.dqn as D
+    import tianshou_amd.drqn as R
+    import tianshou_amd.iqn as I
+    import tianshou_amd.rainbow as RB
+
+    if which == "iqn":
+        from tests import test_iqn_shim as TI
+
+        iqn = TI._classes()[1](TI._iqn_net([512], c=4, h=84, w=84, n_act=6), 6)
+    algo, mod, engine, dims = {"dqn": lambda: (_make_dqn_algo(), D, "DQNEngine", (4, 84, 84, 6)),
+                               "drqn": lambda: (_drqn_algo(), R, "RecurrentDQNEngine", (4, 64, 2, 2)),
+                               "distq": lambda: (_distq_algo("qr"), Q, "DistQEngine", (4, 84, 84, 6, 20)),
+                               "iqn": lambda: (iqn, I, "IQNEngine", (4, 84, 84, 6, 64)),
+                               "rainbow": lambda: (_rainbow_algo(), RB, "RainbowEngine", (4, 84, 84, 6, 11))}[which]()
+    double = type("Double", (_QDouble,), {"built": []})
+    _patch_for_cpu(monkeypatch)
+    monkeypatch.setattr(mod, engine, double)
+    monkeypatch.setattr(D, "gather_obs_nhwc", lambda frames, m, idx, stack, as_u8=False: frames[idx].permute(0, 2, 3, 1))
+    if which == "drqn":
+        buf = VectorReplayBuffer(32, 2, stack_num=4, ignore_obs_next=True)
+        _fill(buf, 12, (4,), np.zeros(2, np.int64))
+    else:
+        buf = VectorReplayBuffer(32, 2)
+        _fill(buf, 12, (4, 84, 84), np.zeros(2, np.int64), np.uint8)
+    return algo, buf, double.built, lambda flat: mod.flat_to_torch(flat, *dims)
+
+
+@pytest.mark.parametrize("which", _Q_BODIES)
+def test_q_engine_rebuilt_from_torch_receives_what_the_last_one_wrote_back(which, monkeypatch):
+    """Load and write-back are inverses: after one update, the engine is dropped and built again from the torch modules and
+    torch.optim; it starts from the Adam moments, step count, update count and lagged parameters the first one ended with.
+    (Compared in torch layout: the padding of a flat vector is not state.)"""
+    from tianshou.utils.torch_utils import policy_within_training_step
+
+    algo, buf, built, to_torch = _q_body(which, monkeypatch)
+    with policy_within_training_step(algo.policy):
+        algo.update(buffer=buf, sample_size=8)
+    algo.hip_sync()                                        # (HipDQN writes back when somebody reads; the others already have)
+    first = built[0]
+    algo._hip_invalidate()
+    second = algo._engine() if which == "drqn" else algo._engine(4, 84, 84)
+    assert built == [first, second] and second is not first
+    assert second.adam_step == first.adam_step == 1 and second.iter == first.iter == 1
+    for name, inc in (("params", 2.0), ("params_old", 0.5), ("adam_m", 0.125), ("adam_v", 0.25)):
+        a, b = to_torch(getattr(first, name)), to_torch(getattr(second, name))
+        assert len(a) == len(b) > 0 and all(torch.equal(x, y.to(x.dtype)) for x, y in zip(a, b)), name
+        if name.startswith("adam"):
+            assert all(bool((y == inc).all()) for y in b), name           # ... and it is what the update left, not zeros
+    old, new = to_torch(second.params_old), to_torch(second.params)
+    assert all(torch.allclose(o + 1.5, n) for o, n in zip(old, new))      # the lagged network kept its own values
+
+
+@pytest.mark.parametrize("which", [w for w in _Q_BODIES if w != "dqn"])
+def test_q_write_back_leaves_a_foreign_write_alone(which, monkeypatch):
+    """`_hip_write_back` of every Q-learning class goes through `_hip_put`: a parameter somebody else has written since the
+    engine snapshotted it (`_hip_skip_ids`, set by the `_hip_engine` property) keeps its value, all others are written."""
+    from tianshou.utils.torch_utils import policy_within_training_step
+
+    algo, buf, built, _ = _q_body(which, monkeypatch)
+    with policy_within_training_step(algo.policy):
+        algo.update(buffer=buf, sample_size=8)
+    params = [p for p in algo.policy.model.parameters() if p.requires_grad]      # (RainbowNet's noise is not learnt)
+    before = [p.detach().clone() for p in params]
+    built[0].params += 1.0
+    algo.__dict__["_hip_skip_ids"] = {id(params[1])}
+    try:
+        algo._hip_write_back()
+    finally:
+        algo.__dict__["_hip_skip_ids"] = None
+    assert torch.equal(params[1].detach(), before[1])
+    assert all(torch.allclose(p.detach(), b + 1.0) for i, (p, b) in enumerate(zip(params, before)) if i != 1)
+
+
 def test_device_permutation_key_follows_numpy_seed_and_travels_in_the_checkpoint():
     """permutations="device" (HipPPO's default): the shuffle key is one draw from NumPy's global generator at construction
     -- `np.random.seed` selects it like it selects Batch.split's permutations in the reference -- and (seed, update counter)

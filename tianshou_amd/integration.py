@@ -7,7 +7,8 @@ Overrides exactly the two hooks `Algorithm._update` calls (algorithm_base.py:622
     _update_with_batch(batch, batch_size, repeat) -> A2CTrainingStats   (ppo.py:164-224)
 keeping the Policy / Algorithm API, the Batch fields (`v_s`, `returns`, `adv`, `logp_old`, `act`),
 the stats dataclasses and `state_dict()` (parameters and Adam moments are copied back into the
-torch modules / optimizer after every update()).  Supported net: the MuJoCo actor-critic of
+torch modules / optimizer after every update(), or, under `write_back="lazy"`, when somebody reads them; for the
+Q-learning classes, HipDQN to HipRainbow, that copy is `_q_write_back`).  Supported net: the MuJoCo actor-critic of
 examples/mujoco/mujoco_ppo.py (Net[64,64] tanh, ContinuousActorProbabilistic(unbounded=True) with a
 state-independent sigma, ContinuousCritic); anything else raises at construction.
 """
@@ -15,6 +16,7 @@ from __future__ import annotations
 
 import os
 import weakref
+from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
@@ -1162,10 +1164,121 @@ def _mirror(algorithm, buffer, device):
     return m
 
 
+# -- what the Q-learning classes (HipDQN, HipDRQN, HipQRDQN / HipC51 / HipDiscreteCQL, HipIQN, HipRainbow) share: one path for
+# the torch state into a fresh engine (`_q_load`) and one back (`_q_write_back`), both reading the same `_QState` --------------
+class _QState(NamedTuple):
+    """How a Q network's torch state maps to its engine's flat vectors.  Every class builds its own in `_hip_qstate()`, per
+    call: the converters are looked up in their engine module when they are used, not when the class is made."""
+    keys: list            # names of the parameters, in the order the converters take and return them
+    from_torch: Callable  # the engine module's flat_from_torch(tensors, *dims, device)
+    to_torch: Callable    # the engine module's flat_to_torch(flat, *dims)
+    dims: Callable        # engine -> the dims tuple of the two converters
+
+
+def _q_layout(buffer, who: str):
+    """-> (c, h, w, stack_num) of a frame buffer: whole [c, h, w] observations, or single frames stacked c times."""
+    obs = np.asarray(buffer.obs)
+    stack = int(getattr(buffer, "stack_num", 1))
+    if stack > 1:
+        if obs.ndim != 3:
+            raise NotImplementedError(f"{who}: frame stacking needs single [h, w] frames per slot")
+        return stack, obs.shape[1], obs.shape[2], stack
+    if obs.ndim != 4:
+        raise NotImplementedError(f"{who}: observations must be [c, h, w]")
+    return obs.shape[1], obs.shape[2], obs.shape[3], 1
+
+
+def _q_begin(algo, who: str, batch, buffer, indices):
+    """Every `_preprocess_batch`, once the buffer's layout is accepted: -> (device mirror of `buffer`, `indices` as a device tensor, kept in `_hip_idx` for
+    `_update_with_batch`); a prioritized buffer's importance weights move to the device."""
+    _require_gpu(algo._hip_device, who)
+    m = _mirror(algo, buffer, algo._hip_device)
+    idx = algo._hip_idx = torch.as_tensor(np.asarray(indices, np.int64), device=algo._hip_device)
+    if hasattr(batch, "weight"):
+        batch.weight = torch.as_tensor(np.asarray(batch.weight), dtype=torch.float32, device=algo._hip_device)
+    return m, idx
+
+
+def _q_config_fields(algo) -> dict:
+    """The target / optimizer fields every Q engine's config has."""
+    _, g = _adam_of(algo.optim)
+    return dict(gamma=algo.gamma, n_step=algo.n_step, target_update_freq=algo.target_update_freq, lr=g["lr"],
+                betas=tuple(g["betas"]), adam_eps=g["eps"], max_grad_norm=algo.optim._max_grad_norm)
+
+
+def _q_flat(algo, dims: tuple) -> torch.Tensor:
+    """The online network's parameters as the flat vector an engine is constructed from."""
+    st = algo._hip_qstate()
+    return st.from_torch([p.detach() for p in params_by_keys(algo.policy.model, st.keys)], *dims, algo._hip_device)
+
+
+def _q_old_params(algo, st: _QState):
+    """The lagged network's parameters; `model_old` is the bare module or its EvalModeModuleWrapper."""
+    return params_by_keys(getattr(algo.model_old, "module", algo.model_old), st.keys)
+
+
+def _q_load(algo, eng):
+    """Torch state -> a fresh engine (built from `_q_flat`): update counter, Adam moments (resume from a checkpoint), lagged
+    network.  The inverse of `_q_write_back`.  -> eng"""
+    st, dev = algo._hip_qstate(), algo._hip_device
+    dims = st.dims(eng)
+    eng.iter = algo._iter
+    ms, vs, eng.adam_step = adam_state(algo.optim._optim, params_by_keys(algo.policy.model, st.keys))
+    eng.adam_m, eng.adam_v = st.from_torch(ms, *dims, dev), st.from_torch(vs, *dims, dev)
+    if eng.params_old is not None:
+        eng.params_old = st.from_torch([p.detach() for p in _q_old_params(algo, st)], *dims, dev)
+    return eng
+
+
+def _q_write_back(algo) -> None:
+    """`_hip_write_back` of the Q-learning classes: engine parameters, lagged parameters and Adam state -> the torch modules
+    and torch.optim, every parameter through `_hip_put` (which leaves out what somebody else has written)."""
+    eng = algo.__dict__.get("_hip_engine_obj")
+    if eng is None:
+        return
+    st = algo._hip_qstate()
+    dims = st.dims(eng)
+    params = params_by_keys(algo.policy.model, st.keys)
+    with torch.no_grad():
+        for p, t in zip(params, st.to_torch(eng.params, *dims)):
+            algo._hip_put(p, t)
+        if eng.params_old is not None:
+            for p, t in zip(_q_old_params(algo, st), st.to_torch(eng.params_old, *dims)):
+                algo._hip_put(p, t)
+    store_adam_state(algo.optim._optim, params, st.to_torch(eng.adam_m, *dims), st.to_torch(eng.adam_v, *dims), eng.adam_step)
+
+
+def _dqn_config(algo):
+    from . import dqn as D
+
+    return D.DQNConfig(is_double=algo.is_double, huber_delta=algo.huber_loss_delta, **_q_config_fields(algo))
+
+
+def _dqn_update(algo, batch, Stats):
+    """`_update_with_batch` of HipDRQN, and of HipDQN where the two hooks are two library calls: `_preprocess_batch` left the
+    batch's observations in `_hip_obs` and the returns on the batch."""
+    eng, m = algo._hip_engine, algo._hip_mirror
+    weight = batch.pop("weight", None)
+    # (index-only sampling: the batch carries no host copy of the actions; the mirror's rows are the same values)
+    act = torch.as_tensor(np.asarray(batch.act), device=algo._hip_device) if hasattr(batch, "act") else m.act[algo._hip_idx]
+    runner = eng
+    if algo._hip_dp_on:
+        from .distributed import DataParallelDQN
+
+        runner = algo._hip_dp(DataParallelDQN, eng)
+    loss, td = runner.update_with_batch(algo._hip_obs, act, batch.returns.reshape(-1), weight)
+    algo._iter = eng.iter
+    batch.weight = td                                                         # prio-buffer, dqn.py:401
+    algo._hip_after_update()                                                  # write-back now ("eager") or when read ("lazy")
+    return Stats(loss=float(loss.item()))
+
+
 def make_hip_dqn(ref=None):
     """Returns HipDQN(DQN): `_preprocess_batch` / `_update_with_batch` (dqn.py:257-275, 381-404) on the engine.
     Supported model: DQNet(c, h, w, n_act) (atari_network.py:60-122), Adam; buffer either stores whole [c, h, w]
     observations or single frames with stack_num = c (save_only_last_obs); obs_next optional.
+    What the engine learnt reaches the torch modules and torch.optim in `_q_write_back`, which is `_hip_write_back` of this
+    class and of the other Q-learning classes below; `_HipGlue._hip_after_update` decides when.
     `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
     DQN = _ref(ref, "tianshou.algorithm.modelfree.dqn", "DQN")
     SimpleLossTrainingStats = _ref(ref, "tianshou.algorithm.modelfree.reinforce", "SimpleLossTrainingStats")
@@ -1211,46 +1324,20 @@ def make_hip_dqn(ref=None):
                 return super().update(buffer, sample_size)
             return self._hip_offpolicy_update(buffer, sample_size, Batch)
 
+        def _hip_qstate(self):
+            return _QState(D.TIANSHOU_KEYS, D.flat_from_torch, D.flat_to_torch, lambda eng: (eng.c, eng.h, eng.w, eng.n_act))
+
         def _engine(self, c, h, w):
             if self._hip_engine is None:
-                sd = self.policy.model.state_dict()
-                n_act = sd[D.TIANSHOU_KEYS[-1]].numel()
-                opt, g = _adam_of(self.optim)
-                cfg = D.DQNConfig(gamma=self.gamma, n_step=self.n_step, target_update_freq=self.target_update_freq,
-                                  is_double=self.is_double, huber_delta=self.huber_loss_delta, lr=g["lr"],
-                                  betas=tuple(g["betas"]), adam_eps=g["eps"], max_grad_norm=self.optim._max_grad_norm)
-                flat = D.flat_from_torch([sd[k] for k in D.TIANSHOU_KEYS], c, h, w, n_act, self._hip_device)
-                eng = self._hip_engine = D.DQNEngine(c, h, w, n_act, flat, cfg)
-                eng.iter = self._iter
-                ms, vs, step = adam_state(opt, list(self.policy.model.parameters()))       # resume from a checkpoint
-                eng.adam_m = D.flat_from_torch(ms, c, h, w, n_act, self._hip_device)
-                eng.adam_v = D.flat_from_torch(vs, c, h, w, n_act, self._hip_device)
-                eng.adam_step = step
-                if eng.params_old is not None:
-                    old = [p.detach() for p in self.model_old.parameters()]
-                    eng.params_old = D.flat_from_torch(old, c, h, w, n_act, self._hip_device)
+                n_act = self.policy.model.state_dict()[D.TIANSHOU_KEYS[-1]].numel()
+                eng = D.DQNEngine(c, h, w, n_act, _q_flat(self, (c, h, w, n_act)), _dqn_config(self))
+                self._hip_engine = _q_load(self, eng)
             return self._hip_engine
 
-        def _layout(self, buffer):
-            obs = np.asarray(buffer.obs)
-            stack = int(getattr(buffer, "stack_num", 1))
-            if stack > 1:
-                if obs.ndim != 3:
-                    raise NotImplementedError("HipDQN: frame stacking needs single [h, w] frames per slot")
-                return stack, obs.shape[1], obs.shape[2], stack
-            if obs.ndim != 4:
-                raise NotImplementedError("HipDQN: observations must be [c, h, w]")
-            return obs.shape[1], obs.shape[2], obs.shape[3], 1
-
         def _preprocess_batch(self, batch, buffer, indices):
-            _require_gpu(self._hip_device, "HipDQN")
-            c, h, w, stack = self._layout(buffer)
+            c, h, w, stack = self._layout(buffer, "HipDQN")
+            m, idx = _q_begin(self, "HipDQN", batch, buffer, indices)
             eng = self._engine(c, h, w)
-            m = _mirror(self, buffer, self._hip_device)
-            idx = torch.as_tensor(np.asarray(indices, np.int64), device=self._hip_device)
-            self._hip_idx, self._hip_stack = idx, stack
-            if hasattr(batch, "weight"):
-                batch.weight = torch.as_tensor(np.asarray(batch.weight), dtype=torch.float32, device=self._hip_device)
             # Inside HipDQN.update()'s own sequence (`_hip_offpolicy_update`: nobody reads the batch between the two hooks) on the
             # Atari layout (single uint8 frames, stack 4, no stored obs_next) the two hooks are ONE library call, made by
             # `_update_with_batch` (ts_dqn_learn_rows; `batch.returns` is attached there).  Called on its own (the reference's
@@ -1271,42 +1358,18 @@ def make_hip_dqn(ref=None):
 
         def _update_with_batch(self, batch):
             self._hip_refresh_lr()
+            if not self.__dict__.pop("_hip_deferred", False):
+                return _dqn_update(self, batch, SimpleLossTrainingStats)
             eng, m = self._hip_engine, self._hip_mirror
-            weight = batch.pop("weight", None)
-            if self.__dict__.pop("_hip_deferred", False):
-                loss, td, ret = eng.learn_rows(m, m.obs, m.act, self._hip_idx, weight)
-                batch.returns = ret.reshape(-1, 1)
-                self._iter = eng.iter
-                batch.weight = td                                                 # prio-buffer, dqn.py:401
-                self._hip_after_update()
-                return SimpleLossTrainingStats(loss=float(loss.item()))
-            obs = self._hip_obs
-            # (index-only sampling: the batch carries no host copy of the actions; the mirror's rows are the same values)
-            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device) if hasattr(batch, "act") else m.act[self._hip_idx]
-            runner = eng
-            if self._hip_dp_on:
-                from .distributed import DataParallelDQN
-
-                runner = self._hip_dp(DataParallelDQN, eng)
-            loss, td = runner.update_with_batch(obs, act, batch.returns.reshape(-1), weight)
+            loss, td, ret = eng.learn_rows(m, m.obs, m.act, self._hip_idx, batch.pop("weight", None))
+            batch.returns = ret.reshape(-1, 1)
             self._iter = eng.iter
-            batch.weight = td                                                     # prio-buffer, dqn.py:401
-            self._hip_after_update()                                              # write-back now ("eager") or when read ("lazy")
+            batch.weight = td                                                 # prio-buffer, dqn.py:401
+            self._hip_after_update()
             return SimpleLossTrainingStats(loss=float(loss.item()))
 
-        def _hip_write_back(self) -> None:
-            eng = self.__dict__.get("_hip_engine_obj")
-            if eng is None:
-                return
-            dims = (eng.c, eng.h, eng.w, eng.n_act)
-            with torch.no_grad():
-                for p, t in zip(self.policy.model.parameters(), D.flat_to_torch(eng.params, *dims)):
-                    self._hip_put(p, t)
-                if eng.params_old is not None:
-                    for p, t in zip(self.model_old.parameters(), D.flat_to_torch(eng.params_old, *dims)):
-                        self._hip_put(p, t)
-            store_adam_state(self.optim._optim, list(self.policy.model.parameters()), D.flat_to_torch(eng.adam_m, *dims),
-                             D.flat_to_torch(eng.adam_v, *dims), eng.adam_step)
+        _layout = staticmethod(_q_layout)
+        _hip_write_back = _q_write_back
 
     return HipDQN
 
@@ -1321,7 +1384,6 @@ def make_hip_drqn(ref=None):
     DQN = _ref(ref, "tianshou.algorithm.modelfree.dqn", "DQN")
     SimpleLossTrainingStats = _ref(ref, "tianshou.algorithm.modelfree.reinforce", "SimpleLossTrainingStats")
 
-    from . import dqn as D
     from . import drqn as R
 
     class HipDRQN(_HipGlue, DQN):
@@ -1341,71 +1403,35 @@ def make_hip_drqn(ref=None):
             self._hip_engine = None
             self._hip_glue_init()
 
+        def _hip_qstate(self):
+            dims = self._hip_dims                 # (obs_dim, hidden, layers, n_act): what the engine was built with
+            return _QState(R.state_dict_keys(dims[2]), R.flat_from_torch, R.flat_to_torch, lambda eng: dims)
+
         def _engine(self):
             if self._hip_engine is None:
-                sd = self.policy.model.state_dict()
-                dims, dev = self._hip_dims, self._hip_device
-                keys = R.state_dict_keys(dims[2])
-                opt, g = _adam_of(self.optim)
-                cfg = D.DQNConfig(gamma=self.gamma, n_step=self.n_step, target_update_freq=self.target_update_freq,
-                                  is_double=self.is_double, huber_delta=self.huber_loss_delta, lr=g["lr"],
-                                  betas=tuple(g["betas"]), adam_eps=g["eps"], max_grad_norm=self.optim._max_grad_norm)
-                eng = self._hip_engine = R.RecurrentDQNEngine(*dims, R.flat_from_torch([sd[k] for k in keys], *dims, dev), cfg)
-                eng.iter = self._iter
-                ms, vs, step = adam_state(opt, params_by_keys(self.policy.model, keys))       # resume from a checkpoint
-                eng.adam_m, eng.adam_v = R.flat_from_torch(ms, *dims, dev), R.flat_from_torch(vs, *dims, dev)
-                eng.adam_step = step
-                if eng.params_old is not None:
-                    old = getattr(self.model_old, "module", self.model_old).state_dict()       # EvalModeModuleWrapper
-                    eng.params_old = R.flat_from_torch([old[k] for k in keys], *dims, dev)
+                dims = self._hip_dims
+                self._hip_engine = _q_load(self, R.RecurrentDQNEngine(*dims, _q_flat(self, dims), _dqn_config(self)))
             return self._hip_engine
 
         def _preprocess_batch(self, batch, buffer, indices):
-            _require_gpu(self._hip_device, "HipDRQN")
             obs = np.asarray(buffer.obs)
             if obs.ndim != 2 or obs.shape[1] != self._hip_dims[0]:
                 raise NotImplementedError("HipDRQN: the buffer must hold vector observations of the model's state_shape")
+            m, idx = _q_begin(self, "HipDRQN", batch, buffer, indices)
             eng = self._engine()
-            m = _mirror(self, buffer, self._hip_device)
-            idx = torch.as_tensor(np.asarray(indices, np.int64), device=self._hip_device)
             stack = int(getattr(buffer, "stack_num", 1))
             nxt = m.obs_next if m.obs_next is not None else None
             # the batch's own stacked observations are gathered here, so that their forward pass (the one _update_with_batch needs)
             # can run on a side stream beside the two obs_next passes of _target_q; data-parallel runs keep the plain order
             self._hip_obs, ret = eng.preprocess_with_obs(m, m.obs, idx, stack, obs_next_rows=nxt, prefetch=not self._hip_dp_on)
             batch.returns = ret.reshape(-1, 1)
-            self._hip_idx, self._hip_stack = idx, stack
-            if hasattr(batch, "weight"):
-                batch.weight = torch.as_tensor(np.asarray(batch.weight), dtype=torch.float32, device=self._hip_device)
             return batch
 
         def _update_with_batch(self, batch):
             self._hip_refresh_lr()
-            eng, m = self._hip_engine, self._hip_mirror
-            weight = batch.pop("weight", None)
-            obs = self._hip_obs
-            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device)
-            runner = eng
-            if self._hip_dp_on:
-                from .distributed import DataParallelDQN
+            return _dqn_update(self, batch, SimpleLossTrainingStats)
 
-                runner = self._hip_dp(DataParallelDQN, eng)
-            loss, td = runner.update_with_batch(obs, act, batch.returns.reshape(-1), weight)
-            self._iter = eng.iter
-            batch.weight = td                                                     # prio-buffer, dqn.py:401
-            dims = self._hip_dims
-            keys = R.state_dict_keys(dims[2])
-            params = params_by_keys(self.policy.model, keys)
-            with torch.no_grad():
-                for p, t in zip(params, R.flat_to_torch(eng.params, *dims)):
-                    p.copy_(t)
-                if eng.params_old is not None:
-                    old_mod = getattr(self.model_old, "module", self.model_old)
-                    for p, t in zip(params_by_keys(old_mod, keys), R.flat_to_torch(eng.params_old, *dims)):
-                        p.copy_(t)
-            store_adam_state(self.optim._optim, params, R.flat_to_torch(eng.adam_m, *dims), R.flat_to_torch(eng.adam_v, *dims),
-                             eng.adam_step)
-            return SimpleLossTrainingStats(loss=float(loss.item()))
+        _hip_write_back = _q_write_back
 
     return HipDRQN
 
@@ -1446,59 +1472,33 @@ def _make_hip_distq(kind: str, ref=None, cql: bool = False):
         def _n_atoms(self) -> int:
             return int(self.num_quantiles if kind == Q.QR else self.policy.num_atoms)
 
+        def _hip_qstate(self):
+            return _QState(D.TIANSHOU_KEYS, Q.flat_from_torch, Q.flat_to_torch,
+                           lambda eng: (eng.c, eng.h, eng.w, eng.n_act, eng.cfg.n_atoms))
+
         def _engine(self, c, h, w):
             if self._hip_engine is None:
-                sd = self.policy.model.state_dict()
                 n_atoms = self._n_atoms()
-                n_out = sd[D.TIANSHOU_KEYS[-1]].numel()
+                n_out = self.policy.model.state_dict()[D.TIANSHOU_KEYS[-1]].numel()
                 if n_out % n_atoms:
                     raise NotImplementedError(f"{who}: head width {n_out} is not a multiple of {n_atoms} atoms")
                 n_act = n_out // n_atoms
-                opt, g = _adam_of(self.optim)
-                fields = dict(kind=kind, n_atoms=n_atoms, gamma=self.gamma, n_step=self.n_step,
-                              target_update_freq=self.target_update_freq, lr=g["lr"], betas=tuple(g["betas"]),
-                              adam_eps=g["eps"], max_grad_norm=self.optim._max_grad_norm,
-                              v_min=float(getattr(self.policy, "v_min", -10.0)),
-                              v_max=float(getattr(self.policy, "v_max", 10.0)))
-                dev = self._hip_device
-                flat = Q.flat_from_torch([sd[k] for k in D.TIANSHOU_KEYS], c, h, w, n_act, n_atoms, dev)
+                fields = dict(kind=kind, n_atoms=n_atoms, v_min=float(getattr(self.policy, "v_min", -10.0)),
+                              v_max=float(getattr(self.policy, "v_max", 10.0)), **_q_config_fields(self))
+                flat = _q_flat(self, (c, h, w, n_act, n_atoms))
                 if cql:
                     cfg = CQ.DiscreteCQLConfig(min_q_weight=float(self.min_q_weight), **fields)
-                    eng = self._hip_engine = CQ.DiscreteCQLEngine(c, h, w, n_act, flat, cfg)
+                    eng = CQ.DiscreteCQLEngine(c, h, w, n_act, flat, cfg)
                 else:
-                    eng = self._hip_engine = Q.DistQEngine(c, h, w, n_act, flat, Q.DistQConfig(**fields))
-                eng.iter = self._iter
-                ms, vs, step = adam_state(opt, list(self.policy.model.parameters()))       # resume from a checkpoint
-                eng.adam_m = Q.flat_from_torch(ms, c, h, w, n_act, n_atoms, dev)
-                eng.adam_v = Q.flat_from_torch(vs, c, h, w, n_act, n_atoms, dev)
-                eng.adam_step = step
-                if eng.params_old is not None:
-                    old = [p.detach() for p in self.model_old.parameters()]
-                    eng.params_old = Q.flat_from_torch(old, c, h, w, n_act, n_atoms, dev)
+                    eng = Q.DistQEngine(c, h, w, n_act, flat, Q.DistQConfig(**fields))
+                self._hip_engine = _q_load(self, eng)
             return self._hip_engine
 
-        @staticmethod
-        def _layout(buffer):
-            obs = np.asarray(buffer.obs)
-            stack = int(getattr(buffer, "stack_num", 1))
-            if stack > 1:
-                if obs.ndim != 3:
-                    raise NotImplementedError(f"{who}: frame stacking needs single [h, w] frames per slot")
-                return stack, obs.shape[1], obs.shape[2], stack
-            if obs.ndim != 4:
-                raise NotImplementedError(f"{who}: observations must be [c, h, w]")
-            return obs.shape[1], obs.shape[2], obs.shape[3], 1
-
         def _preprocess_batch(self, batch, buffer, indices):
-            _require_gpu(self._hip_device, who)
-            c, h, w, stack = self._layout(buffer)
+            c, h, w, self._hip_stack = self._layout(buffer, who)
+            m, idx = _q_begin(self, who, batch, buffer, indices)
             eng = self._engine(c, h, w)
-            m = _mirror(self, buffer, self._hip_device)
-            idx = torch.as_tensor(np.asarray(indices, np.int64), device=self._hip_device)
-            batch.returns = eng.preprocess(m, m.obs, idx, stack, obs_next_frames=m.obs_next)
-            self._hip_idx, self._hip_stack = idx, stack
-            if hasattr(batch, "weight"):
-                batch.weight = torch.as_tensor(np.asarray(batch.weight), dtype=torch.float32, device=self._hip_device)
+            batch.returns = eng.preprocess(m, m.obs, idx, self._hip_stack, obs_next_frames=m.obs_next)
             return batch
 
         def _update_with_batch(self, batch):
@@ -1519,21 +1519,16 @@ def _make_hip_distq(kind: str, ref=None, cql: bool = False):
             loss, prio = eng.update_with_batch(obs, act, batch.returns, weight, obs_next_nhwc=obs_next)
             self._iter = eng.iter
             batch.weight = prio                                                   # prio-buffer, qrdqn.py:128 / c51.py:157
-            dims = (eng.c, eng.h, eng.w, eng.n_act, eng.cfg.n_atoms)
-            with torch.no_grad():
-                for p, t in zip(self.policy.model.parameters(), Q.flat_to_torch(eng.params, *dims)):
-                    p.copy_(t)
-                if eng.params_old is not None:
-                    for p, t in zip(self.model_old.parameters(), Q.flat_to_torch(eng.params_old, *dims)):
-                        p.copy_(t)
-            store_adam_state(self.optim._optim, list(self.policy.model.parameters()), Q.flat_to_torch(eng.adam_m, *dims),
-                             Q.flat_to_torch(eng.adam_v, *dims), eng.adam_step)
+            self._hip_after_update()
             if cql:
                 total, qr_loss, cql_loss = loss.tolist()                          # one transfer for the three numbers
                 return DiscreteCQLTrainingStats(loss=total, qr_loss=qr_loss, cql_loss=cql_loss)       # discrete_cql.py:109-113
             if kind == Q.QR:
                 return SimpleLossTrainingStats(loss=float(loss.item()))
             return LossSequenceTrainingStats(loss=float(loss.item()))            # as c51.py:160
+
+        _layout = staticmethod(_q_layout)
+        _hip_write_back = _q_write_back
 
     HipDistQ.__name__ = HipDistQ.__qualname__ = who
     return HipDistQ
@@ -1629,81 +1624,48 @@ def make_hip_iqn(ref=None):
             return torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t, dtype=torch.float32,
                                    device=self._hip_device)
 
+        def _hip_qstate(self):
+            return _QState(I.TIANSHOU_KEYS, I.flat_from_torch, I.flat_to_torch,
+                           lambda eng: (eng.c, eng.h, eng.w, eng.n_act, eng.cfg.n_cos))
+
         def _engine(self, c, h, w):
             if self._hip_engine is None:
-                sd = self.policy.model.state_dict()
-                n_act = int(sd[I.TIANSHOU_KEYS[8]].shape[0])
-                opt, g = _adam_of(self.optim)
+                n_act = int(self.policy.model.state_dict()[I.TIANSHOU_KEYS[8]].shape[0])
                 cfg = I.IQNConfig(n_cos=64, sample_size=min(max(int(self.policy.sample_size), 2), 64),
                                   online_sample_size=int(self.policy.online_sample_size),
-                                  target_sample_size=int(self.policy.target_sample_size), gamma=self.gamma, n_step=self.n_step,
-                                  target_update_freq=self.target_update_freq, lr=g["lr"], betas=tuple(g["betas"]),
-                                  adam_eps=g["eps"], max_grad_norm=self.optim._max_grad_norm, seed=self._hip_seed)
-                dev = self._hip_device
-                eng = I.IQNEngine(c, h, w, n_act, I.flat_from_torch([sd[k] for k in I.TIANSHOU_KEYS], c, h, w, n_act, 64, dev), cfg)
-                eng.iter = self._iter
+                                  target_sample_size=int(self.policy.target_sample_size), seed=self._hip_seed,
+                                  **_q_config_fields(self))
+                eng = I.IQNEngine(c, h, w, n_act, _q_flat(self, (c, h, w, n_act, 64)), cfg)
                 eng.tau_counter = self._hip_tau_counter
-                ms, vs, step = adam_state(opt, params_by_keys(self.policy.model, I.TIANSHOU_KEYS))       # resume from a checkpoint
-                eng.adam_m = I.flat_from_torch(ms, c, h, w, n_act, 64, dev)
-                eng.adam_v = I.flat_from_torch(vs, c, h, w, n_act, 64, dev)
-                eng.adam_step = step
-                if eng.params_old is not None:
-                    old = getattr(self.model_old, "module", self.model_old).state_dict()       # EvalModeModuleWrapper
-                    eng.params_old = I.flat_from_torch([old[k] for k in I.TIANSHOU_KEYS], c, h, w, n_act, 64, dev)
-                self._hip_engine = eng
+                self._hip_engine = _q_load(self, eng)
             return self._hip_engine
 
-        @staticmethod
-        def _layout(buffer):
-            obs = np.asarray(buffer.obs)
-            stack = int(getattr(buffer, "stack_num", 1))
-            if stack > 1:
-                if obs.ndim != 3:
-                    raise NotImplementedError("HipIQN: frame stacking needs single [h, w] frames per slot")
-                return stack, obs.shape[1], obs.shape[2], stack
-            if obs.ndim != 4:
-                raise NotImplementedError("HipIQN: observations must be [c, h, w]")
-            return obs.shape[1], obs.shape[2], obs.shape[3], 1
-
         def _preprocess_batch(self, batch, buffer, indices):
-            _require_gpu(self._hip_device, "HipIQN")
-            c, h, w, stack = self._layout(buffer)
+            c, h, w, self._hip_stack = self._layout(buffer, "HipIQN")
+            m, idx = _q_begin(self, "HipIQN", batch, buffer, indices)
             eng = self._engine(c, h, w)
-            m = _mirror(self, buffer, self._hip_device)
-            idx = torch.as_tensor(np.asarray(indices, np.int64), device=self._hip_device)
             tau_online = self._hip_next_tau()                                    # qrdqn.py:100 / :103
             tau_target = self._hip_next_tau() if eng.params_old is not None else None      # qrdqn.py:101
-            batch.returns = eng.preprocess(m, m.obs, idx, stack, obs_next_frames=m.obs_next, tau_online=tau_online,
+            batch.returns = eng.preprocess(m, m.obs, idx, self._hip_stack, obs_next_frames=m.obs_next, tau_online=tau_online,
                                            tau_target=tau_target)
-            self._hip_idx, self._hip_stack = idx, stack
             self._hip_tau_counter = eng.tau_counter
-            if hasattr(batch, "weight"):
-                batch.weight = torch.as_tensor(np.asarray(batch.weight), dtype=torch.float32, device=self._hip_device)
             return batch
 
         def _update_with_batch(self, batch):
             self._hip_refresh_lr()
             eng, m = self._hip_engine, self._hip_mirror
-            idx, stack = self._hip_idx, self._hip_stack
             weight = batch.pop("weight", None)
-            obs = D.gather_obs_nhwc(m.obs, m, idx, stack, as_u8=True)
+            obs = D.gather_obs_nhwc(m.obs, m, self._hip_idx, self._hip_stack, as_u8=True)
             act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device)
             loss, prio = eng.update_with_batch(obs, act, batch.returns, weight, tau=self._hip_next_tau())      # iqn.py:162
             self._iter = eng.iter
             self._hip_tau_counter = eng.tau_counter
             batch.weight = prio                                                   # prio-buffer, iqn.py:180
-            dims = (eng.c, eng.h, eng.w, eng.n_act, eng.cfg.n_cos)
-            params = params_by_keys(self.policy.model, I.TIANSHOU_KEYS)
-            with torch.no_grad():
-                for p, t in zip(params, I.flat_to_torch(eng.params, *dims)):
-                    p.copy_(t)
-                if eng.params_old is not None:
-                    old_mod = getattr(self.model_old, "module", self.model_old)
-                    for p, t in zip(params_by_keys(old_mod, I.TIANSHOU_KEYS), I.flat_to_torch(eng.params_old, *dims)):
-                        p.copy_(t)
-            store_adam_state(self.optim._optim, params, I.flat_to_torch(eng.adam_m, *dims), I.flat_to_torch(eng.adam_v, *dims),
-                             eng.adam_step)
+            self._hip_after_update()
             return SimpleLossTrainingStats(loss=float(loss.item()))
+
+        _layout = staticmethod(_q_layout)
+        _hip_write_back = _q_write_back
 
     return HipIQN
 
@@ -1736,53 +1698,28 @@ def make_hip_rainbow(ref=None):
             sd = model.state_dict()
             return RB.noise_from_torch([sd[k] for k in RB.NOISE_KEYS], *dims, self._hip_device)
 
+        def _hip_qstate(self):
+            return _QState(RB.TIANSHOU_KEYS, RB.flat_from_torch, RB.flat_to_torch,
+                           lambda eng: (eng.c, eng.h, eng.w, eng.n_act, eng.cfg.n_atoms))
+
         def _engine(self, c, h, w):
             if self._hip_engine is None:
                 model = self.policy.model
-                sd = model.state_dict()
                 n_atoms = int(self.policy.num_atoms)
-                n_act = sd["Q.2.mu_bias"].numel() // n_atoms
+                n_act = model.state_dict()["Q.2.mu_bias"].numel() // n_atoms
                 dims = (c, h, w, n_act, n_atoms)
-                opt, g = _adam_of(self.optim)
-                cfg = Q.DistQConfig(kind=Q.C51, n_atoms=n_atoms, gamma=self.gamma, n_step=self.n_step,
-                                    target_update_freq=self.target_update_freq, lr=g["lr"], betas=tuple(g["betas"]),
-                                    adam_eps=g["eps"], max_grad_norm=self.optim._max_grad_norm,
-                                    v_min=float(self.policy.v_min), v_max=float(self.policy.v_max))
-                dev = self._hip_device
-                eng = self._hip_engine = RB.RainbowEngine(c, h, w, n_act, RB.flat_from_torch([sd[k] for k in RB.TIANSHOU_KEYS], *dims, dev),
-                                                          self._noise_of(model, dims), cfg)
-                eng.iter = self._iter
-                ms, vs, step = adam_state(opt, params_by_keys(model, RB.TIANSHOU_KEYS))          # resume from a checkpoint
-                eng.adam_m, eng.adam_v = RB.flat_from_torch(ms, *dims, dev), RB.flat_from_torch(vs, *dims, dev)
-                eng.adam_step = step
+                cfg = Q.DistQConfig(kind=Q.C51, n_atoms=n_atoms, v_min=float(self.policy.v_min), v_max=float(self.policy.v_max),
+                                    **_q_config_fields(self))
+                eng = _q_load(self, RB.RainbowEngine(c, h, w, n_act, _q_flat(self, dims), self._noise_of(model, dims), cfg))
                 if eng.params_old is not None:
-                    so = self.model_old.state_dict()
-                    eng.params_old = RB.flat_from_torch([so[k] for k in RB.TIANSHOU_KEYS], *dims, dev)
                     eng.noise_old = self._noise_of(self.model_old, dims)
+                self._hip_engine = eng
             return self._hip_engine
 
-        @staticmethod
-        def _layout(buffer):
-            obs = np.asarray(buffer.obs)
-            stack = int(getattr(buffer, "stack_num", 1))
-            if stack > 1:
-                if obs.ndim != 3:
-                    raise NotImplementedError("HipRainbow: frame stacking needs single [h, w] frames per slot")
-                return stack, obs.shape[1], obs.shape[2], stack
-            if obs.ndim != 4:
-                raise NotImplementedError("HipRainbow: observations must be [c, h, w]")
-            return obs.shape[1], obs.shape[2], obs.shape[3], 1
-
         def _preprocess_batch(self, batch, buffer, indices):
-            _require_gpu(self._hip_device, "HipRainbow")
-            c, h, w, stack = self._layout(buffer)
-            eng = self._engine(c, h, w)
-            m = _mirror(self, buffer, self._hip_device)
-            idx = torch.as_tensor(np.asarray(indices, np.int64), device=self._hip_device)
-            batch.returns = eng.preprocess(m, idx)
-            self._hip_idx, self._hip_stack = idx, stack
-            if hasattr(batch, "weight"):
-                batch.weight = torch.as_tensor(np.asarray(batch.weight), dtype=torch.float32, device=self._hip_device)
+            c, h, w, self._hip_stack = self._layout(buffer, "HipRainbow")
+            m, idx = _q_begin(self, "HipRainbow", batch, buffer, indices)
+            batch.returns = self._engine(c, h, w).preprocess(m, idx)
             return batch
 
         def _update_with_batch(self, batch):
@@ -1806,20 +1743,19 @@ def make_hip_rainbow(ref=None):
             loss, prio = eng.update_with_batch(obs, act, batch.returns, obs_next, weight)
             self._iter = eng.iter
             batch.weight = prio                                                   # prio-buffer, c51.py:157
-            model = self.policy.model
-            with torch.no_grad():
-                for p, t in zip(params_by_keys(model, RB.TIANSHOU_KEYS), RB.flat_to_torch(eng.params, *dims)):
-                    p.copy_(t)
-                if eng.params_old is not None:
-                    for p, t in zip(params_by_keys(self.model_old, RB.TIANSHOU_KEYS), RB.flat_to_torch(eng.params_old, *dims)):
-                        p.copy_(t)
-                    if (eng.iter - 1) % eng.cfg.target_update_freq == 0:          # the sync carried the noise along
-                        so, sn = self.model_old.state_dict(), model.state_dict()
-                        for k in RB.NOISE_KEYS:
-                            so[k].copy_(sn[k])
-            store_adam_state(self.optim._optim, params_by_keys(model, RB.TIANSHOU_KEYS), RB.flat_to_torch(eng.adam_m, *dims),
-                             RB.flat_to_torch(eng.adam_v, *dims), eng.adam_step)
+            self._hip_after_update()
             return LossSequenceTrainingStats(loss=float(loss.item()))            # as c51.py:160
+
+        _layout = staticmethod(_q_layout)
+
+        def _hip_write_back(self) -> None:
+            _q_write_back(self)
+            eng = self.__dict__.get("_hip_engine_obj")
+            if eng is not None and eng.params_old is not None and (eng.iter - 1) % eng.cfg.target_update_freq == 0:
+                so, sn = self.model_old.state_dict(), self.policy.model.state_dict()      # the sync carried the noise along
+                with torch.no_grad():
+                    for k in RB.NOISE_KEYS:
+                        so[k].copy_(sn[k])
 
     return HipRainbow
 
