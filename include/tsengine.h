@@ -1357,6 +1357,21 @@ int ts_td3_update(ts_workspace* ws, const ts_td3_state* st, int64_t critic_step,
                   const ts_mlp_trunk* trunk, const ts_td3_hparams* hp, float* stats_out3, float* weight_out, float* grads_out,
                   ts_stream_t stream);
 
+/* TD3BC._update_with_batch (imitation/td3_bc.py:102-127, arXiv 2106.06860): ts_td3_update with the actor loss
+ *   lmbda = bc_alpha / Q1(s, pi(s)).abs().mean().detach();  -lmbda * Q1(s, pi(s)).mean() + mse_loss(pi(s), act)
+ * (act = the batch's actions, float32[B, act_dim]).  Critic steps, delayed actor, Polyak updates, weight_out and grads_out are
+ * ts_td3_update's, and so is the number of kernel launches: lmbda stays on the device, the critic backward runs on -1/B and
+ * the policy backward scales its result (the critic backward is linear in its upstream gradient).  The three sums (Q, |Q|,
+ * (pi(s) - act)^2) are taken by one workgroup in a fixed order without atomics: the same inputs give the same bits.
+ * stats_out4 = {actor_loss, critic1_loss, critic2_loss, lmbda}; slots 0 and 3 are written only when hp->update_actor.
+ * bc_alpha must be finite and >= 0 (0: lmbda == 0 exactly, pure behaviour cloning) and both critics must be present (the
+ * reference copies critic 1 when it is given no second one): TS_ERR_INVALID_ARG otherwise, before any HIP call.
+ * Q1.abs().mean() is not clamped: where it is 0, lmbda and the loss are IEEE inf / NaN, as in the reference. */
+int ts_td3bc_update(ts_workspace* ws, const ts_td3_state* st, int64_t critic_step, int64_t actor_step, const float* obs,
+                    const float* act, const float* returns, const float* weight, int64_t B, int64_t obs_dim, int64_t act_dim,
+                    const ts_mlp_trunk* trunk, const ts_td3_hparams* hp, double bc_alpha, float* stats_out4, float* weight_out,
+                    float* grads_out, ts_stream_t stream);
+
 /* ---- data-parallel exchange ------------------------------------------------------------------
  * One process per GPU; the reference has no distributed path (its only multi-GPU mechanism is single-process
  * nn.DataParallel, tianshou/utils/net/common.py:473-515).  In-place sum all-reduce of a flat fp32 buffer over RCCL

@@ -870,6 +870,67 @@ __global__ __launch_bounds__(256) void det_policy_bwd_kernel(const float* __rest
     d_head[b * 32 + j] = dx[b * kc + obs_dim + j] * max_action * (1.f - t * t);
 }
 
+// TD3+BC actor loss (imitation/td3_bc.py:114-117) = -lmbda Q1(s, pi(s)).mean() + mse_loss(pi(s), batch.act) with
+// lmbda = alpha / Q1.abs().mean().detach().  Launched as det_actor_loss_kernel: workgroups 1.. write the d_q1 rows (-1/B: the
+// critic backward is linear in its upstream gradient, so td3bc_policy_bwd_kernel scales dx by lmbda instead), workgroup 0 keeps
+// the three sums in block_sum_1024's order.  x_p holds pi(s) in columns [obs_dim, obs_dim + A) (det_policy_kernel).
+// mean|Q| == 0 gives IEEE inf / NaN, as the reference does: no clamp.
+__global__ __launch_bounds__(1024) void td3bc_actor_loss_kernel(const float* __restrict__ q1, const float* __restrict__ x_p,
+                                                                const float* __restrict__ a_data, int64_t B, int A,
+                                                                int obs_dim, int kc, float alpha, float* __restrict__ d_q1,
+                                                                float* __restrict__ lmbda_out, float* __restrict__ stats) {
+    __shared__ float red[1024];
+    const float inv_b = 1.f / (float)B;
+    if (blockIdx.x > 0) {
+        const int64_t b = (int64_t)(blockIdx.x - 1) * 1024 + threadIdx.x;
+        if (b < B) store_head_row(d_q1 + b * 32, -inv_b);
+        return;
+    }
+    float sq = 0.f, sabs = 0.f, sbc = 0.f;
+    for (int64_t b = threadIdx.x; b < B; b += 1024) {
+        const float q = q1[b * 32];
+        sq += q;
+        sabs += fabsf(q);
+    }
+    // (a - a_data)^2: thread (r, j) of 1024 / A rows x A columns per pass, so that neighbouring lanes read neighbouring
+    // floats of a_data and of a row of x_p (a lane per row would touch 64 cache lines per load) and the loop divides nothing
+    const int rows = 1024 / A, r = (int)threadIdx.x / A, j = (int)threadIdx.x - r * A;
+    if (r < rows) {
+#pragma unroll 8
+        for (int64_t b = r; b < B; b += rows) {
+            const float dlt = x_p[b * kc + obs_dim + j] - a_data[b * A + j];
+            sbc += dlt * dlt;
+        }
+    }
+    const float tq = block_sum_1024(sq, red);
+    const float tabs = block_sum_1024(sabs, red);
+    const float tbc = block_sum_1024(sbc, red);
+    if (threadIdx.x == 0) {
+        const float lmbda = alpha / (tabs / (float)B);
+        *lmbda_out = lmbda;
+        stats[0] = -lmbda * (tq / (float)B) + tbc / ((float)B * (float)A);
+        stats[3] = lmbda;
+    }
+}
+
+// d(actor loss) / d(actor head), det_policy_bwd_kernel's thread map: dx is the critic backward of -mean(Q1), so lmbda dx is
+// the gradient of the Q term; 2 (a - a_data) / (B A) is mse_loss's.  lmbda == 0 (alpha == 0) leaves the cloning term alone.
+__global__ __launch_bounds__(256) void td3bc_policy_bwd_kernel(const float* __restrict__ dx, const float* __restrict__ keep,
+                                                               const float* __restrict__ a_data,
+                                                               const float* __restrict__ lmbda_p, int64_t B, int A,
+                                                               float max_action, int obs_dim, int kc,
+                                                               float* __restrict__ d_head) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;       // thread (b, j < 32): the whole 32-column row is written
+    const int64_t b = i >> 5;
+    const int j = (int)(i & 31);
+    if (b >= B) return;
+    if (j >= A) { d_head[b * 32 + j] = 0.f; return; }
+    const float t = keep[b * A + j];
+    const float inv_n = 1.f / ((float)B * (float)A);
+    const float bc = 2.f * (__fmul_rn(max_action, t) - a_data[b * A + j]) * inv_n;   // a as det_policy_kernel rounded it
+    d_head[b * 32 + j] = (*lmbda_p * dx[b * kc + obs_dim + j] + bc) * max_action * (1.f - t * t);
+}
+
 __global__ __launch_bounds__(1024) void td3_weight_kernel(const float* __restrict__ td1, const float* __restrict__ td2,
                                                           int64_t B, float* __restrict__ out) {
     for (int64_t b = (int64_t)blockIdx.x * 1024 + threadIdx.x; b < B; b += (int64_t)gridDim.x * 1024)
@@ -1827,18 +1888,28 @@ int ts_td3_target_q(ts_workspace* ws, const float* actor_old, const float* criti
     return TS_OK;
 }
 
-int ts_td3_update(ts_workspace* ws, const ts_td3_state* st, int64_t critic_step, int64_t actor_step, const float* obs,
-                  const float* act, const float* returns, const float* weight, int64_t B, int64_t obs_dim, int64_t act_dim,
-                  const ts_mlp_trunk* trunk, const ts_td3_hparams* hp, float* stats_out3, float* weight_out, float* grads_out,
-                  ts_stream_t stream) {
-    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_td3_update: workspace is NULL");
+}  // extern "C"
+
+namespace {
+// TD3._update_with_batch (td3.py:204-226) / DDPG's (ddpg.py:401-411); `bc`: TD3+BC's actor loss (imitation/td3_bc.py:112-120)
+// in place of -Q1.mean() -- the same launches, with the two small actor-phase kernels exchanged.  `who` names the entry point.
+int td3_update_impl(const char* who, bool bc, double bc_alpha, ts_workspace* ws, const ts_td3_state* st, int64_t critic_step,
+                    int64_t actor_step, const float* obs, const float* act, const float* returns, const float* weight, int64_t B,
+                    int64_t obs_dim, int64_t act_dim, const ts_mlp_trunk* trunk, const ts_td3_hparams* hp, float* stats_out3,
+                    float* weight_out, float* grads_out, ts_stream_t stream) {
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "%s: workspace is NULL", who);
     TS_REQUIRE(st && hp && obs && act && returns && stats_out3 && B >= 1 && critic_step >= 1 && actor_step >= 1,
-               TS_ERR_INVALID_ARG, "ts_td3_update: bad argument");
+               TS_ERR_INVALID_ARG, "%s: bad argument", who);
     TS_REQUIRE(st->actor && st->actor_m && st->actor_v && st->critic1 && st->critic1_m && st->critic1_v &&
-                   st->actor_old && st->critic1_old, TS_ERR_INVALID_ARG, "ts_td3_update: NULL state pointer");
+                   st->actor_old && st->critic1_old, TS_ERR_INVALID_ARG, "%s: NULL state pointer", who);
     const bool twin = st->critic2 != nullptr;
     TS_REQUIRE(!twin || (st->critic2_m && st->critic2_v && st->critic2_old), TS_ERR_INVALID_ARG,
-               "ts_td3_update: incomplete second critic");
+               "%s: incomplete second critic", who);
+    if (bc) {
+        TS_REQUIRE(std::isfinite(bc_alpha) && bc_alpha >= 0.0, TS_ERR_INVALID_ARG,
+                   "%s: bc_alpha must be finite and >= 0 (got %g)", who, bc_alpha);
+        TS_REQUIRE(twin, TS_ERR_INVALID_ARG, "%s: TD3+BC needs both critics (critic2 is NULL)", who);
+    }
     Dims d;
     if (int rc = make_dims(trunk, obs_dim, act_dim, &d)) return rc;
     hipStream_t s = ts::as_stream(stream), side;
@@ -1850,7 +1921,7 @@ int ts_td3_update(ts_workspace* ws, const ts_td3_state* st, int64_t critic_step,
     const unsigned gb = (unsigned)ts::ceil_div(B, 256);
     const size_t bytes = al(4 * B * d.ka) + 3 * al(4 * B * d.kc) + 9 * hbytes(B, d) + 4 * al(4 * B * 32) + al(4 * 3 * gb) +
                          4 * hbytes(B, d) + 2 * al(4 * slab) + 2 * al(4 * std::max(pa, pc)) + 2 * al(4 * B) +
-                         al(4 * B * d.act) + 2 * al(4 * spl) + 8192;
+                         al(4 * B * d.act) + 2 * al(4 * spl) + 8192 + (bc ? 256 : 0);
     if (int rc = ts::ws_reserve(ws, bytes)) return rc;
     Carve c{static_cast<char*>(ws->base)};
     float* x_a = c.take<float>(B * d.ka);
@@ -1872,6 +1943,7 @@ int ts_td3_update(ts_workspace* ws, const ts_td3_state* st, int64_t critic_step,
     float* keep = c.take<float>(B * d.act);
     float* splits[2] = {c.take<float>(spl), c.take<float>(spl)};
     float* norm_part = c.take<float>(1024);
+    float* lmbda = bc ? c.take<float>(1) : nullptr;        // TD3+BC: alpha / mean|Q1|, loss kernel -> policy backward
     float* g_out[3] = {grads_out, grads_out ? grads_out + pc : nullptr, grads_out ? grads_out + 2 * pc : nullptr};
 
     hipLaunchKernelGGL(sac_pack_kernel, dim3((unsigned)ts::ceil_div(B * (d.ka + d.kc) / 4, 256)), dim3(256), 0, s, obs, act, B,
@@ -1940,12 +2012,20 @@ int ts_td3_update(ts_workspace* ws, const ts_td3_state* st, int64_t critic_step,
                            (const float*)nullptr, B, d.act, (float)hp->max_action, 0.f, 0.f, d.obs, d.kc, x_p,
                            (float*)nullptr, keep);
         if (int rc = mlp_forward(s, ws, mc, st->critic1, x_p, a1, splits[0])) return rc;
-        hipLaunchKernelGGL(det_actor_loss_kernel, dim3(1 + (unsigned)ts::ceil_div(B, 1024)), dim3(1024), 0, s, a1.out, B, d_q, stats_out3);
+        if (bc)
+            hipLaunchKernelGGL(td3bc_actor_loss_kernel, dim3(1 + (unsigned)ts::ceil_div(B, 1024)), dim3(1024), 0, s, a1.out, x_p,
+                               act, B, d.act, d.obs, d.kc, (float)bc_alpha, d_q, lmbda, stats_out3);
+        else
+            hipLaunchKernelGGL(det_actor_loss_kernel, dim3(1 + (unsigned)ts::ceil_div(B, 1024)), dim3(1024), 0, s, a1.out, B, d_q, stats_out3);
         TS_LAUNCH_CHECK();
         if (int rc = mlp_backward(s, ws, mc, st->critic1, x_p, a1, d_q, nullptr, dx1, d.obs, d.obs + d.act, scs[0]))
             return rc;
-        hipLaunchKernelGGL(det_policy_bwd_kernel, dim3((unsigned)ts::ceil_div(B * 32, 256)), dim3(256), 0, s, dx1, keep, B,
-                           d.act, (float)hp->max_action, d.obs, d.kc, d_pol);
+        if (bc)
+            hipLaunchKernelGGL(td3bc_policy_bwd_kernel, dim3((unsigned)ts::ceil_div(B * 32, 256)), dim3(256), 0, s, dx1, keep, act,
+                               lmbda, B, d.act, (float)hp->max_action, d.obs, d.kc, d_pol);
+        else
+            hipLaunchKernelGGL(det_policy_bwd_kernel, dim3((unsigned)ts::ceil_div(B * 32, 256)), dim3(256), 0, s, dx1, keep, B,
+                               d.act, (float)hp->max_action, d.obs, d.kc, d_pol);
         TS_LAUNCH_CHECK();
         float* ga = g_out[2] ? g_out[2] : gbuf[0];
         if (int rc = mlp_backward(s, ws, ma, st->actor, x_a, aa, d_pol, ga, nullptr, 0, 0, scs[0])) return rc;
@@ -1968,6 +2048,25 @@ int ts_td3_update(ts_workspace* ws, const ts_td3_state* st, int64_t critic_step,
     }
     TS_LAUNCH_CHECK();
     return TS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ts_td3_update(ts_workspace* ws, const ts_td3_state* st, int64_t critic_step, int64_t actor_step, const float* obs,
+                  const float* act, const float* returns, const float* weight, int64_t B, int64_t obs_dim, int64_t act_dim,
+                  const ts_mlp_trunk* trunk, const ts_td3_hparams* hp, float* stats_out3, float* weight_out, float* grads_out,
+                  ts_stream_t stream) {
+    return td3_update_impl("ts_td3_update", false, 0.0, ws, st, critic_step, actor_step, obs, act, returns, weight, B, obs_dim,
+                           act_dim, trunk, hp, stats_out3, weight_out, grads_out, stream);
+}
+
+int ts_td3bc_update(ts_workspace* ws, const ts_td3_state* st, int64_t critic_step, int64_t actor_step, const float* obs,
+                    const float* act, const float* returns, const float* weight, int64_t B, int64_t obs_dim, int64_t act_dim,
+                    const ts_mlp_trunk* trunk, const ts_td3_hparams* hp, double bc_alpha, float* stats_out4, float* weight_out,
+                    float* grads_out, ts_stream_t stream) {
+    return td3_update_impl("ts_td3bc_update", true, bc_alpha, ws, st, critic_step, actor_step, obs, act, returns, weight, B,
+                           obs_dim, act_dim, trunk, hp, stats_out4, weight_out, grads_out, stream);
 }
 
 // ---- DiscreteSAC ---------------------------------------------------------------------------------------------------

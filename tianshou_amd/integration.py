@@ -2472,7 +2472,9 @@ def make_hip_ppo_discrete(algo: str = "ppo", ref=None):
 # ---------------------------------------------------------------------------------------------------
 # TD3 / DDPG (td3.py:104-226, ddpg.py:343-411) on the mujoco_td3.py / mujoco_ddpg.py networks
 # ---------------------------------------------------------------------------------------------------
-def _make_hip_det(twin: bool, ref=None):
+def _make_hip_det(twin: bool, ref=None, bc: bool = False):
+    """`bc`: TD3+BC (imitation/td3_bc.py), TD3 with the behaviour-cloning term in the actor loss -- the same hooks over
+    tianshou_amd.td3bc.TD3BCEngine, with `alpha` read at every update."""
     DDPG = _ref(ref, "tianshou.algorithm.modelfree.ddpg", "DDPG")
     DDPGTrainingStats = _ref(ref, "tianshou.algorithm.modelfree.ddpg", "DDPGTrainingStats")
     TD3 = _ref(ref, "tianshou.algorithm.modelfree.td3", "TD3")
@@ -2481,6 +2483,10 @@ def _make_hip_det(twin: bool, ref=None):
     from . import td3 as T
 
     base = TD3 if twin else DDPG
+    if bc:
+        from . import td3bc as TB
+
+        base = _ref(ref, "tianshou.algorithm.imitation.td3_bc", "TD3BC")      # (OfflineAlgorithm first in its MRO)
 
     class HipDet(_HipGlue, base):
         _HIP_LR = (("actor_lr", "policy_optim"), ("critic_lr", "critic_optim")) + \
@@ -2531,17 +2537,18 @@ def _make_hip_det(twin: bool, ref=None):
                 sa = self.policy.actor.state_dict()
                 obs_dim, act_dim = sa[self._hip_akeys[0]].shape[1], sa[self._hip_akeys[2 * self._hip_depth]].shape[0]
                 ga, gc = _adam_of(self.policy_optim)[1], _adam_of(self.critic_optim)[1]
-                cfg = T.TD3Config(gamma=self.gamma, tau=self.tau, n_step=self.n_step_return_horizon, twin=twin,
-                                  policy_noise=getattr(self, "policy_noise", 0.0), noise_clip=getattr(self, "noise_clip", 0.0),
-                                  update_actor_freq=getattr(self, "update_actor_freq", 1),
-                                  max_action=float(self.policy.actor.max_action), actor_lr=ga["lr"], critic_lr=gc["lr"],
-                                  betas=tuple(ga["betas"]), adam_eps=ga["eps"])
+                Config, Engine = (TB.TD3BCConfig, TB.TD3BCEngine) if bc else (T.TD3Config, T.TD3Engine)
+                cfg = Config(gamma=self.gamma, tau=self.tau, n_step=self.n_step_return_horizon, twin=twin,
+                             policy_noise=getattr(self, "policy_noise", 0.0), noise_clip=getattr(self, "noise_clip", 0.0),
+                             update_actor_freq=getattr(self, "update_actor_freq", 1),
+                             max_action=float(self.policy.actor.max_action), actor_lr=ga["lr"], critic_lr=gc["lr"],
+                             betas=tuple(ga["betas"]), adam_eps=ga["eps"], **({"alpha": float(self.alpha)} if bc else {}))
                 dev = self._hip_device
                 flats = {n: conv([mod.state_dict()[k] for k in keys], obs_dim, act_dim, dev)
                          for n, mod, _, keys, conv, _, _ in self._hip_parts()}
-                eng = self._hip_engine = T.TD3Engine(obs_dim, act_dim, flats["actor"], flats["critic1"],
-                                                     flats.get("critic2"), cfg, hidden=self._hip_hidden, depth=self._hip_depth,
-                                                     activation=self._hip_actfn)
+                eng = self._hip_engine = Engine(obs_dim, act_dim, flats["actor"], flats["critic1"],
+                                                flats.get("critic2"), cfg, hidden=self._hip_hidden, depth=self._hip_depth,
+                                                activation=self._hip_actfn)
                 eng.cnt = getattr(self, "_cnt", 0)
                 for n, mod, optim, keys, conv, _, old in self._hip_parts():           # resume from a checkpoint
                     setattr(eng, n + "_old", conv([old.state_dict()[k] for k in keys], obs_dim, act_dim, dev))
@@ -2567,6 +2574,8 @@ def _make_hip_det(twin: bool, ref=None):
             from .buffer import gather_rows_multi
 
             eng, m = self._hip_engine, self._hip_mirror
+            if bc:
+                eng.cfg.alpha = float(self.alpha)                                 # read at every update, as the learning rate
             stats, w = eng.update_with_batch(*gather_rows_multi([m.obs, m.act], self._hip_idx),
                                              batch.returns.reshape(-1), getattr(batch, "weight", None))
             batch.weight = w
@@ -2588,7 +2597,7 @@ def _make_hip_det(twin: bool, ref=None):
                 return TD3TrainingStats(actor_loss=float(s[0]), critic1_loss=float(s[1]), critic2_loss=float(s[2]))
             return DDPGTrainingStats(actor_loss=float(s[0]), critic_loss=float(s[1]))
 
-    HipDet.__name__ = "HipTD3" if twin else "HipDDPG"
+    HipDet.__name__ = "HipTD3BC" if bc else "HipTD3" if twin else "HipDDPG"
     return HipDet
 
 
@@ -2600,3 +2609,12 @@ def make_hip_td3(ref=None):
 def make_hip_ddpg(ref=None):
     """Returns HipDDPG(DDPG) (hooks ddpg.py:397-411 on the engine)."""
     return _make_hip_det(False, ref)
+
+
+def make_hip_td3bc(ref=None):
+    """Returns HipTD3BC(TD3BC): TD3's hooks (td3.py:190-202, ddpg.py:287-301) with `_update_with_batch` of
+    imitation/td3_bc.py:102-127 on the engine (tianshou_amd/td3bc.py).  Networks as HipTD3, always two critics (the reference
+    copies critic 1 when it is given no second one).  The offline case is a plain ReplayBuffer / VectorReplayBuffer without
+    `weight`; a prioritized buffer works as well.  `alpha` is read from the algorithm at every update; the statistics are
+    TD3TrainingStats.  `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    return _make_hip_det(True, ref, bc=True)
