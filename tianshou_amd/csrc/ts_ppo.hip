@@ -10,8 +10,8 @@
 //                                                                                  + ppo_adam_kernel
 //
 // Roofline: fp32 MFMA (v_mfma_f32_32x32x2_f32, 157.3 TF/s peak).  Algorithmic work of one update
-// step = 60,544 flop / sample; the kernel issues 484 MFMAs (4096 flop each) per
-// 32-sample tile.
+// step = 60,544 flop / sample; per 32-sample tile a wave issues 420 of them (4096 flop
+// each) and, for its quarter of the two dW1 products, 128 v_mfma_f32_16x16x4_f32 (2048 flop each).
 //
 // Data layout in a wave: activations are kept TRANSPOSED, H^T[feature, sample] = W . X^T, so that
 // the MFMA's C/D layout (lane = sample column, 16 registers = 16 feature rows) of one layer is
@@ -43,6 +43,10 @@ __device__ __forceinline__ int featF(int r, int h) { return (r & 3) + 8 * (r >> 
 
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+
+__device__ __forceinline__ f32x4 mfma16x4(float a, float b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
 struct Dims {
@@ -696,6 +700,53 @@ __device__ __forceinline__ f32x16 tile128_mma(const float* T, int rowA, int rowB
     return c;
 }
 
+// dW1aug[f][k] = sum_s dZ1[s][f] Xaug[s][k] for the wave's 16 features f = 16 wave + .. over the workgroup's 128 samples, on
+// 16x16x4 tiles (v_mfma_f32_16x16x4_f32, 32 cycles): columns 0..15 are one N tile, KP > 16 takes a second one.  Lane (m, kg)
+// holds row 16 wave + m of A and row m of B for the k-group kg.  The products of one output element are added in the order
+// a 32x32x2 tile over the same 128 samples adds them (tile128_mma: step j = 16 c + t takes sample 32 c + t and then sample
+// 32 c + t + 16; an fp32 MFMA adds its k-steps one after the other), so that the gradient keeps its bits whichever tile
+// shape computes it: MFMA jp = 8 c + t' takes the steps 2 jp and 2 jp + 1, its k-groups 0..3 the samples 32 c + 2 t',
+// + 16, + 1, + 17 -- one accumulator per tile, a chain of 32.  The phase-B tiles are written with the samples of every
+// 16-group reordered even ones first (dw1_col), so that the eight samples a lane needs from a 32-sample block are two
+// ds_read_b128.  Rows of X^T beyond KP hold stale but finite H1 values; their output columns are not stored.
+__device__ __forceinline__ int dw1_col(int col) { return (col & ~15) | ((col & 1) << 3) | ((col & 15) >> 1); }
+
+template <int KS1>
+__device__ __forceinline__ void dw1_wave(const float* T, int wave, int lane, float* w1, bool first) {
+    constexpr int KP = 2 * KS1;
+    constexpr int NT = KP > 16 ? 2 : 1;
+    static_assert(KP <= 32 && T2_XROW + 16 * NT <= 96, "X^T rows stay below the misc slots");
+    const int m = lane & 15, kg = lane >> 4;
+    const int s0 = 16 * (kg & 1) + 8 * (kg >> 1);
+    const float* pa = T + (16 * wave + m) * P128 + s0;
+    const float* pb = T + (T2_XROW + m) * P128 + s0;
+    f32x4 acc[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const f32x4 a = ld4(pa + 32 * (t >> 1) + 4 * (t & 1));
+        f32x4 b[NT];
+#pragma unroll
+        for (int n = 0; n < NT; ++n) b[n] = ld4(pb + 16 * n * P128 + 32 * (t >> 1) + 4 * (t & 1));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+#pragma unroll
+            for (int n = 0; n < NT; ++n) acc[n] = mfma16x4(a[e], b[n][e], acc[n]);
+        }
+    }
+    // accumulator register r of lane (m, kg) is row 4 kg + r, column m of the tile
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        const int k = 16 * n + m;
+        if (k < KP) {
+            float* p = w1 + (16 * wave + 4 * kg) * KP + k;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) store_acc(p + r * KP, acc[n][r], first);
+        }
+    }
+}
+
 // forward, loss and backward of one net for the wave's 32 samples, up to dZ2 (returned in h2), dZ1, the head-weight
 // gradients gw (lane = feature) and the `misc` row (lanes 0..7 head-bias gradients, 8..15 sigma gradients, 16 loss sum)
 template <int KS1, bool ACTOR, bool BOUNDED = false>
@@ -928,7 +979,6 @@ __device__ __forceinline__ void net_wgrad(float* lds, const StepArgs& g, const D
     [[maybe_unused]] constexpr int MK = ACTOR ? 2 : 10;
     constexpr int NA = ACTOR ? ACT_PAD : 1;
     constexpr int net = ACTOR ? 0 : 1;
-    constexpr int KP = 2 * KS1;
     // lane, wave and the slab pointer are made opaque here: otherwise LLVM hoists the (loop-invariant) store and tile
     // addresses of the fully unrolled body out of the tile loop into the kernel prologue, where they are spilled
     int lane = lane_in;
@@ -960,10 +1010,11 @@ __device__ __forceinline__ void net_wgrad(float* lds, const StepArgs& g, const D
     }
     __syncthreads();                       // B3: all reads of the phase-A tiles are done
     TS_MARK(g, MK + 5);
-    tile128_write(T, 0, dz1[0], col, h);
-    tile128_write(T, 32, dz1[1], col, h);
+    const int colB = dw1_col(col);     // dW1's sample order, see dw1_wave
+    tile128_write(T, 0, dz1[0], colB, h);
+    tile128_write(T, 32, dz1[1], colB, h);
 #pragma unroll
-    for (int s = 0; s < KS1; ++s) T[(T2_XROW + KS1 * h + s) * P128 + col] = in.x[s];
+    for (int s = 0; s < KS1; ++s) T[(T2_XROW + KS1 * h + s) * P128 + colB] = in.x[s];
     {
         float* M = T + T2_MISC + wave * MISC_SLOT;
 #pragma unroll
@@ -971,45 +1022,28 @@ __device__ __forceinline__ void net_wgrad(float* lds, const StepArgs& g, const D
         M[8 * 64 + lane] = misc;
     }
     __syncthreads();                       // B4
-    // the two dW1 tiles go to one wave pair, the small rows to the other; the pairs swap roles between the nets so
-    // that every wave issues the same number of MFMAs per launch
-    const bool w1_wave = ACTOR ? (wave < 2) : (wave >= 2);
-    if (w1_wave) {
-        // dW1aug[f1][k] = sum_s dZ1[s][f1] Xaug[s][k]   (k == obs is the bias column; rows of X^T beyond 2 KS1 hold
-        // stale but finite H1 values whose output columns are not stored)
-        const int tM = wave & 1;
-        const f32x16 c = tile128_mma<false>(T, 32 * tM, T2_XROW, i, h, nullptr);
-        if (i < KP) {
-            float* p = slab + SL.w1[net] + (32 * tM + 4 * h) * KP + i;
-            if (first) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) slab_st(p + ((r & 3) + 8 * (r >> 2)) * KP, c[r]);
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) slab_st(p + ((r & 3) + 8 * (r >> 2)) * KP, ((gfloat_ptr)p)[((r & 3) + 8 * (r >> 2)) * KP] + c[r]);
-            }
-        }
-    } else {
-        const int part = wave & 1;
+    dw1_wave<KS1>(T, wave, lane, slab + SL.w1[net], first);
+    {
+        // the small rows: wave w sums the head-weight rows 2 w and 2 w + 1 of the four waves' slots (critic: wave 1 its one
+        // row), wave 0 the misc row
         const float* M = T + T2_MISC;
         const int n_head = ACTOR ? d.act : 1;
         if (ACTOR) {
-            // part 0: rows 0..3 and the misc row, part 1: rows 4..7
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int row = 4 * part + q;
+            for (int q = 0; q < 2; ++q) {
+                const int row = 2 * wave + q;
                 float v = 0.f;
 #pragma unroll
                 for (int sl = 0; sl < STEP_WAVES; ++sl) v += M[sl * MISC_SLOT + row * 64 + lane];
                 if (row < n_head) store_acc(slab + SL.head[net] + row * HID + lane, v, first);
             }
-        } else if (part == 1) {
+        } else if (wave == 1) {
             float v = 0.f;
 #pragma unroll
             for (int sl = 0; sl < STEP_WAVES; ++sl) v += M[sl * MISC_SLOT + lane];
             store_acc(slab + SL.head[net] + lane, v, first);
         }
-        if (part == 0) {
+        if (wave == 0) {
             float v = 0.f;
 #pragma unroll
             for (int sl = 0; sl < STEP_WAVES; ++sl) v += M[sl * MISC_SLOT + 8 * 64 + lane];
