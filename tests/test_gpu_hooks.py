@@ -1919,3 +1919,97 @@ def test_hip_reinforce_hooks_on_generic_trunks_replay_the_reference(tag):
         k_v = "square_avg" if cfg["opt_rmsprop"] else "exp_avg_sq"
         for i, k in enumerate(keys):
             np.testing.assert_allclose(state[named[k]][k_v].cpu().numpy(), g[f"u{u}_a{i}_v"], rtol=2e-3, atol=1e-9, err_msg=f"update {u}: {k} v")
+
+
+# ------------------------------------------------------------------------------------ a rebuilt engine continues (eager bodies)
+def _ac_resume_algo(which):
+    """HipTD3 / HipDDPG / HipDiscreteSAC / HipREDQ over the stand-ins: observations of 11, 3 actions (5 discrete ones), trunks
+    [48, 40] -- unequal widths, no multiple of 32, so the state path goes through the zero-padding embed and `sizes=`."""
+    from tianshou_amd import integration as I
+
+    obs_dim, act_dim, n_act, H = 11, 3, 5, [48, 40]
+    torch.manual_seed(71)
+    net = lambda d, **kw: SI.Net(d, H, nn.ReLU, **kw)   # noqa: E731
+    if which in ("td3", "ddpg"):
+        actor = SI.ContinuousActorDeterministic(net(obs_dim), act_dim, max_action=1.0)
+        kw = dict(policy=SI.Policy(actor), critic=SI.ContinuousCritic(net(obs_dim + act_dim)), lr=3e-4, critic_lr=1e-3, tau=0.01,
+                  gamma=0.98, device="cuda")
+        if which == "td3":
+            algo = I.make_hip_td3(ref=SI)(critic2=SI.ContinuousCritic(net(obs_dim + act_dim)), policy_noise=0.2,
+                                          update_actor_freq=2, noise_clip=0.5, **kw)
+        else:
+            algo = I.make_hip_ddpg(ref=SI)(**kw)
+    elif which == "redq":
+        lin = lambda x, y: SI.EnsembleLinear(3, x, y)   # noqa: E731
+        actor = SI.ContinuousActorProbabilistic(net(obs_dim), act_dim, unbounded=True, conditioned_sigma=True)
+        critic = SI.ContinuousCritic(net(obs_dim + act_dim, linear_layer=lin), linear_layer=lin)
+        algo = I.make_hip_redq(ref=SI)(policy=SI.Policy(actor), critic=critic, lr=3e-4, critic_lr=1e-3, ensemble_size=3, subset_size=2,
+                                       tau=0.01, gamma=0.97, alpha=SI.AutoAlpha(-float(act_dim), -0.6, 3e-4), actor_delay=2,
+                                       target_mode="min", device="cuda")
+    else:
+        actor = SI.DiscreteActor(net(obs_dim), n_act, softmax_output=False)
+        c1, c2 = SI.DiscreteCritic(net(obs_dim), last_size=n_act), SI.DiscreteCritic(net(obs_dim), last_size=n_act)
+        algo = I.make_hip_discrete_sac(ref=SI)(policy=SI.Policy(actor), critic=c1, critic2=c2, lr=3e-4, critic_lr=1e-3, tau=0.02, gamma=0.96,
+                                               alpha=SI.AutoAlpha(0.98 * float(np.log(n_act)), -0.4, 3e-4), device="cuda",
+                                               match_rng_stream=which == "dsac_match_rng")
+    algo = algo.to("cuda")
+    assert algo._hip_hidden == 64 and algo._hip_sizes["actor"] == (48, 40)
+    algo.policy.is_within_training_step = True
+    discrete = which.startswith("dsac")
+    buf = SI.VectorReplayBuffer(4 * 100, 4, obs_shape=(obs_dim,), act_shape=() if discrete else (act_dim,),
+                                act_dtype=np.int64 if discrete else np.float32, seed=72)
+    rng = np.random.default_rng(73)
+    obs = rng.normal(size=(61, 4, obs_dim)).astype(np.float32)
+    for t in range(60):                                                          # 240 rows, about 5 % terminals
+        term = rng.random(4) < 0.05
+        act = rng.integers(0, n_act, 4) if discrete else rng.normal(size=(4, act_dim)).astype(np.float32)
+        buf.add(SI.Batch(obs=obs[t], act=act, rew=rng.normal(size=4).astype(np.float32), terminated=term,
+                         truncated=(rng.random(4) < 0.03) & ~term, obs_next=obs[t + 1]))
+    return algo, buf
+
+
+def _ac_resume_optimizers(algo):
+    opts = [o._optim for o in algo._optimizers]
+    return opts + ([algo.alpha._optim] if hasattr(getattr(algo, "alpha", None), "_optim") else [])
+
+
+@pytest.mark.parametrize("which", ["td3", "ddpg", "dsac_match_rng", "dsac_no_draws", "redq"])
+def test_hip_actor_critic_rebuilt_engine_continues_where_the_last_one_stopped(which):
+    """The torch<->engine state path of the eager off-policy actor-critic bodies, both directions, on the real engine: run A makes
+    four updates; run B, seeded alike, makes two, drops its engine (`_hip_invalidate()`: the next update builds a new one from the
+    torch modules and torch.optim) and makes two more.  Write-back and load are plain fp32 copies, so B ends bit for bit where A
+    does: every online and lagged parameter, log alpha, every optimizer's moments and step, the last update's statistics.
+    (HipDDPG: the critic's Adam step is the engine's `cnt`, which the hooks keep in `_cnt` as for TD3; without it the rebuilt engine
+    restarted that count at 0 and the critic ended up to 0.87 lr away, its `step` at 2 instead of 4.)"""
+    import dataclasses
+
+    def run(algo, buf, us):
+        for u in us:
+            torch.manual_seed(900 + u)                                            # the hooks' torch.randn / Categorical draws
+            np.random.seed(950 + u)                                               # REDQ's critic subset
+            stats = algo.update(buf, 32)
+        return dataclasses.asdict(stats)
+
+    a, buf_a = _ac_resume_algo(which)
+    stats_a = run(a, buf_a, range(4))
+    b, buf_b = _ac_resume_algo(which)
+    run(b, buf_b, range(2))
+    first = b._hip_engine
+    b._hip_invalidate()
+    stats_b = run(b, buf_b, range(2, 4))
+    assert first is not None and b._hip_engine is not first
+    pa, pb = dict(a.named_parameters()), dict(b.named_parameters())
+    assert list(pa) == list(pb) and any("_old" in k for k in pa) and ("alpha._log_alpha" in pa) == (which not in ("td3", "ddpg"))
+    worst = {k: float((pa[k].detach() - pb[k].detach()).abs().max()) for k in pa if not torch.equal(pa[k], pb[k])}
+    print(which, "parameters that differ:", worst, "statistics:", stats_a, stats_b)
+    oa, ob = _ac_resume_optimizers(a), _ac_resume_optimizers(b)
+    assert len(oa) == len(ob) == {"td3": 3, "ddpg": 2, "redq": 3}.get(which, 4)
+    state = []
+    for i, (x, y) in enumerate(zip(oa, ob)):
+        for j, (p, q) in enumerate(zip(x.param_groups[0]["params"], y.param_groups[0]["params"])):
+            sx, sy = x.state[p], y.state[q]
+            assert set(sx) == set(sy) == {"step", "exp_avg", "exp_avg_sq"}, (i, j)
+            state += [(i, j, k, float(sx[k]) if k == "step" else None, float(sy[k]) if k == "step" else None)
+                      for k in sx if not torch.equal(sx[k].cpu(), sy[k].cpu())]
+    print(which, "optimizer state entries that differ:", state)
+    assert not worst and not state and stats_a == stats_b

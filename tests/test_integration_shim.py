@@ -1178,7 +1178,7 @@ def test_a2c_subclasses_map_hyperparameters_and_fail_loudly():
 
 
 # ------------------------------------------------------------------------------------ REDQ subclass
-def _redq_algo(auto=True, hidden=256, **kw):
+def _redq_algo(auto=True, hidden=256, actor_delay=2, **kw):
     ref_shim.install()
     import gymnasium as gym
 
@@ -1198,7 +1198,7 @@ def _redq_algo(auto=True, hidden=256, **kw):
     alpha = AutoAlpha(-3.0, 0.0, AdamOptimizerFactory(lr=3e-4)) if auto else 0.2
     return make_hip_redq()(policy=policy, policy_optim=AdamOptimizerFactory(lr=1e-3), critic=critic,
                            critic_optim=AdamOptimizerFactory(lr=1e-3), ensemble_size=4, subset_size=2, alpha=alpha,
-                           actor_delay=2, target_mode="min", n_step_return_horizon=2, device="cpu", **kw)
+                           actor_delay=actor_delay, target_mode="min", n_step_return_horizon=2, device="cpu", **kw)
 
 
 def test_redq_subclass_keeps_signatures_and_fails_loudly():
@@ -1834,6 +1834,207 @@ def test_q_write_back_leaves_a_foreign_write_alone(which, monkeypatch):
         algo.__dict__["_hip_skip_ids"] = None
     assert torch.equal(params[1].detach(), before[1])
     assert all(torch.allclose(p.detach(), b + 1.0) for i, (p, b) in enumerate(zip(params, before)) if i != 1)
+
+
+# ------------------------------------------------------------------------------------ the actor-critic classes' one state path
+class _ACDouble:
+    """What the four off-policy actor-critic class bodies (HipSAC, HipREDQ, HipDiscreteSAC, HipTD3 / HipDDPG / HipTD3BC) use of
+    their engines, on the CPU.  `names` (set per body, see `_ac_body`) are the engine's networks, `lagged` those with a `_old` copy.
+    Every update adds a constant of its own to each network's parameters, lagged parameters and two Adam moments (`INC` plus the
+    network's position / 128: all exact in fp32, all distinct) and to log alpha and its moments, and advances the counters as the
+    real engines do.  `built` collects the engines in the order they were constructed."""
+    INC = {"": 2.0, "_old": 0.5, "_m": 0.125, "_v": 0.25, "log_alpha": 0.0625, "log_alpha_m": 0.03125, "log_alpha_v": 0.046875}
+
+    def __init__(self, *args, hidden=None, **kw):            # dims (hidden among them for DiscreteSAC), one flat per network, cfg
+        flats = [a for a in args if isinstance(a, torch.Tensor)]
+        dims = [a for a in args if isinstance(a, int)]
+        self.obs_dim, self.act_dim, self.hidden = dims[0], dims[1], hidden if hidden is not None else dims[2]
+        self.n_act, self.cfg = self.act_dim, [a for a in args if a is not None][-1]
+        assert len(flats) == len(self.names)
+        for n, f in zip(self.names, flats):
+            setattr(self, n, f.clone())
+            setattr(self, n + "_m", torch.zeros_like(f))
+            setattr(self, n + "_v", torch.zeros_like(f))
+            if n in self.lagged:
+                setattr(self, n + "_old", f.clone())
+        self.log_alpha, self.log_alpha_m, self.log_alpha_v = torch.zeros(1), torch.zeros(1), torch.zeros(1)
+        self.adam_step = self.cnt = self.actor_steps = self.critic_gradient_step = 0
+        self._stats = torch.zeros(4)
+        self.built.append(self)
+
+    @classmethod
+    def inc(cls, name, kind):
+        return cls.INC[kind] + cls.names.index(name) / 128.0
+
+    def will_update_actor(self):                             # REDQEngine
+        return (self.critic_gradient_step + 1) % self.cfg.actor_delay == 0
+
+    def policy_forward(self, obs):                           # DiscreteSACEngine
+        return torch.zeros(obs.shape[0], self.n_act)
+
+    def preprocess(self, *a, **k):
+        return torch.zeros(8)
+
+    def update_with_batch(self, *a, **k):
+        self.adam_step += 1                                  # SACEngine, DiscreteSACEngine
+        self.actor_steps += int(self.will_update_actor() if hasattr(self.cfg, "actor_delay") else
+                                self.cnt % (self.cfg.update_actor_freq if self.cfg.twin else 1) == 0 if hasattr(self.cfg, "twin") else 0)
+        self.critic_gradient_step += 1                       # REDQEngine
+        self.cnt += 1                                        # TD3Engine
+        for n in self.names:
+            for kind in ("", "_m", "_v") + (("_old",) if n in self.lagged else ()):
+                self.add(n, kind)
+        for n in ("log_alpha", "log_alpha_m", "log_alpha_v"):
+            getattr(self, n).add_(self.INC[n])
+        return torch.arange(1.0, 6.0), torch.ones(8)
+
+    def add(self, name, kind):
+        getattr(self, name + kind).add_(self.inc(name, kind))
+
+
+_AC_BODIES = ["sac", "dsac", "redq", "td3", "ddpg", "td3bc"]
+
+
+def _ac_body(which, monkeypatch, double=_ACDouble):
+    """-> (the algorithm of one class body with an `_ACDouble` in place of its engine, a buffer to sample 8 of, the doubles built so
+    far, per engine network: (flat vector -> tensors in torch layout by the engine module's own converter, the online torch module,
+    the lagged one or None, its optimizer, the engine counter that is its step count, whether the optimizer's step is loaded))."""
+    from tianshou.data import VectorReplayBuffer
+    import tianshou_amd.dsac as DS
+    import tianshou_amd.redq as RQ
+    import tianshou_amd.returns as R
+    import tianshou_amd.sac as S
+    import tianshou_amd.td3 as T
+    import tianshou_amd.td3bc as TB
+
+    act = np.zeros(2, np.int64) if which == "dsac" else np.zeros((2, 3), np.float32)
+    if which == "td3bc":
+        from tests import test_td3bc_shim as TT
+
+        if not TT.REAL:
+            pytest.skip("reference not mounted")
+        algo, mod, engine = TT._make(alpha=1.25), TB, "TD3BCEngine"
+    else:
+        algo, mod, engine = {"sac": lambda: (_make_sac_algo(), S, "SACEngine"),
+                             "dsac": lambda: (_dsac_algo(), DS, "DiscreteSACEngine"),
+                             "redq": lambda: (_redq_algo(actor_delay=1), RQ, "REDQEngine"),       # (the actor steps at update 1)
+                             "td3": lambda: (_det_algo(True), T, "TD3Engine"),
+                             "ddpg": lambda: (_det_algo(False), T, "TD3Engine")}[which]()
+    actor = algo.policy.actor
+    if which in ("sac", "dsac"):
+        conv_a = (lambda f: S.actor_flat_to_torch(f, 11, 3, 256)) if which == "sac" else (lambda f: DS.net_flat_to_torch(f, 11, 5, 64))
+        conv_c = (lambda f: S.critic_flat_to_torch(f, 11, 3, 256)) if which == "sac" else conv_a
+        nets = {"actor": (conv_a, actor, None, algo.policy_optim, "adam_step", True),
+                "critic1": (conv_c, algo.critic, algo.critic_old.module, algo.critic_optim, "adam_step", True),
+                "critic2": (conv_c, algo.critic2, algo.critic2_old.module, algo.critic2_optim, "adam_step", True)}
+    elif which == "redq":
+        nets = {"actor": (lambda f: S.actor_flat_to_torch(f, 11, 3, 256), actor, None, algo.policy_optim, "actor_steps", True),
+                "critics": (lambda f: RQ.ensemble_flat_to_torch(f, 4, 11, 3, 256), algo.critic, algo.critic_old.module, algo.critic_optim,
+                            "critic_gradient_step", False)}
+    else:
+        conv_c = lambda f: T.critic_flat_to_torch(f, 11, 3, 256)   # noqa: E731
+        nets = {"actor": (lambda f: T.actor_flat_to_torch(f, 11, 3, 256), actor, algo.actor_old.module, algo.policy_optim, "actor_steps", True),
+                "critic1": (conv_c, algo.critic, algo.critic_old.module, algo.critic_optim, "cnt", False)}
+        if which != "ddpg":
+            nets["critic2"] = (conv_c, algo.critic2, algo.critic2_old.module, algo.critic2_optim, "cnt", False)
+    double = type("Double", (double,), {"built": [], "names": tuple(nets), "lagged": tuple(n for n, v in nets.items() if v[2] is not None)})
+    _patch_for_cpu(monkeypatch)
+    monkeypatch.setattr(mod, engine, double)
+    monkeypatch.setattr(DS, "layout", lambda o, a, h, d=2: {"ka": 32, "hw": 32, "count": 33 * h + (h + 1) * h + (h + 1) * 32,
+                                                             "offs": [0, 33 * h, 33 * h + (h + 1) * h, 33 * h + (h + 1) * h + (h + 1) * 32]})
+    monkeypatch.setattr(R, "nstep_indices", lambda m, idx, n: idx)
+    buf = VectorReplayBuffer(32, 2)
+    _fill(buf, 12, (11,), act)
+    return algo, buf, double.built, nets
+
+
+def _ac_update(algo, buf):
+    from tianshou.utils.torch_utils import policy_within_training_step
+
+    with policy_within_training_step(algo.policy):
+        algo.update(buffer=buf, sample_size=8)
+    algo.hip_sync()                                        # (HipSAC writes back when somebody reads; the others already have)
+
+
+@pytest.mark.parametrize("which", _AC_BODIES)
+def test_ac_engine_rebuilt_from_torch_receives_what_the_last_one_wrote_back(which, monkeypatch):
+    """Load and write-back are inverses: after one update, the engine is dropped and built again from the torch modules and
+    torch.optim; it starts from the parameters, lagged parameters, Adam moments, step counts and log alpha moments the first one
+    ended with.  (Compared in torch layout: the padding of a flat vector is not state.)"""
+    algo, buf, built, nets = _ac_body(which, monkeypatch)
+    _ac_update(algo, buf)
+    first = built[0]
+    algo._hip_invalidate()
+    second = algo._engine()
+    assert built == [first, second] and second is not first
+    for name, (to_torch, _, old, _, counter, loaded) in nets.items():
+        assert getattr(second, counter) == getattr(first, counter) == 1, (name, counter)       # (the critics': by the algorithm)
+        for kind in ("", "_m", "_v") + (("_old",) if old is not None else ()):
+            a, b = to_torch(getattr(first, name + kind)), to_torch(getattr(second, name + kind))
+            assert len(a) == len(b) > 0 and all(torch.equal(x, y.to(x.dtype)) for x, y in zip(a, b)), (name, kind)
+            if kind in ("_m", "_v"):
+                assert all(bool((y == first.inc(name, kind)).all()) for y in b), (name, kind)  # ... what the update left, not zeros
+        if old is not None:                                                   # the lagged network kept its own values
+            assert all(torch.allclose(o + 1.5, n) for o, n in zip(to_torch(getattr(second, name + "_old")), to_torch(getattr(second, name))))
+    if which in ("sac", "dsac", "redq"):
+        assert second.cfg.auto_alpha and float(second.cfg.log_alpha0) == float(first.log_alpha) == 0.0625
+        assert (float(second.log_alpha_m), float(second.log_alpha_v)) == (0.03125, 0.046875)
+
+
+@pytest.mark.parametrize("which", _AC_BODIES)
+def test_ac_write_back_leaves_a_foreign_write_alone(which, monkeypatch):
+    """`_hip_write_back` of every actor-critic class goes through `_hip_put`: a parameter somebody else has written since the
+    engine snapshotted it (`_hip_skip_ids`, set by the `_hip_engine` property) keeps its value, online or lagged; all others,
+    of every module, are written."""
+    algo, buf, built, nets = _ac_body(which, monkeypatch)
+    _ac_update(algo, buf)
+    mods = [m for _, m, old, _, _, _ in nets.values() for m in (m, old) if m is not None]
+    params = [p for m in mods for p in m.parameters()]
+    before = [p.detach().clone() for p in params]
+    for name, (_, _, old, _, _, _) in nets.items():
+        getattr(built[0], name).add_(1.0)
+        if old is not None:
+            getattr(built[0], name + "_old").add_(1.0)
+    last = list(nets.values())[-1]                         # a critic: it has a lagged copy in every body
+    skip = {id(list(last[1].parameters())[1]), id(list(last[2].parameters())[0])}
+    algo.__dict__["_hip_skip_ids"] = skip
+    try:
+        algo._hip_write_back()
+    finally:
+        algo.__dict__["_hip_skip_ids"] = None
+    assert sum(id(p) in skip for p in params) == 2
+    for p, b in zip(params, before):
+        assert torch.equal(p.detach(), b) if id(p) in skip else torch.allclose(p.detach(), b + 1.0)
+
+
+def test_ac_write_back_follows_key_order_not_definition_order(monkeypatch):
+    """HipSAC's write-back pairs the converters' tensors, which come in `keys` order, with the parameters of those names, for
+    the parameters as for the Adam state: an update that moves the k-th tensor (in key order) of every network by k + 1 is found
+    under the k-th key, in whatever order the module defines its parameters."""
+    import tianshou_amd.sac as S
+
+    class ByPosition(_ACDouble):
+        def add(self, name, kind):
+            back = S.actor_flat_to_torch if name == "actor" else S.critic_flat_to_torch
+            fwd = S.actor_flat_from_torch if name == "actor" else S.critic_flat_from_torch
+            t = back(getattr(self, name + kind), 11, 3, 256)
+            setattr(self, name + kind, fwd([x + (k + 1) for k, x in enumerate(t)], 11, 3, "cpu", hidden=256))
+
+    algo, buf, built, nets = _ac_body("sac", monkeypatch, ByPosition)
+    mods = {"actor": algo.policy.actor, "critic1": algo.critic, "critic2": algo.critic2}
+    keys = {"actor": S.actor_keys(2), "critic1": S.critic_keys(2), "critic2": S.critic_keys(2)}
+    # definition order is NOT key order here: the heads come first in the modules' own parameter lists
+    for m in mods.values():
+        m._modules["preprocess"] = m._modules.pop("preprocess")
+        assert [k for k, _ in m.named_parameters()][0].split(".")[0] != "preprocess"
+    before = {n: {k: p.detach().clone() for k, p in m.named_parameters()} for n, m in mods.items()}
+    _ac_update(algo, buf)
+    for n, m in mods.items():
+        named = dict(m.named_parameters())
+        for k, key in enumerate(keys[n]):
+            assert torch.allclose(named[key].detach(), before[n][key] + (k + 1)), (n, key)
+            st = nets[n][3]._optim.state[named[key]]
+            assert bool((st["exp_avg"] == k + 1).all()) and bool((st["exp_avg_sq"] == k + 1).all()), (n, key)
 
 
 def test_device_permutation_key_follows_numpy_seed_and_travels_in_the_checkpoint():

@@ -689,7 +689,7 @@ def test_redq_standin_has_the_reference_surface():
     from tianshou_amd.integration import make_hip_redq
 
     A, B = make_hip_redq(), make_hip_redq(ref=SI)
-    for name in ("__init__", "_preprocess_batch", "_update_with_batch", "_engine", "_critic_tensors"):
+    for name in ("__init__", "_preprocess_batch", "_update_with_batch", "_engine", "_hip_parts"):
         assert getattr(A, name).__code__.co_code == getattr(B, name).__code__.co_code, name
 
 

@@ -8,7 +8,8 @@ Overrides exactly the two hooks `Algorithm._update` calls (algorithm_base.py:622
 keeping the Policy / Algorithm API, the Batch fields (`v_s`, `returns`, `adv`, `logp_old`, `act`),
 the stats dataclasses and `state_dict()` (parameters and Adam moments are copied back into the
 torch modules / optimizer after every update(), or, under `write_back="lazy"`, when somebody reads them; for the
-Q-learning classes, HipDQN to HipRainbow, that copy is `_q_write_back`).  Supported net: the MuJoCo actor-critic of
+Q-learning classes, HipDQN to HipRainbow, that copy is `_q_write_back`; for the off-policy actor-critic classes, HipSAC, HipREDQ,
+HipDiscreteSAC and HipTD3 / HipDDPG / HipTD3BC, it is `_ac_write_back`).  Supported net: the MuJoCo actor-critic of
 examples/mujoco/mujoco_ppo.py (Net[64,64] tanh, ContinuousActorProbabilistic(unbounded=True) with a
 state-independent sigma, ContinuousCritic); anything else raises at construction.
 """
@@ -140,7 +141,7 @@ class _HipGlue:
     @_hip_engine.setter
     def _hip_engine(self, value) -> None:
         self.__dict__["_hip_engine_obj"] = value
-        self.__dict__["_hip_pdicts"] = self.__dict__["_hip_modules"] = None
+        self.__dict__["_hip_pdicts"] = self.__dict__["_hip_modules"] = self.__dict__["_hip_ac_params"] = None
         self.__dict__["_hip_versions"] = None if value is None else self._hip_current_versions()
 
     # -- write-back of what the engine learnt (off-policy subclasses) ---------------------------------------------------
@@ -279,7 +280,7 @@ class _HipGlue:
         """`Algorithm.load_state_dict` replaced parameters AND optimizer state: drop the engine without flushing."""
         self.__dict__["_hip_engine_obj"] = None
         self.__dict__["_hip_versions"] = None
-        self.__dict__["_hip_pdicts"] = self.__dict__["_hip_modules"] = None
+        self.__dict__["_hip_pdicts"] = self.__dict__["_hip_modules"] = self.__dict__["_hip_ac_params"] = None
         self.__dict__["_hip_stale"] = False
         self._hip_adam_dirty = False
         # the collector forward's flat copy of the torch parameters is keyed on (data_ptr, _version): blind to `.data` edits too
@@ -1248,6 +1249,134 @@ def _q_write_back(algo) -> None:
     store_adam_state(algo.optim._optim, params, st.to_torch(eng.adam_m, *dims), st.to_torch(eng.adam_v, *dims), eng.adam_step)
 
 
+# -- what the off-policy actor-critic classes (HipSAC, HipREDQ, HipDiscreteSAC, HipTD3 / HipDDPG / HipTD3BC) share: the same two
+# paths over one `_ACPart` per network (`_ac_load`, `_ac_write_back`), the constructor envelope, the config fields, the preamble --
+class _ACPart(NamedTuple):
+    """How one network's torch state maps to its engine's flat vectors `eng.<name>`, `eng.<name>_old`, `eng.<name>_m` / `_v`.
+    Every class body builds its parts in `_hip_parts()`, per call (the converters are looked up in their engine module when they
+    are used) and closes them over its dims, so the engine modules' differing converter signatures end there."""
+    name: str             # the engine attribute stem
+    module: object        # the online torch module
+    old: object           # the lagged torch module, or None
+    optim: object         # the Algorithm.Optimizer wrapper of `module`
+    keys: list            # names of the parameters, in the order the converters take and return them
+    from_torch: Callable  # tensors in `keys` order (parameters or Adam moments) -> flat
+    to_torch: Callable    # flat -> tensors in `keys` order
+    step: str             # the engine counter that is this optimizer's step count at write-back
+    load_step: bool       # whether torch.optim's step is loaded into that counter (else the body sets it from the algorithm)
+
+    def flat(self) -> torch.Tensor:
+        """The online network's parameters as the flat vector an engine is constructed from."""
+        return self.from_torch([p.detach() for p in params_by_keys(self.module, self.keys)])
+
+
+def _ac_nets(algo, who: str, envelope: str, nets, optims, widths=None) -> dict:
+    """The constructor envelope.  `nets`: (name, module, depth -> state_dict keys) per network, actor first: one depth for all of
+    them (`_hip_depth`), one activation (`_hip_actfn`), the hidden widths (`_hip_sizes`; `widths[name]`: tensors -> widths of a
+    network that is no plain MLP) embedded in one engine width (`_hip_hidden`), Adam on every optimizer, and the actor's
+    `_hip_obs_dim` / `_hip_act_dim`.  -> {name: keys}"""
+    from . import widths as WD
+
+    keys, depth = {}, None
+    for name, mod, keys_of in nets:
+        have = list(mod.state_dict().keys())
+        d = next((d for d in range(1, WD.MAX_DEPTH + 1) if have == keys_of(d)), None)
+        if d is None or depth not in (None, d):
+            raise NotImplementedError(f"{who}: {envelope}")
+        depth, keys[name] = d, have
+    algo._hip_depth = depth
+    algo._hip_actfn = _trunk_activation([mod for _, mod, _ in nets], who)
+    try:        # any hidden widths per network: embedded by zero padding into the engine's Net[h] * depth (tianshou_amd.widths)
+        sizes = {}
+        for name, mod, _ in nets:
+            t = [p.detach() for p in params_by_keys(mod, keys[name])]
+            sizes[name] = widths[name](t) if name in (widths or {}) else WD.layer_widths(t, len(t) // 2 - depth)
+        algo._hip_sizes, algo._hip_hidden = sizes, WD.engine_hidden(sizes.values())
+    except NotImplementedError as e:
+        raise NotImplementedError(f"{who}: hidden layers of widths up to 1024 per network ({e})") from None
+    for o in optims:
+        _adam_of(o)
+    first = dict(nets[0][1].named_parameters())
+    algo._hip_obs_dim = int(first[keys[nets[0][0]][0]].shape[1])
+    algo._hip_act_dim = int(first[keys[nets[0][0]][2 * depth]].shape[0])
+    return keys
+
+
+def _ac_config_fields(algo) -> dict:
+    """The target / optimizer fields every actor-critic engine's config has."""
+    ga, gc = _adam_of(algo.policy_optim)[1], _adam_of(algo.critic_optim)[1]
+    return dict(gamma=algo.gamma, tau=algo.tau, n_step=algo.n_step_return_horizon, actor_lr=ga["lr"], critic_lr=gc["lr"],
+                betas=tuple(ga["betas"]), adam_eps=ga["eps"])
+
+
+def _ac_entropy_fields(algo, AutoAlpha) -> dict:
+    """The entropy-coefficient fields of SACConfig / REDQConfig: a fixed alpha, or AutoAlpha's (sac.py:175-210)."""
+    auto = isinstance(algo.alpha, AutoAlpha)
+    return dict(alpha=0.0 if auto else float(algo.alpha.value), auto_alpha=auto,
+                target_entropy=float(algo.alpha._target_entropy) if auto else 0.0,
+                log_alpha0=float(algo.alpha._log_alpha.item()) if auto else 0.0,
+                alpha_lr=algo.alpha._optim.param_groups[0]["lr"] if auto else 0.0)
+
+
+def _ac_begin(algo, who: str, buffer, indices):
+    """Every `_preprocess_batch`: -> (engine, device mirror of `buffer`, `indices` as a device tensor, kept in `_hip_idx` for
+    `_update_with_batch`)."""
+    _require_gpu(algo._hip_device, who)
+    eng = algo._engine()
+    m = _mirror(algo, buffer, algo._hip_device)
+    idx = algo._hip_idx = torch.as_tensor(np.asarray(indices, np.int64), device=algo._hip_device)
+    return eng, m, idx
+
+
+def _ac_load(algo, eng):
+    """Torch state -> a fresh engine (built from every part's `flat()`): lagged networks, Adam moments and step counts (resume from
+    a checkpoint), log alpha's moments.  The inverse of `_ac_write_back`.  -> eng"""
+    for part in algo._hip_parts():
+        if part.old is not None:
+            setattr(eng, part.name + "_old", part.from_torch([p.detach() for p in params_by_keys(part.old, part.keys)]))
+        ms, vs, step = adam_state(part.optim._optim, params_by_keys(part.module, part.keys))
+        setattr(eng, part.name + "_m", part.from_torch(ms))
+        setattr(eng, part.name + "_v", part.from_torch(vs))
+        if part.load_step:
+            setattr(eng, part.step, max(getattr(eng, part.step), step))
+    if getattr(eng.cfg, "auto_alpha", False):
+        st = algo.alpha._optim.state.get(algo.alpha._log_alpha, {})
+        if "exp_avg" in st:
+            eng.log_alpha_m[0], eng.log_alpha_v[0] = float(st["exp_avg"]), float(st["exp_avg_sq"])
+    return eng
+
+
+def _ac_write_back(algo) -> None:
+    """`_hip_write_back` of the actor-critic classes: engine parameters, lagged parameters, log alpha and Adam state -> the torch
+    modules and torch.optim, every parameter through `_hip_put` (which leaves out what somebody else has written).  An optimizer
+    that has not stepped yet (REDQ's delayed actor) gets no state; log alpha's optimizer steps with the actor's."""
+    eng = algo.__dict__.get("_hip_engine_obj")
+    if eng is None:
+        return
+    parts, put = algo._hip_parts(), algo._hip_put
+    # the parameter lists, looked up once per engine (`params_by_keys` walks the module tree: six walks per TD3 write-back)
+    cache = algo.__dict__.get("_hip_ac_params")
+    if cache is None or cache[0] is not eng:
+        cache = algo.__dict__["_hip_ac_params"] = (eng, [(params_by_keys(part.module, part.keys),
+                                                            () if part.old is None else params_by_keys(part.old, part.keys)) for part in parts])
+    with torch.no_grad():
+        for part, (params, old) in zip(parts, cache[1]):
+            for p, t in zip(params, part.to_torch(getattr(eng, part.name))):
+                put(p, t)
+            if part.old is not None:
+                for p, t in zip(old, part.to_torch(getattr(eng, part.name + "_old"))):
+                    put(p, t)
+            step = getattr(eng, part.step)
+            if step:
+                store_adam_state(part.optim._optim, params, part.to_torch(getattr(eng, part.name + "_m")),
+                                 part.to_torch(getattr(eng, part.name + "_v")), step)
+        if getattr(eng.cfg, "auto_alpha", False):
+            put(algo.alpha._log_alpha, eng.log_alpha[0])
+            step = getattr(eng, parts[0].step)
+            if step:
+                store_adam_state(algo.alpha._optim, [algo.alpha._log_alpha], [eng.log_alpha_m[0]], [eng.log_alpha_v[0]], step)
+
+
 def _dqn_config(algo):
     from . import dqn as D
 
@@ -1828,28 +1957,12 @@ def make_hip_sac(ref=None):
             self._hip_update_noise, self._hip_host_batch, self._hip_noise_calls = update_noise, bool(host_batch), 0
             self._hip_noise_key = int(torch.initial_seed() % (2**31 - 1)) if noise_seed is None else int(noise_seed)
             self._hip_device = torch.device(device)
-            sa, sc = self.policy.actor.state_dict(), self.critic.state_dict()
-            depth = S.keys_depth(sa.keys(), ("mu", "sigma"))
-            if depth is None or any(S.keys_depth(c.state_dict().keys(), ("last",)) != depth for c in (self.critic, self.critic2)):
-                raise NotImplementedError("HipSAC: networks must be those of examples/mujoco/mujoco_sac.py (Net trunks of one depth, "
-                                          "1 .. 6 hidden layers, single-Linear mu / sigma / Q heads)")
-            self._hip_depth, self._hip_akeys, self._hip_ckeys = depth, S.actor_keys(depth), S.critic_keys(depth)
-            self._hip_actfn = _trunk_activation((self.policy.actor, self.critic, self.critic2), "HipSAC")
+            keys = _ac_nets(self, "HipSAC", "networks must be those of examples/mujoco/mujoco_sac.py (Net trunks of one depth, "
+                            "1 .. 6 hidden layers, single-Linear mu / sigma / Q heads)",
+                            (("actor", self.policy.actor, S.actor_keys), ("critic1", self.critic, S.critic_keys),
+                             ("critic2", self.critic2, S.critic_keys)), (self.policy_optim, self.critic_optim, self.critic2_optim))
+            self._hip_akeys, self._hip_ckeys = keys["actor"], keys["critic1"]
             self._hip_bound = _actor_bound(self.policy.actor)
-            # any hidden widths per network (round 6): embedded by zero padding into the engine's Net[h] * depth, h = the largest
-            # width of the three networks rounded up to 32 (tianshou_amd.widths)
-            from . import widths as WD
-
-            lists = {"actor": [sa[k] for k in self._hip_akeys], "critic1": [sc[k] for k in self._hip_ckeys],
-                     "critic2": [self.critic2.state_dict()[k] for k in self._hip_ckeys]}
-            try:
-                self._hip_sizes = {n: WD.layer_widths(t, 2 if n == "actor" else 1) for n, t in lists.items()}
-                hid = WD.engine_hidden(self._hip_sizes.values())
-            except NotImplementedError as e:
-                raise NotImplementedError(f"HipSAC: hidden layers of widths up to 1024 per network ({e})") from None
-            self._hip_hidden = hid
-            for o in (self.policy_optim, self.critic_optim, self.critic2_optim):
-                _adam_of(o)
             self._hip_engine = None
             self._hip_glue_init()
             self._hip_dp_setup(data_parallel, group, allreduce, shard_buffer=False)
@@ -1859,8 +1972,8 @@ def make_hip_sac(ref=None):
                 from . import policy as HP
 
                 HP.attach(self.policy, "sac", self, device=str(self._hip_device), sampling=sampling, noise_seed=noise_seed,
-                          obs_dim=int(sa[self._hip_akeys[0]].shape[1]), act_dim=int(sa[self._hip_akeys[2 * self._hip_depth]].shape[0]),
-                          hidden=hid, depth=depth, max_action=self._hip_bound, activation=self._hip_actfn)
+                          obs_dim=self._hip_obs_dim, act_dim=self._hip_act_dim, hidden=self._hip_hidden, depth=self._hip_depth,
+                          max_action=self._hip_bound, activation=self._hip_actfn)
             self._hip_set_write_back(write_back, attached=policy_forward == "hip")
 
         def update(self, buffer, sample_size):
@@ -1891,55 +2004,28 @@ def make_hip_sac(ref=None):
 
         def _engine(self):
             if self._hip_engine is None:
-                sa = self.policy.actor.state_dict()
-                obs_dim = sa[self._hip_akeys[0]].shape[1]
-                act_dim = sa[self._hip_akeys[2 * self._hip_depth]].shape[0]
-                auto = isinstance(self.alpha, AutoAlpha)
-                ga, gc = _adam_of(self.policy_optim)[1], _adam_of(self.critic_optim)[1]
-                cfg = S.SACConfig(gamma=self.gamma, tau=self.tau, n_step=self.n_step_return_horizon,
-                                  alpha=0.0 if auto else float(self.alpha.value), auto_alpha=auto,
-                                  target_entropy=float(self.alpha._target_entropy) if auto else 0.0,
-                                  log_alpha0=float(self.alpha._log_alpha.item()) if auto else 0.0,
-                                  actor_lr=ga["lr"], critic_lr=gc["lr"],
-                                  alpha_lr=self.alpha._optim.param_groups[0]["lr"] if auto else 0.0,
-                                  betas=tuple(ga["betas"]), adam_eps=ga["eps"])
-                dev = self._hip_device
-                hid = self._hip_hidden
-                flat_c = lambda mod: S.critic_flat_from_torch(  # noqa: E731
-                    [mod.state_dict()[k] for k in self._hip_ckeys], obs_dim, act_dim, dev, hidden=hid)
-                eng = self._hip_engine = S.SACEngine(
-                    obs_dim, act_dim,
-                    S.actor_flat_from_torch([sa[k] for k in self._hip_akeys], obs_dim, act_dim, dev, hidden=hid),
-                    flat_c(self.critic), flat_c(self.critic2), cfg, hidden=self._hip_hidden, depth=self._hip_depth,
-                    max_action=self._hip_bound, activation=self._hip_actfn)
-                # resume: lagged critics, Adam moments / steps of a loaded checkpoint
-                eng.critic1_old, eng.critic2_old = flat_c(self.critic_old.module), flat_c(self.critic2_old.module)
-                for name, mod, optim, keys, conv in self._hip_parts(S):
-                    ms, vs, step = adam_state(optim._optim, params_by_keys(mod, keys))
-                    setattr(eng, name + "_m", conv(ms, obs_dim, act_dim, dev))
-                    setattr(eng, name + "_v", conv(vs, obs_dim, act_dim, dev))
-                    eng.adam_step = max(eng.adam_step, step)
-                if auto:
-                    st = self.alpha._optim.state.get(self.alpha._log_alpha, {})
-                    if "exp_avg" in st:
-                        eng.log_alpha_m[0], eng.log_alpha_v[0] = float(st["exp_avg"]), float(st["exp_avg_sq"])
+                flats = {p.name: p.flat() for p in self._hip_parts()}
+                eng = S.SACEngine(self._hip_obs_dim, self._hip_act_dim, flats["actor"], flats["critic1"], flats["critic2"],
+                                  S.SACConfig(**_ac_config_fields(self), **_ac_entropy_fields(self, AutoAlpha)),
+                                  hidden=self._hip_hidden, depth=self._hip_depth, max_action=self._hip_bound, activation=self._hip_actfn)
+                self._hip_engine = _ac_load(self, eng)     # resume: lagged critics, Adam moments / steps of a loaded checkpoint
             return self._hip_engine
 
-        def _hip_parts(self, S):
-            import functools
+        def _hip_parts(self):
+            o, a, h, dev, sz = self._hip_obs_dim, self._hip_act_dim, self._hip_hidden, self._hip_device, self._hip_sizes
 
-            fa = functools.partial(S.actor_flat_from_torch, hidden=self._hip_hidden)
-            fc = functools.partial(S.critic_flat_from_torch, hidden=self._hip_hidden)
-            return (("actor", self.policy.actor, self.policy_optim, self._hip_akeys, fa),
-                    ("critic1", self.critic, self.critic_optim, self._hip_ckeys, fc),
-                    ("critic2", self.critic2, self.critic2_optim, self._hip_ckeys, fc))
+            def part(name, mod, old, optim, keys, fwd, back):
+                return _ACPart(name, mod, old, optim, keys, lambda t: fwd(t, o, a, dev, hidden=h),
+                               lambda f: back(f, o, a, h, sizes=sz[name]), "adam_step", True)
+
+            return (part("actor", self.policy.actor, None, self.policy_optim, self._hip_akeys, S.actor_flat_from_torch, S.actor_flat_to_torch),
+                    part("critic1", self.critic, self.critic_old.module, self.critic_optim, self._hip_ckeys,
+                         S.critic_flat_from_torch, S.critic_flat_to_torch),
+                    part("critic2", self.critic2, self.critic2_old.module, self.critic2_optim, self._hip_ckeys,
+                         S.critic_flat_from_torch, S.critic_flat_to_torch))
 
         def _preprocess_batch(self, batch, buffer, indices):
-            _require_gpu(self._hip_device, "HipSAC")
-            eng = self._engine()
-            m = _mirror(self, buffer, self._hip_device)
-            idx = torch.as_tensor(np.asarray(indices, np.int64), device=self._hip_device)
-            self._hip_idx = idx
+            eng, m, idx = _ac_begin(self, "HipSAC", buffer, indices)
             # Inside HipSAC.update()'s own sequence (`_hip_offpolicy_update`: nobody reads the batch between the two hooks) an
             # n_step = 1 update with the engine's noise is ONE library call, made by `_update_with_batch` (ts_sac_learn_rows: the
             # target pass in front of the update, 16 launches instead of 22); `batch.returns` is attached there.  Called on its own
@@ -1984,30 +2070,7 @@ def make_hip_sac(ref=None):
             return SACTrainingStats(actor_loss=float(s[0]), critic1_loss=float(s[1]), critic2_loss=float(s[2]),
                                     alpha=float(s[3]), alpha_loss=float(s[4]) if auto else None)
 
-        def _hip_write_back(self) -> None:
-            eng = self.__dict__.get("_hip_engine_obj")
-            if eng is None:
-                return
-            with torch.no_grad():
-                sz = self._hip_sizes
-                for mod, flat, conv, name in ((self.policy.actor, eng.actor, S.actor_flat_to_torch, "actor"),
-                                              (self.critic, eng.critic1, S.critic_flat_to_torch, "critic1"),
-                                              (self.critic2, eng.critic2, S.critic_flat_to_torch, "critic2"),
-                                              (self.critic_old.module, eng.critic1_old, S.critic_flat_to_torch, "critic1"),
-                                              (self.critic2_old.module, eng.critic2_old, S.critic_flat_to_torch, "critic2")):
-                    for p, t in zip(mod.parameters(), conv(flat, eng.obs_dim, eng.act_dim, eng.hidden, sizes=sz[name])):
-                        self._hip_put(p, t)
-                if eng.cfg.auto_alpha:
-                    self._hip_put(self.alpha._log_alpha, eng.log_alpha[0])
-            back = {"actor": S.actor_flat_to_torch, "critic1": S.critic_flat_to_torch, "critic2": S.critic_flat_to_torch}
-            for name, mod, optim, keys, _ in self._hip_parts(S):
-                store_adam_state(optim._optim, params_by_keys(mod, keys),
-                                 back[name](getattr(eng, name + "_m"), eng.obs_dim, eng.act_dim, eng.hidden, sizes=self._hip_sizes[name]),
-                                 back[name](getattr(eng, name + "_v"), eng.obs_dim, eng.act_dim, eng.hidden, sizes=self._hip_sizes[name]),
-                                 eng.adam_step)
-            if eng.cfg.auto_alpha:
-                store_adam_state(self.alpha._optim, [self.alpha._log_alpha], [eng.log_alpha_m[0]],
-                                 [eng.log_alpha_v[0]], eng.adam_step)
+        _hip_write_back = _ac_write_back
 
     return HipSAC
 
@@ -2035,78 +2098,50 @@ def make_hip_redq(ref=None):
         def __init__(self, *args, device="cuda", **kwargs):
             super().__init__(*args, **kwargs)
             self._hip_device = torch.device(device)
-            sa, sc = self.policy.actor.state_dict(), self.critic.state_dict()
-            depth = S.keys_depth(sa.keys(), ("mu", "sigma"))
-            if depth is None or RQ.keys_depth(sc.keys()) != depth:
-                raise NotImplementedError("HipREDQ: networks must be those of test/continuous/test_redq.py (SAC's actor; a critic of "
-                                          "EnsembleLinear layers; trunks of one depth, 1 .. 6 hidden layers)")
-            self._hip_depth, self._hip_akeys, self._hip_ckeys = depth, S.actor_keys(depth), RQ.critic_keys(depth)
-            self._hip_actfn = _trunk_activation((self.policy.actor, self.critic), "HipREDQ")
-            self._hip_bound = _actor_bound(self.policy.actor)
-            from . import widths as WD
 
-            try:        # any hidden widths (round 6): embedded by zero padding (tianshou_amd.widths)
-                cw = [sc[k] for k in self._hip_ckeys[:2 * depth:2]]          # EnsembleLinear weights [E, in, out]
+            def ensemble_widths(t):                                   # EnsembleLinear weights [E, in, out]
+                cw = t[:-2:2]
                 if any(w.dim() != 3 or w.shape[0] != self.ensemble_size or (i > 0 and w.shape[1] != cw[i - 1].shape[2]) for i, w in enumerate(cw)):
                     raise NotImplementedError("EnsembleLinear weights [ensemble_size, in, out] are required")
-                self._hip_sizes = {"actor": WD.layer_widths([sa[k] for k in self._hip_akeys], 2),
-                                   "critic": tuple(int(w.shape[2]) for w in cw)}
-                hid = WD.engine_hidden(self._hip_sizes.values())
-            except NotImplementedError as e:
-                raise NotImplementedError(f"HipREDQ: hidden layers of widths up to 1024 per network ({e})") from None
-            self._hip_hidden = hid
-            for o in (self.policy_optim, self.critic_optim):
-                _adam_of(o)
+                return tuple(int(w.shape[2]) for w in cw)
+
+            keys = _ac_nets(self, "HipREDQ", "networks must be those of test/continuous/test_redq.py (SAC's actor; a critic of "
+                            "EnsembleLinear layers; trunks of one depth, 1 .. 6 hidden layers)",
+                            (("actor", self.policy.actor, S.actor_keys), ("critic", self.critic, RQ.critic_keys)),
+                            (self.policy_optim, self.critic_optim), widths={"critic": ensemble_widths})
+            self._hip_akeys, self._hip_ckeys = keys["actor"], keys["critic"]
+            self._hip_bound = _actor_bound(self.policy.actor)
             self._hip_engine = None
             self._hip_glue_init()
 
-        def _critic_tensors(self, mod):
-            return [mod.state_dict()[k] for k in self._hip_ckeys]
+        def _hip_parts(self):
+            o, a, h, dev, sz = self._hip_obs_dim, self._hip_act_dim, self._hip_hidden, self._hip_device, self._hip_sizes
+            E = self.ensemble_size
+            return (_ACPart("actor", self.policy.actor, None, self.policy_optim, self._hip_akeys,
+                            lambda t: S.actor_flat_from_torch(t, o, a, dev, hidden=h),
+                            lambda f: S.actor_flat_to_torch(f, o, a, h, sizes=sz["actor"]), "actor_steps", True),
+                    _ACPart("critics", self.critic, self.critic_old.module, self.critic_optim, self._hip_ckeys,
+                            lambda t: RQ.ensemble_flat_from_torch(t, o, a, dev, hidden=h),
+                            lambda f: RQ.ensemble_flat_to_torch(f, E, o, a, h, sizes=sz["critic"]), "critic_gradient_step", False))
 
         def _engine(self):
             if self._hip_engine is None:
-                sa = self.policy.actor.state_dict()
-                obs_dim, act_dim = sa[self._hip_akeys[0]].shape[1], sa[self._hip_akeys[2 * self._hip_depth]].shape[0]
-                auto = isinstance(self.alpha, AutoAlpha)
-                ga, gc = _adam_of(self.policy_optim)[1], _adam_of(self.critic_optim)[1]
-                cfg = RQ.REDQConfig(gamma=self.gamma, tau=self.tau, n_step=self.n_step_return_horizon,
-                                    alpha=0.0 if auto else float(self.alpha.value), auto_alpha=auto,
-                                    target_entropy=float(self.alpha._target_entropy) if auto else 0.0,
-                                    log_alpha0=float(self.alpha._log_alpha.item()) if auto else 0.0,
-                                    actor_lr=ga["lr"], critic_lr=gc["lr"],
-                                    alpha_lr=self.alpha._optim.param_groups[0]["lr"] if auto else 0.0,
-                                    betas=tuple(ga["betas"]), adam_eps=ga["eps"], ensemble_size=self.ensemble_size,
+                cfg = RQ.REDQConfig(**_ac_config_fields(self), **_ac_entropy_fields(self, AutoAlpha), ensemble_size=self.ensemble_size,
                                     subset_size=self.subset_size, actor_delay=self.actor_delay, target_mode=self.target_mode)
-                dev = self._hip_device
-                hid = self._hip_hidden
-                eng = self._hip_engine = RQ.REDQEngine(
-                    obs_dim, act_dim, S.actor_flat_from_torch([sa[k] for k in self._hip_akeys], obs_dim, act_dim, dev, hidden=hid),
-                    RQ.ensemble_flat_from_torch(self._critic_tensors(self.critic), obs_dim, act_dim, dev, hidden=hid), cfg,
-                    hidden=self._hip_hidden, depth=self._hip_depth, max_action=self._hip_bound, activation=self._hip_actfn)
-                # resume: lagged ensemble, counters, Adam moments / steps of a loaded checkpoint
-                eng.critics_old = RQ.ensemble_flat_from_torch(self._critic_tensors(self.critic_old.module), obs_dim, act_dim, dev, hidden=hid)
+                flats = {p.name: p.flat() for p in self._hip_parts()}
+                eng = RQ.REDQEngine(self._hip_obs_dim, self._hip_act_dim, flats["actor"], flats["critics"], cfg, hidden=self._hip_hidden,
+                                    depth=self._hip_depth, max_action=self._hip_bound, activation=self._hip_actfn)
+                # resume: the counters the reference keeps on the algorithm, then lagged ensemble, Adam moments / actor steps
                 eng.critic_gradient_step = int(self.critic_gradient_step)
-                ms, vs, step = adam_state(self.policy_optim._optim, params_by_keys(self.policy.actor, self._hip_akeys))
-                eng.actor_m, eng.actor_v = (S.actor_flat_from_torch(x, obs_dim, act_dim, dev, hidden=hid) for x in (ms, vs))
-                eng.actor_steps = step
-                ms, vs, _ = adam_state(self.critic_optim._optim, params_by_keys(self.critic, self._hip_ckeys))
-                eng.critics_m, eng.critics_v = (RQ.ensemble_flat_from_torch(x, obs_dim, act_dim, dev, hidden=hid) for x in (ms, vs))
                 eng._stats[0] = float(self._last_actor_loss)
-                if auto:
-                    st = self.alpha._optim.state.get(self.alpha._log_alpha, {})
-                    if "exp_avg" in st:
-                        eng.log_alpha_m[0], eng.log_alpha_v[0] = float(st["exp_avg"]), float(st["exp_avg_sq"])
+                self._hip_engine = _ac_load(self, eng)
             return self._hip_engine
 
         def _preprocess_batch(self, batch, buffer, indices):
-            _require_gpu(self._hip_device, "HipREDQ")
-            eng = self._engine()
-            m = _mirror(self, buffer, self._hip_device)
-            idx = torch.as_tensor(np.asarray(indices, np.int64), device=self._hip_device)
+            eng, m, idx = _ac_begin(self, "HipREDQ", buffer, indices)
             noise = torch.randn(len(indices), eng.act_dim)                  # Normal.rsample of the target policy call
             subset = np.random.choice(self.ensemble_size, self.subset_size, replace=False)     # redq.py:252
             batch.returns = eng.preprocess(m, idx, noise, subset).reshape(-1, 1)
-            self._hip_idx = idx
             return batch
 
         def _update_with_batch(self, batch):
@@ -2123,31 +2158,11 @@ def make_hip_redq(ref=None):
             s = stats.cpu().numpy()                                               # one D2H per update()
             self.critic_gradient_step = eng.critic_gradient_step
             self._last_actor_loss = float(s[0])
-            dims = (eng.obs_dim, eng.act_dim, eng.hidden)
-            E = eng.cfg.ensemble_size
-            with torch.no_grad():
-                sa_, sc_ = self._hip_sizes["actor"], self._hip_sizes["critic"]
-                for p, t in zip(params_by_keys(self.policy.actor, self._hip_akeys), S.actor_flat_to_torch(eng.actor, *dims, sizes=sa_)):
-                    p.copy_(t)
-                for mod, flat in ((self.critic, eng.critics), (self.critic_old.module, eng.critics_old)):
-                    for p, t in zip(params_by_keys(mod, self._hip_ckeys), RQ.ensemble_flat_to_torch(flat, E, *dims, sizes=sc_)):
-                        p.copy_(t)
-                if eng.cfg.auto_alpha:
-                    self.alpha._log_alpha.copy_(eng.log_alpha[0])
-            store_adam_state(self.critic_optim._optim, params_by_keys(self.critic, self._hip_ckeys),
-                             RQ.ensemble_flat_to_torch(eng.critics_m, E, *dims, sizes=self._hip_sizes["critic"]),
-                             RQ.ensemble_flat_to_torch(eng.critics_v, E, *dims, sizes=self._hip_sizes["critic"]),
-                             eng.critic_gradient_step)
-            if eng.actor_steps:
-                store_adam_state(self.policy_optim._optim, params_by_keys(self.policy.actor, self._hip_akeys),
-                                 S.actor_flat_to_torch(eng.actor_m, *dims, sizes=self._hip_sizes["actor"]),
-                                 S.actor_flat_to_torch(eng.actor_v, *dims, sizes=self._hip_sizes["actor"]),
-                                 eng.actor_steps)
-                if eng.cfg.auto_alpha:
-                    store_adam_state(self.alpha._optim, [self.alpha._log_alpha], [eng.log_alpha_m[0]], [eng.log_alpha_v[0]],
-                                     eng.actor_steps)
+            self._hip_after_update()
             return REDQTrainingStats(actor_loss=float(s[0]), critic_loss=float(s[1]), alpha=float(s[2]),
                                      alpha_loss=None if np.isnan(s[3]) else float(s[3]))
+
+        _hip_write_back = _ac_write_back
 
     return HipREDQ
 
@@ -2179,65 +2194,36 @@ def make_hip_discrete_sac(ref=None):
             super().__init__(*args, **kwargs)
             self._hip_device = torch.device(device)
             self._hip_match_rng = match_rng_stream
-            mods = (self.policy.actor, self.critic, self.critic2)
-            depth = DS.keys_depth(mods[0].state_dict().keys(), ("last",))
-            if depth is None or any(DS.keys_depth(m.state_dict().keys(), ("last",)) != depth for m in mods):
-                raise NotImplementedError("HipDiscreteSAC: networks must be Net(obs, [h, ...]) of one depth (1 .. 6 hidden layers) + a "
-                                          "single Linear head")
-            self._hip_depth, self._hip_keys = depth, DS.net_keys(depth)
-            self._hip_actfn = _trunk_activation(mods, "HipDiscreteSAC")
-            sa = self.policy.actor.state_dict()
-            from . import widths as WD
-
-            lists = {n: [m.state_dict()[k] for k in self._hip_keys] for n, m in zip(("actor", "critic1", "critic2"), mods)}
-            try:        # any hidden widths per network (round 6): embedded by zero padding (tianshou_amd.widths)
-                self._hip_sizes = {n: WD.layer_widths(t, 1) for n, t in lists.items()}
-                self._hip_hidden = WD.engine_hidden(self._hip_sizes.values())
-            except NotImplementedError as e:
-                raise NotImplementedError(f"HipDiscreteSAC: hidden layers of widths up to 1024 per network ({e})") from None
-            if not 2 <= sa[self._hip_keys[2 * self._hip_depth]].shape[0] <= 64:
+            keys = _ac_nets(self, "HipDiscreteSAC", "networks must be Net(obs, [h, ...]) of one depth (1 .. 6 hidden layers) + a "
+                            "single Linear head",
+                            (("actor", self.policy.actor, DS.net_keys), ("critic1", self.critic, DS.net_keys),
+                             ("critic2", self.critic2, DS.net_keys)), (self.policy_optim, self.critic_optim, self.critic2_optim))
+            self._hip_keys = keys["actor"]
+            if not 2 <= self._hip_act_dim <= 64:
                 raise NotImplementedError("HipDiscreteSAC: 2..64 actions")
             if getattr(self.policy.actor, "softmax_output", False):
                 raise NotImplementedError("HipDiscreteSAC: the actor must output logits (softmax_output=False)")
-            for o in (self.policy_optim, self.critic_optim, self.critic2_optim):
-                _adam_of(o)
             self._hip_engine = None
             self._hip_glue_init()
 
         def _hip_parts(self):
-            return (("actor", self.policy.actor, self.policy_optim), ("critic1", self.critic, self.critic_optim),
-                    ("critic2", self.critic2, self.critic2_optim))
+            o, n, h, dev, sz = self._hip_obs_dim, self._hip_act_dim, self._hip_hidden, self._hip_device, self._hip_sizes
+
+            def part(name, mod, old, optim):
+                return _ACPart(name, mod, old, optim, self._hip_keys, lambda t: DS.net_flat_from_torch(t, o, n, h, dev),
+                               lambda f: DS.net_flat_to_torch(f, o, n, h, sizes=sz[name]), "adam_step", True)
+
+            return (part("actor", self.policy.actor, None, self.policy_optim),
+                    part("critic1", self.critic, self.critic_old.module, self.critic_optim),
+                    part("critic2", self.critic2, self.critic2_old.module, self.critic2_optim))
 
         def _engine(self):
             if self._hip_engine is None:
-                sa = self.policy.actor.state_dict()
-                obs_dim = sa[self._hip_keys[0]].shape[1]
-                n_act = sa[self._hip_keys[2 * self._hip_depth]].shape[0]
-                dims = (obs_dim, n_act, self._hip_hidden)
-                auto = isinstance(self.alpha, AutoAlpha)
-                ga, gc = _adam_of(self.policy_optim)[1], _adam_of(self.critic_optim)[1]
-                cfg = SACConfig(gamma=self.gamma, tau=self.tau, n_step=self.n_step_return_horizon,
-                                alpha=0.0 if auto else float(self.alpha.value), auto_alpha=auto,
-                                target_entropy=float(self.alpha._target_entropy) if auto else 0.0,
-                                log_alpha0=float(self.alpha._log_alpha.item()) if auto else 0.0,
-                                actor_lr=ga["lr"], critic_lr=gc["lr"],
-                                alpha_lr=self.alpha._optim.param_groups[0]["lr"] if auto else 0.0,
-                                betas=tuple(ga["betas"]), adam_eps=ga["eps"])
-                dev = self._hip_device
-                flat = lambda mod: DS.net_flat_from_torch(  # noqa: E731
-                    [mod.state_dict()[k] for k in self._hip_keys], *dims, dev)
-                eng = self._hip_engine = DS.DiscreteSACEngine(*dims, flat(self.policy.actor), flat(self.critic),
-                                                              flat(self.critic2), cfg, depth=self._hip_depth, activation=self._hip_actfn)
-                eng.critic1_old, eng.critic2_old = flat(self.critic_old.module), flat(self.critic2_old.module)
-                for name, mod, optim in self._hip_parts():             # resume from a loaded checkpoint
-                    ms, vs, step = adam_state(optim._optim, params_by_keys(mod, self._hip_keys))
-                    setattr(eng, name + "_m", DS.net_flat_from_torch(ms, *dims, dev))
-                    setattr(eng, name + "_v", DS.net_flat_from_torch(vs, *dims, dev))
-                    eng.adam_step = max(eng.adam_step, step)
-                if auto:
-                    st = self.alpha._optim.state.get(self.alpha._log_alpha, {})
-                    if "exp_avg" in st:
-                        eng.log_alpha_m[0], eng.log_alpha_v[0] = float(st["exp_avg"]), float(st["exp_avg_sq"])
+                flats = {p.name: p.flat() for p in self._hip_parts()}
+                eng = DS.DiscreteSACEngine(self._hip_obs_dim, self._hip_act_dim, self._hip_hidden, flats["actor"], flats["critic1"],
+                                           flats["critic2"], SACConfig(**_ac_config_fields(self), **_ac_entropy_fields(self, AutoAlpha)),
+                                           depth=self._hip_depth, activation=self._hip_actfn)
+                self._hip_engine = _ac_load(self, eng)                 # resume from a loaded checkpoint
             return self._hip_engine
 
         def _hip_draw(self, obs):
@@ -2247,16 +2233,12 @@ def make_hip_discrete_sac(ref=None):
         def _preprocess_batch(self, batch, buffer, indices):
             from .buffer import gather_rows
 
-            _require_gpu(self._hip_device, "HipDiscreteSAC")
-            eng = self._engine()
-            m = _mirror(self, buffer, self._hip_device)
-            idx = torch.as_tensor(np.asarray(indices, np.int64), device=self._hip_device)
+            eng, m, idx = _ac_begin(self, "HipDiscreteSAC", buffer, indices)
             if self._hip_match_rng:
                 from .returns import nstep_indices
 
                 self._hip_draw(gather_rows(m.obs_next, nstep_indices(m, idx, eng.cfg.n_step)))
             batch.returns = eng.preprocess(m, idx).reshape(-1, 1)
-            self._hip_idx = idx
             return batch
 
         def _update_with_batch(self, batch):
@@ -2270,26 +2252,12 @@ def make_hip_discrete_sac(ref=None):
             stats, w = eng.update_with_batch(obs, gather_rows(m.act, self._hip_idx), batch.returns.reshape(-1), weight)
             batch.weight = w                                                      # prio-buffer, discrete_sac.py:174
             s = stats.cpu().numpy()                                               # one D2H per update()
-            dims = (eng.obs_dim, eng.n_act, eng.hidden)
-            with torch.no_grad():
-                sz = self._hip_sizes
-                for mod, flat, nm in ((self.policy.actor, eng.actor, "actor"), (self.critic, eng.critic1, "critic1"),
-                                      (self.critic2, eng.critic2, "critic2"), (self.critic_old.module, eng.critic1_old, "critic1"),
-                                      (self.critic2_old.module, eng.critic2_old, "critic2")):
-                    for p, t in zip(params_by_keys(mod, self._hip_keys), DS.net_flat_to_torch(flat, *dims, sizes=sz[nm])):
-                        p.copy_(t)
-                if eng.cfg.auto_alpha:
-                    self.alpha._log_alpha.copy_(eng.log_alpha[0])
-            for name, mod, optim in self._hip_parts():
-                store_adam_state(optim._optim, params_by_keys(mod, self._hip_keys),
-                                 DS.net_flat_to_torch(getattr(eng, name + "_m"), *dims, sizes=self._hip_sizes[name]),
-                                 DS.net_flat_to_torch(getattr(eng, name + "_v"), *dims, sizes=self._hip_sizes[name]), eng.adam_step)
-            if eng.cfg.auto_alpha:
-                store_adam_state(self.alpha._optim, [self.alpha._log_alpha], [eng.log_alpha_m[0]],
-                                 [eng.log_alpha_v[0]], eng.adam_step)
+            self._hip_after_update()
             auto = eng.cfg.auto_alpha
             return DiscreteSACTrainingStats(actor_loss=float(s[0]), critic1_loss=float(s[1]), critic2_loss=float(s[2]),
                                             alpha=float(s[3]), alpha_loss=float(s[4]) if auto else None)
+
+        _hip_write_back = _ac_write_back
 
     return HipDiscreteSAC
 
@@ -2494,79 +2462,50 @@ def _make_hip_det(twin: bool, ref=None, bc: bool = False):
         def __init__(self, *args, device="cuda", **kwargs):
             super().__init__(*args, **kwargs)
             self._hip_device = torch.device(device)
-            sa = self.policy.actor.state_dict()
-            critics = [self.critic] + ([self.critic2] if twin else [])
-            depth = T.keys_depth(sa.keys(), ("last",))
-            if depth is None or any(T.keys_depth(c.state_dict().keys(), ("last",)) != depth for c in critics):
-                raise NotImplementedError("HipTD3 / HipDDPG: networks must be those of examples/mujoco/mujoco_td3.py (Net trunks of "
-                                          "one depth, 1 .. 6 hidden layers, single-Linear action / Q heads)")
-            self._hip_depth, self._hip_akeys, self._hip_ckeys = depth, T.actor_keys(depth), T.critic_keys(depth)
-            self._hip_actfn = _trunk_activation([self.policy.actor] + critics, "HipTD3 / HipDDPG")
-            # any hidden widths per network, e.g. the [400, 300] of the TD3 / DDPG papers (round 6, tianshou_amd.widths)
-            from . import widths as WD
-
-            lists = {"actor": [sa[k] for k in self._hip_akeys]}
-            for i, c in enumerate(critics):
-                lists[f"critic{i + 1}"] = [c.state_dict()[k] for k in self._hip_ckeys]
-            try:
-                self._hip_sizes = {n: WD.layer_widths(t, 1) for n, t in lists.items()}
-                hid = WD.engine_hidden(self._hip_sizes.values())
-            except NotImplementedError as e:
-                raise NotImplementedError(f"HipTD3 / HipDDPG: hidden layers of widths up to 1024 per network ({e})") from None
-            self._hip_hidden = hid
-            for o in [self.policy_optim, self.critic_optim] + ([self.critic2_optim] if twin else []):
-                _adam_of(o)
+            nets = [("actor", self.policy.actor, T.actor_keys), ("critic1", self.critic, T.critic_keys)]
+            keys = _ac_nets(self, "HipTD3 / HipDDPG", "networks must be those of examples/mujoco/mujoco_td3.py (Net trunks of "
+                            "one depth, 1 .. 6 hidden layers, single-Linear action / Q heads)",
+                            nets + ([("critic2", self.critic2, T.critic_keys)] if twin else []),
+                            [self.policy_optim, self.critic_optim] + ([self.critic2_optim] if twin else []))
+            self._hip_akeys, self._hip_ckeys = keys["actor"], keys["critic1"]
             self._hip_engine = None
             self._hip_glue_init()
 
         def _hip_parts(self):
-            import functools
+            o, a, h, dev, sz = self._hip_obs_dim, self._hip_act_dim, self._hip_hidden, self._hip_device, self._hip_sizes
 
-            P, hid, sz = functools.partial, self._hip_hidden, self._hip_sizes
-            parts = [("actor", self.policy.actor, self.policy_optim, self._hip_akeys, P(T.actor_flat_from_torch, hidden=hid),
-                      P(T.actor_flat_to_torch, sizes=sz["actor"]), self.actor_old.module),
-                     ("critic1", self.critic, self.critic_optim, self._hip_ckeys, P(T.critic_flat_from_torch, hidden=hid),
-                      P(T.critic_flat_to_torch, sizes=sz["critic1"]), self.critic_old.module)]
+            def part(name, mod, old, optim):
+                # (the critics' step count is TD3's `_cnt`, which the algorithm keeps: `_engine` sets it, no optimizer is asked)
+                actor = name == "actor"
+                keys, fwd, back = ((self._hip_akeys, T.actor_flat_from_torch, T.actor_flat_to_torch) if actor else
+                                   (self._hip_ckeys, T.critic_flat_from_torch, T.critic_flat_to_torch))
+                return _ACPart(name, mod, old.module, optim, keys, lambda t: fwd(t, o, a, dev, hidden=h),
+                               lambda f: back(f, o, a, h, sizes=sz[name]), "actor_steps" if actor else "cnt", actor)
+
+            parts = [part("actor", self.policy.actor, self.actor_old, self.policy_optim),
+                     part("critic1", self.critic, self.critic_old, self.critic_optim)]
             if twin:
-                parts.append(("critic2", self.critic2, self.critic2_optim, self._hip_ckeys, P(T.critic_flat_from_torch, hidden=hid),
-                              P(T.critic_flat_to_torch, sizes=sz["critic2"]), self.critic2_old.module))
+                parts.append(part("critic2", self.critic2, self.critic2_old, self.critic2_optim))
             return parts
 
         def _engine(self):
             if self._hip_engine is None:
-                sa = self.policy.actor.state_dict()
-                obs_dim, act_dim = sa[self._hip_akeys[0]].shape[1], sa[self._hip_akeys[2 * self._hip_depth]].shape[0]
-                ga, gc = _adam_of(self.policy_optim)[1], _adam_of(self.critic_optim)[1]
                 Config, Engine = (TB.TD3BCConfig, TB.TD3BCEngine) if bc else (T.TD3Config, T.TD3Engine)
-                cfg = Config(gamma=self.gamma, tau=self.tau, n_step=self.n_step_return_horizon, twin=twin,
+                cfg = Config(**_ac_config_fields(self), twin=twin,
                              policy_noise=getattr(self, "policy_noise", 0.0), noise_clip=getattr(self, "noise_clip", 0.0),
                              update_actor_freq=getattr(self, "update_actor_freq", 1),
-                             max_action=float(self.policy.actor.max_action), actor_lr=ga["lr"], critic_lr=gc["lr"],
-                             betas=tuple(ga["betas"]), adam_eps=ga["eps"], **({"alpha": float(self.alpha)} if bc else {}))
-                dev = self._hip_device
-                flats = {n: conv([mod.state_dict()[k] for k in keys], obs_dim, act_dim, dev)
-                         for n, mod, _, keys, conv, _, _ in self._hip_parts()}
-                eng = self._hip_engine = Engine(obs_dim, act_dim, flats["actor"], flats["critic1"],
-                                                flats.get("critic2"), cfg, hidden=self._hip_hidden, depth=self._hip_depth,
-                                                activation=self._hip_actfn)
+                             max_action=float(self.policy.actor.max_action), **({"alpha": float(self.alpha)} if bc else {}))
+                flats = {p.name: p.flat() for p in self._hip_parts()}
+                eng = Engine(self._hip_obs_dim, self._hip_act_dim, flats["actor"], flats["critic1"], flats.get("critic2"), cfg,
+                             hidden=self._hip_hidden, depth=self._hip_depth, activation=self._hip_actfn)
                 eng.cnt = getattr(self, "_cnt", 0)
-                for n, mod, optim, keys, conv, _, old in self._hip_parts():           # resume from a checkpoint
-                    setattr(eng, n + "_old", conv([old.state_dict()[k] for k in keys], obs_dim, act_dim, dev))
-                    ms, vs, step = adam_state(optim._optim, params_by_keys(mod, keys))
-                    setattr(eng, n + "_m", conv(ms, obs_dim, act_dim, dev))
-                    setattr(eng, n + "_v", conv(vs, obs_dim, act_dim, dev))
-                    if n == "actor":
-                        eng.actor_steps = step
+                self._hip_engine = _ac_load(self, eng)                               # resume from a checkpoint
             return self._hip_engine
 
         def _preprocess_batch(self, batch, buffer, indices):
-            _require_gpu(self._hip_device, "HipTD3 / HipDDPG")
-            eng = self._engine()
-            m = _mirror(self, buffer, self._hip_device)
-            idx = torch.as_tensor(np.asarray(indices, np.int64), device=self._hip_device)
+            eng, m, idx = _ac_begin(self, "HipTD3 / HipDDPG", buffer, indices)
             noise = torch.randn(size=(len(indices), eng.act_dim)) if twin else None        # td3.py:196
             batch.returns = eng.preprocess(m, idx, noise).reshape(-1, 1)
-            self._hip_idx = idx
             return batch
 
         def _update_with_batch(self, batch):
@@ -2579,23 +2518,16 @@ def _make_hip_det(twin: bool, ref=None, bc: bool = False):
             stats, w = eng.update_with_batch(*gather_rows_multi([m.obs, m.act], self._hip_idx),
                                              batch.returns.reshape(-1), getattr(batch, "weight", None))
             batch.weight = w
-            if twin:
-                self._cnt = eng.cnt
             s = stats.cpu().numpy()
-            with torch.no_grad():
-                for n, mod, optim, keys, _, back, old in self._hip_parts():
-                    params = params_by_keys(mod, keys)
-                    for p, t in zip(params, back(getattr(eng, n), eng.obs_dim, eng.act_dim, eng.hidden)):
-                        p.copy_(t)
-                    for p, t in zip(params_by_keys(old, keys), back(getattr(eng, n + "_old"), eng.obs_dim, eng.act_dim, eng.hidden)):
-                        p.copy_(t)
-                    step = eng.actor_steps if n == "actor" else eng.cnt
-                    store_adam_state(optim._optim, params, back(getattr(eng, n + "_m"), eng.obs_dim, eng.act_dim, eng.hidden),
-                                     back(getattr(eng, n + "_v"), eng.obs_dim, eng.act_dim, eng.hidden), step)
+            self._cnt = eng.cnt                       # (DDPG has no `_cnt` of its own: kept for it too, a rebuilt engine starts from it)
             if twin:
                 self._last = float(s[0])
+            self._hip_after_update()
+            if twin:
                 return TD3TrainingStats(actor_loss=float(s[0]), critic1_loss=float(s[1]), critic2_loss=float(s[2]))
             return DDPGTrainingStats(actor_loss=float(s[0]), critic_loss=float(s[1]))
+
+        _hip_write_back = _ac_write_back
 
     HipDet.__name__ = "HipTD3BC" if bc else "HipTD3" if twin else "HipDDPG"
     return HipDet
