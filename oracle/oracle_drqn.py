@@ -59,17 +59,18 @@ def n_layers(p: dict) -> int:
     return sum(1 for k in p if k.startswith("nn.weight_ih_l"))
 
 
-def forward(p: dict, obs, state=None, want_state: bool = False):
-    """obs [B, T, dim] (or [B, dim]) -> Q [B, n_act]; state = (hidden, cell) each [L, B, H]."""
-    x = torch.as_tensor(np.asarray(obs) if not isinstance(obs, torch.Tensor) else obs, dtype=torch.float32)
+def forward(p: dict, obs, state=None, want_state: bool = False, dtype=torch.float32):
+    """obs [B, T, dim] (or [B, dim]) -> Q [B, n_act]; state = (hidden, cell) each [L, B, H].  `dtype`: the arithmetic's type
+    (the parameters and the state must come in it); torch.float64 gives the yardstick of tests/drqn_edge_cases.py."""
+    x = torch.as_tensor(np.asarray(obs) if not isinstance(obs, torch.Tensor) else obs, dtype=dtype)
     if x.dim() == 2:
         x = x.unsqueeze(-2)
     x = F.linear(x, p["fc1.weight"], p["fc1.bias"])
     B, T, H = x.shape
     hs, cs = [], []
     for k in range(n_layers(p)):
-        h = torch.zeros(B, H) if state is None else state[0][k]
-        c = torch.zeros(B, H) if state is None else state[1][k]
+        h = torch.zeros(B, H, dtype=dtype) if state is None else state[0][k]
+        c = torch.zeros(B, H, dtype=dtype) if state is None else state[1][k]
         outs = []
         for t in range(T):
             gates = F.linear(x[:, t], p[f"nn.weight_ih_l{k}"], p[f"nn.bias_ih_l{k}"]) + \

@@ -8,6 +8,7 @@ import torch
 from oracle import oracle_dqn as OD
 from oracle import oracle_drqn as ORQ
 from tests import dqn_common as DC
+from tests.drqn_edge_cases import rand_params
 
 pytestmark = pytest.mark.gpu
 
@@ -18,16 +19,6 @@ def lstm_path(request, monkeypatch):
     and one GEMM + one cell launch per step (TS_RNN_PER_STEP, the path of the other widths)."""
     if request.param == "per_step":
         monkeypatch.setenv("TS_RNN_PER_STEP", "1")
-
-
-def rand_params(obs_dim, hidden, layers, n_act, seed):
-    g = torch.Generator().manual_seed(seed)
-    shapes = ORQ.param_shapes(obs_dim, hidden, layers, n_act)
-    p = {}
-    for k in ORQ.param_keys(layers):
-        bound = 1.0 / np.sqrt(hidden if k.startswith("nn.") or k.startswith("fc2") else obs_dim)
-        p[k] = (torch.rand(shapes[k], generator=g) * 2 - 1) * (2.0 * bound)
-    return p
 
 
 def make_engine(p, obs_dim, hidden, layers, n_act, ocfg):
