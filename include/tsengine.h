@@ -881,6 +881,62 @@ int ts_iqn_update(ts_workspace* ws, float* params, float* adam_m, float* adam_v,
                   const ts_distq_hparams* hp, float* prio_out, float* loss_out, float* grad_out, ts_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * DiscreteBCQ (tianshou/algorithm/imitation/discrete_bcq.py) on two DiscreteActor heads (hidden_sizes = [512],
+ * softmax_output = False) over ONE DQNet(features_only=True) trunk (examples/offline/atari_bcq.py:100-118):
+ *   feat[b]   = the DQNet trunk's F = 64 * OH3 * OW3 features
+ *   Q[b]      = relu(feat[b] @ Wq1 + bq1) @ Wq2 + bq2          logits[b] = relu(feat[b] @ Wi1 + bi1) @ Wi2 + bi2
+ *   act[b]    = argmax_a (Q[b, a] - FLT_MAX * 1{logits[b, a] - max_a logits[b, a] < log_tau})      (discrete_bcq.py:116-118)
+ * log_tau is passed as a double that the caller has already rounded to float32 (the reference compares in float32),
+ * -INFINITY for a threshold of 0; a ratio equal to log_tau is NOT masked; ties go to the first action.
+ * Flat parameters: conv1 | conv2 | conv3 (ts_dqn layout) | [Wq1; bq1] [F + 1, 512] | [Wq2; bq2] [513, ld] | [Wi1; bi1]
+ * [F + 1, 512] | [Wi2; bi2] [513, ld]; F in (h, w, c) order, ld = n_act rounded up to a multiple of 32, padding columns are
+ * (and stay) zero.  The lagged vector has the same length; its imitator part is never read.
+ * Limits (TS_ERR_INVALID_ARG otherwise): 1 <= n_act <= 64, hidden 512, log_tau <= 0 and not NaN, penalty finite and >= 0.
+ * ------------------------------------------------------------------------------------------- */
+int64_t ts_bcq_param_count(int64_t c, int64_t h, int64_t w, int64_t n_act);
+/* h_out10 (host): {F, ld, total, offsets of conv1, conv2, conv3, Q fc1, Q fc2, I fc1, I fc2} */
+int ts_bcq_layout(int64_t c, int64_t h, int64_t w, int64_t n_act, int64_t* h_out10);
+
+/* The per-sample kernels on raw arrays (edge tests; no network, no workspace).  q / logits / q_old: float32[B, n_act].
+ * ts_bcq_head: act_out int64[B] = the masked argmax.  ts_bcq_target: out float32[B] = q_old[b, act[b]], act_out nullable. */
+int ts_bcq_head(const float* q, const float* logits, int64_t B, int64_t n_act, double log_tau, int64_t* act_out,
+                ts_stream_t stream);
+int ts_bcq_target(const float* q, const float* logits, const float* q_old, int64_t B, int64_t n_act, double log_tau,
+                  float* out, int64_t* act_out, ts_stream_t stream);
+/* The loss of discrete_bcq.py:244-252 and its head gradients.  terms_out float32[4, B] = {delta = Q[b, act_b] - returns[b],
+ * smooth_l1(delta), -log_softmax(logits[b])[act_b], sum_a logits[b, a]^2}; loss4_out float32[4] = [loss, q_loss, i_loss,
+ * reg_loss], loss = (q_loss + i_loss) + penalty * reg_loss in float32; dq_out / dlogits_out float32[B, ld] (ld = n_act
+ * rounded up to 32; every column written, padding exactly 0):
+ *   dq[b, a] = clamp(delta, -1, 1) / B at a = act_b, else 0
+ *   dlogits[b, a] = (softmax[b, a] - 1{a = act_b}) / B + 2 penalty logits[b, a] / (B n_act)
+ * act int64[B]: values outside [0, n_act) are clamped into it. */
+int ts_bcq_loss(const float* q, const float* logits, const int64_t* act, const float* returns, int64_t B, int64_t n_act,
+                double imitation_logits_penalty, float* dq_out, float* dlogits_out, float* terms_out, float* loss4_out,
+                ts_stream_t stream);
+
+/* DiscreteBCQPolicy.forward (discrete_bcq.py:104-127): the trunk once, both heads -> q_out float32[B, n_act], logits_out
+ * float32[B, n_act], act_out int64[B]; each nullable. */
+int ts_bcq_forward(ts_workspace* ws, const float* params, int64_t c, int64_t h, int64_t w, int64_t n_act, const void* obs_nhwc,
+                   int obs_u8, int64_t B, double log_tau, float* q_out, float* logits_out, int64_t* act_out,
+                   ts_stream_t stream);
+
+/* DiscreteBCQ._target_q (discrete_bcq.py:228-234): the masked argmax of the LIVE Q head and the LIVE imitator on obs_next,
+ * the lagged trunk + Q head (params_old) beside them on a side stream of the workspace -> out float32[B] =
+ * Q_old(obs_next)[b, act[b]]; act_out int64[B] nullable. */
+int ts_bcq_target_q(ts_workspace* ws, const float* params, const float* params_old, int64_t c, int64_t h, int64_t w,
+                    int64_t n_act, const void* obs_next_nhwc, int obs_u8, int64_t B, double log_tau, float* out,
+                    int64_t* act_out, ts_stream_t stream);
+
+/* DiscreteBCQ._update_with_batch (discrete_bcq.py:236-261) after the periodic sync: forward, the three-term loss (no
+ * importance weights: BCQ reads none), backward through both heads into the shared trunk, clip_grad_norm_ + ONE Adam over
+ * the whole flat vector.  returns float32[B]; loss4_out float32[4] = [loss, q_loss, i_loss, reg_loss] (ts_dqn_wait_td waits
+ * for them); grad_out nullable: the flat gradient; hp->lr < 0: gradient only (needs grad_out; hp->huber_delta unused). */
+int ts_bcq_update(ts_workspace* ws, float* params, float* adam_m, float* adam_v, int64_t adam_step, int64_t c, int64_t h,
+                  int64_t w, int64_t n_act, const void* obs_nhwc, int obs_u8, const int64_t* act, const float* returns,
+                  int64_t B, const ts_dqn_hparams* hp, double imitation_logits_penalty, float* loss4_out, float* grad_out,
+                  ts_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Rainbow (tianshou/algorithm/modelfree/rainbow.py): C51 on RainbowNet (env/atari/atari_network.py:154-208) -- DQNet
  * feature trunk, NoisyLinear layers (utils/net/discrete.py:317-374) in a Q branch (F -> 512 -> n_act * n_atoms) and a
  * dueling V branch (F -> 512 -> n_atoms), logits = q - mean_a q + v, softmax over the atoms.

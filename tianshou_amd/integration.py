@@ -1799,6 +1799,127 @@ def make_hip_iqn(ref=None):
     return HipIQN
 
 
+def make_hip_discrete_bcq(ref=None):
+    """Returns HipDiscreteBCQ(DiscreteBCQ): `_preprocess_batch` / `_update_with_batch` (imitation/discrete_bcq.py:213-261) on
+    the engine (tianshou_amd/bcq.py).  Supported model: policy.model and policy.imitator = DiscreteActor(preprocess_net,
+    hidden_sizes=[512], softmax_output=False) on ONE shared DQNet(features_only=True), as examples/offline/atari_bcq.py builds
+    them, with one Adam over the policy; buffer layouts as HipDQN -- a plain ReplayBuffer / VectorReplayBuffer; a prioritized
+    one is accepted and its weights are ignored, as the reference ignores them.  The threshold (`policy._log_tau`) and
+    `_weight_reg` are read from the algorithm at every update; the statistics are DiscreteBCQTrainingStats(loss, q_loss, i_loss,
+    reg_loss).  The parameter root is the POLICY (fourteen parameters, the shared trunk once); `model_old` holds the first ten.
+    The collector's `policy.forward` stays on torch.  `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    from . import bcq as BQ
+    from . import dqn as D
+
+    Base = _ref(ref, "tianshou.algorithm.imitation.discrete_bcq", "DiscreteBCQ")
+    DiscreteBCQTrainingStats = _ref(ref, "tianshou.algorithm.imitation.discrete_bcq", "DiscreteBCQTrainingStats")
+    supported = ("HipDiscreteBCQ: policy.model and policy.imitator must be DiscreteActor(preprocess_net, hidden_sizes=[512], "
+                 "softmax_output=False) on one shared DQNet(features_only=True)")
+    old_keys = [k[len("model."):] for k in BQ.TIANSHOU_KEYS[:BQ.N_LAGGED]]
+
+    class HipDiscreteBCQ(_HipGlue, Base):
+        def __init__(self, *args, device="cuda", **kwargs):
+            super().__init__(*args, **kwargs)
+            self._hip_device = torch.device(device)
+            self._hip_check_model()
+            _adam_of(self.optim)
+            self._hip_engine = None
+            self._hip_glue_init()
+
+        def _hip_check_model(self) -> None:
+            pol = self.policy
+            named = dict(pol.named_parameters())
+            if list(named.keys()) != BQ.TIANSHOU_KEYS:
+                raise NotImplementedError(f"{supported}; got parameters {list(named.keys())}")
+            if getattr(pol.model, "preprocess", None) is not getattr(pol.imitator, "preprocess", None):
+                raise NotImplementedError(f"{supported}; the two heads do not share one trunk object")
+            shapes = [tuple(named[k].shape) for k in BQ.TIANSHOU_KEYS]
+            convs_ok = (len(shapes[0]) == 4 and shapes[0][0] == 32 and shapes[0][2:] == (8, 8) and shapes[2] == (64, 32, 4, 4)
+                        and shapes[4] == (64, 64, 3, 3))
+            if not convs_ok:
+                raise NotImplementedError(f"{supported}; the preprocess_net is not the DQNet convolution trunk")
+            for j in (6, 10):
+                if shapes[j][0] != BQ.HIDDEN or shapes[j + 2][1] != BQ.HIDDEN:
+                    raise NotImplementedError(f"{supported}; got hidden width {shapes[j][0]}")
+            if shapes[8][0] != shapes[12][0] or not 1 <= shapes[8][0] <= 64:
+                raise NotImplementedError("HipDiscreteBCQ: both heads need the same number of actions, 1 <= n_act <= 64")
+            if getattr(pol.model, "softmax_output", False) or getattr(pol.imitator, "softmax_output", False):
+                raise NotImplementedError(f"{supported}; got softmax_output=True")
+            if not self.freq > 0:
+                raise NotImplementedError("HipDiscreteBCQ: BCQ needs target_update_freq > 0")
+            opt_params = [p for g in self.optim._optim.param_groups for p in g["params"]]
+            if len(self.optim._optim.param_groups) != 1 or {id(p) for p in opt_params} != {id(p) for p in named.values()}:
+                raise NotImplementedError("HipDiscreteBCQ: one optimizer group over the policy's fourteen parameters")
+
+        def _hip_old_params(self):
+            """The lagged network's ten parameters; `model_old` is the bare module or its EvalModeModuleWrapper."""
+            return params_by_keys(getattr(self.model_old, "module", self.model_old), old_keys)
+
+        def _hip_read_scalars(self, eng) -> None:
+            eng.cfg.log_tau = float(self.policy._log_tau)                         # read at every call, as the learning rate
+            eng.cfg.imitation_logits_penalty = float(self._weight_reg)
+
+        def _engine(self, c, h, w):
+            if self._hip_engine is None:
+                dev = self._hip_device
+                params = params_by_keys(self.policy, BQ.TIANSHOU_KEYS)
+                n_act = int(params[8].shape[0])
+                dims = (c, h, w, n_act)
+                _, g = _adam_of(self.optim)
+                cfg = BQ.BCQConfig(gamma=self.gamma, n_step=self.n_step, target_update_freq=self.freq, lr=g["lr"],
+                                   betas=tuple(g["betas"]), adam_eps=g["eps"], max_grad_norm=self.optim._max_grad_norm,
+                                   log_tau=float(self.policy._log_tau), imitation_logits_penalty=float(self._weight_reg))
+                eng = BQ.BCQEngine(c, h, w, n_act, BQ.flat_from_torch([p.detach() for p in params], *dims, dev), cfg)
+                eng.iter = self._iter
+                ms, vs, eng.adam_step = adam_state(self.optim._optim, params)
+                eng.adam_m, eng.adam_v = BQ.flat_from_torch(ms, *dims, dev), BQ.flat_from_torch(vs, *dims, dev)
+                eng.params_old = BQ.flat_from_torch([p.detach() for p in self._hip_old_params()], *dims, dev)
+                self._hip_engine = eng
+            return self._hip_engine
+
+        def _hip_write_back(self) -> None:
+            """Engine parameters, lagged parameters and Adam state -> the torch modules and torch.optim: fourteen tensors of the
+            policy (the shared trunk is written once), the first ten of the lagged vector into `model_old`."""
+            eng = self.__dict__.get("_hip_engine_obj")
+            if eng is None:
+                return
+            dims = (eng.c, eng.h, eng.w, eng.n_act)
+            params = params_by_keys(self.policy, BQ.TIANSHOU_KEYS)
+            with torch.no_grad():
+                for p, t in zip(params, BQ.flat_to_torch(eng.params, *dims)):
+                    self._hip_put(p, t)
+                for p, t in zip(self._hip_old_params(), BQ.flat_to_torch(eng.params_old, *dims)[:BQ.N_LAGGED]):
+                    self._hip_put(p, t)
+            store_adam_state(self.optim._optim, params, BQ.flat_to_torch(eng.adam_m, *dims), BQ.flat_to_torch(eng.adam_v, *dims),
+                             eng.adam_step)
+
+        def _preprocess_batch(self, batch, buffer, indices):
+            c, h, w, self._hip_stack = self._layout(buffer, "HipDiscreteBCQ")
+            _require_gpu(self._hip_device, "HipDiscreteBCQ")
+            m = _mirror(self, buffer, self._hip_device)
+            idx = self._hip_idx = torch.as_tensor(np.asarray(indices, np.int64), device=self._hip_device)
+            eng = self._engine(c, h, w)
+            self._hip_read_scalars(eng)
+            batch.returns = eng.preprocess(m, m.obs, idx, self._hip_stack, obs_next_frames=m.obs_next)
+            return batch
+
+        def _update_with_batch(self, batch):
+            self._hip_refresh_lr()
+            eng, m = self._hip_engine, self._hip_mirror
+            obs = D.gather_obs_nhwc(m.obs, m, self._hip_idx, self._hip_stack, as_u8=True)
+            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device)
+            self._hip_read_scalars(eng)
+            losses = eng.update_with_batch(obs, act, batch.returns)              # no batch.weight: BCQ reads and writes none
+            self._iter = eng.iter
+            self._hip_after_update()
+            loss, q_loss, i_loss, reg_loss = losses.tolist()                      # one transfer for the four numbers
+            return DiscreteBCQTrainingStats(loss=loss, q_loss=q_loss, i_loss=i_loss, reg_loss=reg_loss)   # discrete_bcq.py:256-261
+
+        _layout = staticmethod(_q_layout)
+
+    return HipDiscreteBCQ
+
+
 def make_hip_rainbow(ref=None):
     """Returns HipRainbow(RainbowDQN): `_preprocess_batch` / `_update_with_batch` (dqn.py:257-275, rainbow.py:93-101 ->
     c51.py:120-160) on the engine.  Supported model: RainbowNet(is_dueling=True, is_noisy=True)
