@@ -937,6 +937,54 @@ int ts_bcq_update(ts_workspace* ws, float* params, float* adam_m, float* adam_v,
                   ts_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * DiscreteCRR (tianshou/algorithm/imitation/discrete_crr.py) on a DiscreteActor (hidden_sizes = [512], softmax_output =
+ * False) and a DiscreteCritic (hidden_sizes = [512], last_size = n_act) over ONE DQNet(features_only=True) trunk
+ * (examples/offline/atari_crr.py).  The network and its flat layout are DiscreteBCQ's above, with the Q head = the critic
+ * and the imitator head = the actor: ts_bcq_param_count / ts_bcq_layout serve both, and there is no struct of its own.
+ * Per sample b with a = act[b], q = Q(obs)[b], l = the actor's logits on obs, pi = softmax(l):
+ *   nll = logsumexp(l) - l[a]     qa = q[a]     V = sum_j pi_j q_j     adv = qa - V
+ *   y   = rew + gamma * (done > 0 ? 0 : sum_j softmax(l_old)_j q_old_j)          the lagged pair on obs_next, no gradient
+ *   critic_loss = 0.5 mean_b (qa - y)^2     actor_loss = mean_b nll * mean_b coef     cql_loss = mean_b (logsumexp(q) - qa)
+ *   loss = (actor_loss + critic_loss) + min_q_weight * cql_loss                  in float32, in this order
+ * `mode` selects coef: 0 "exp": clamp(exp(adv / beta), 0, ratio_upper_bound); 1 "binary": 1{adv > 0}; 2 "all": 1.
+ * The actor loss is a product of two batch means because the reference multiplies -log_prob(act), a [B], by the weight, a
+ * [B, 1], and takes the mean of the [B, B] product (discrete_crr.py:148-155); its CQL mean runs over the same kind of
+ * broadcast, and that one equals the per-sample form above up to rounding.  In "exp" mode coef is NOT detached (the
+ * reference does not detach it): with nbar = mean_b nll, cbar = mean_b coef, e = exp(adv / beta) and
+ * g = nbar * e / beta * 1{e <= ratio_upper_bound} (the clamp passes the gradient at equality),
+ *   dq[b, j] = (delta 1{j=a} + g (1{j=a} - pi_j) + min_q_weight (softmax(q)_j - 1{j=a})) / B,   delta = qa - y
+ *   dl[b, j] = (cbar (pi_j - 1{j=a}) - g pi_j (q_j - V)) / B
+ * and g = 0 in the other modes.  Where e overflows to inf under a finite bound, g = 0 * inf = NaN, as in the reference.
+ * `done` is uint8 (the element type of the device replay mirror's flags); `> 0` masks.  rew float32[B], act int64[B]
+ * (values outside [0, n_act) are clamped into it).  beta, ratio_upper_bound, min_q_weight and gamma are rounded to float32.
+ * Limits (TS_ERR_INVALID_ARG otherwise, checked before any device work): 1 <= n_act <= 64, hidden 512, mode in {0, 1, 2},
+ * beta finite and nonzero, ratio_upper_bound not NaN, min_q_weight and gamma finite, no NULL pointer (but the two named
+ * nullable), B within ts_bcq_update's limits.
+ * ------------------------------------------------------------------------------------------- */
+/* The per-sample kernels on raw arrays (edge tests; no network, no workspace).  q_old / logits_old: float32[B, n_act];
+ * out float32[B] = y above. */
+int ts_crr_target(const float* q_old, const float* logits_old, const float* rew, const uint8_t* done, int64_t B, int64_t n_act,
+                  double gamma, float* out, ts_stream_t stream);
+/* q / logits: float32[B, n_act]; target float32[B] = y.  terms_out float32[6, B] = {delta, 0.5 delta^2, nll, coef,
+ * logsumexp(q) - qa, adv}; loss6_out float32[6] = [loss, actor_loss, critic_loss, cql_loss, nbar, cbar]; dq_out /
+ * dlogits_out float32[B, ld] (ld = n_act rounded up to 32; every column written, padding exactly 0). */
+int ts_crr_loss(const float* q, const float* logits, const int64_t* act, const float* target, int64_t B, int64_t n_act,
+                int64_t mode, double beta, double ratio_upper_bound, double min_q_weight, float* dq_out, float* dlogits_out,
+                float* terms_out, float* loss6_out, ts_stream_t stream);
+
+/* DiscreteCRR._update_with_batch (discrete_crr.py:125-167) after the periodic sync: the live trunk once and both heads side
+ * by side on obs; the lagged trunk and both lagged heads (params_old) on obs_next on a side stream of the workspace; the
+ * target, the loss, the backward pass through both heads into the shared trunk, clip_grad_norm_ + ONE Adam over the whole
+ * flat vector.  params_old == params is legal (target_update_freq == 0): the target is complete before Adam writes.
+ * obs / obs_next share obs_u8.  loss6_out float32[6] as above (ts_dqn_wait_td waits for them); target_out nullable: y float32[B];
+ * grad_out nullable: the flat gradient; hp->lr < 0: gradient only (needs grad_out; hp->huber_delta unused). */
+int ts_crr_update(ts_workspace* ws, float* params, const float* params_old, float* adam_m, float* adam_v, int64_t adam_step,
+                  int64_t c, int64_t h, int64_t w, int64_t n_act, const void* obs_nhwc, const void* obs_next_nhwc, int obs_u8,
+                  const int64_t* act, const float* rew, const uint8_t* done, int64_t B, const ts_dqn_hparams* hp, double gamma,
+                  int64_t mode, double beta, double ratio_upper_bound, double min_q_weight, float* loss6_out, float* target_out,
+                  float* grad_out, ts_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Rainbow (tianshou/algorithm/modelfree/rainbow.py): C51 on RainbowNet (env/atari/atari_network.py:154-208) -- DQNet
  * feature trunk, NoisyLinear layers (utils/net/discrete.py:317-374) in a Q branch (F -> 512 -> n_act * n_atoms) and a
  * dueling V branch (F -> 512 -> n_atoms), logits = q - mean_a q + v, softmax over the atoms.

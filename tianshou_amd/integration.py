@@ -1920,6 +1920,158 @@ def make_hip_discrete_bcq(ref=None):
     return HipDiscreteBCQ
 
 
+def make_hip_discrete_crr(ref=None):
+    """Returns HipDiscreteCRR(DiscreteCRR): `_update_with_batch` (imitation/discrete_crr.py:125-167) on the engine
+    (tianshou_amd/crr.py).  Supported model: policy.actor = DiscreteActor(preprocess_net, hidden_sizes=[512],
+    softmax_output=False) and critic = DiscreteCritic(preprocess_net, hidden_sizes=[512], last_size=n_act) on ONE shared
+    DQNet(features_only=True), as examples/offline/atari_crr.py builds them, with one Adam over ModuleList([policy, critic]);
+    buffer layouts as HipDQN -- a plain ReplayBuffer / VectorReplayBuffer; a prioritized one is accepted and its weights are
+    ignored, as the reference ignores them.  `_preprocess_batch` is the base implementation unchanged (the discounted episodic
+    returns nothing reads, and the return-standardization state) followed by the device mirror.  The mode, `_beta`,
+    `_ratio_upper_bound`, `_min_q_weight` and gamma are read from the algorithm at every update; the statistics are
+    DiscreteCRRTrainingStats(loss, actor_loss, critic_loss, cql_loss).  `actor_old` and `critic_old` each own a copy of the
+    trunk; the reference syncs them together, so the engine keeps ONE lagged vector, refuses two lagged trunks that differ,
+    and writes the lagged trunk back into both.  With target_update_freq == 0 there is no lagged state.  The collector's
+    `policy.forward` stays on torch.  `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    from . import crr as CR
+    from . import dqn as D
+
+    Base = _ref(ref, "tianshou.algorithm.imitation.discrete_crr", "DiscreteCRR")
+    DiscreteCRRTrainingStats = _ref(ref, "tianshou.algorithm.imitation.discrete_crr", "DiscreteCRRTrainingStats")
+    supported = ("HipDiscreteCRR: policy.actor must be DiscreteActor(preprocess_net, hidden_sizes=[512], softmax_output=False) "
+                 "and critic DiscreteCritic(preprocess_net, hidden_sizes=[512], last_size=n_act) on one shared "
+                 "DQNet(features_only=True)")
+    actor_keys = [k[len("0.actor."):] for k in CR.TIANSHOU_KEYS[:10]]                # actor_old: trunk + actor head
+    critic_keys = actor_keys[:6] + [k[len("1."):] for k in CR.TIANSHOU_KEYS[10:]]     # critic_old: trunk + critic head
+
+    class HipDiscreteCRR(_HipGlue, Base):
+        def __init__(self, *args, device="cuda", **kwargs):
+            super().__init__(*args, **kwargs)
+            self._hip_device = torch.device(device)
+            self._hip_check_model()
+            _adam_of(self.optim)
+            self._hip_engine = None
+            self._hip_glue_init()
+
+        def _hip_live_params(self):
+            named = dict(torch.nn.ModuleList([self.policy, self.critic]).named_parameters())
+            if list(named.keys()) != CR.TIANSHOU_KEYS:
+                raise NotImplementedError(f"{supported}; got parameters {list(named.keys())}")
+            return [named[k] for k in CR.TIANSHOU_KEYS]
+
+        def _hip_check_model(self) -> None:
+            params = self._hip_live_params()
+            actor = getattr(self.policy, "actor", None)
+            if getattr(actor, "preprocess", None) is not getattr(self.critic, "preprocess", None):
+                raise NotImplementedError(f"{supported}; the actor and the critic do not share one trunk object")
+            shapes = [tuple(p.shape) for p in params]
+            convs_ok = (len(shapes[0]) == 4 and shapes[0][0] == 32 and shapes[0][2:] == (8, 8) and shapes[2] == (64, 32, 4, 4)
+                        and shapes[4] == (64, 64, 3, 3))
+            if not convs_ok:
+                raise NotImplementedError(f"{supported}; the preprocess_net is not the DQNet convolution trunk")
+            for j in (6, 10):
+                if shapes[j][0] != CR.HIDDEN or shapes[j + 2][1] != CR.HIDDEN:
+                    raise NotImplementedError(f"{supported}; got hidden width {shapes[j][0]}")
+            if shapes[8][0] != shapes[12][0] or not 1 <= shapes[8][0] <= 64:
+                raise NotImplementedError("HipDiscreteCRR: both heads need the same number of actions, 1 <= n_act <= 64")
+            if getattr(actor, "softmax_output", False):
+                raise NotImplementedError(f"{supported}; got softmax_output=True")
+            CR.mode_id(self._policy_improvement_mode)
+            opt_params = [p for g in self.optim._optim.param_groups for p in g["params"]]
+            if len(self.optim._optim.param_groups) != 1 or {id(p) for p in opt_params} != {id(p) for p in params}:
+                raise NotImplementedError("HipDiscreteCRR: one optimizer group over the fourteen parameters of "
+                                          "ModuleList([policy, critic])")
+
+        def _hip_old_params(self):
+            """The fourteen lagged parameters in TIANSHOU_KEYS order: the trunk and the actor head of `actor_old`, the critic
+            head of `critic_old` (each the bare module or its EvalModeModuleWrapper), and `critic_old`'s own trunk, which must
+            equal `actor_old`'s bit for bit -- the reference always syncs the two together."""
+            a_old = params_by_keys(getattr(self.actor_old, "module", self.actor_old), actor_keys)
+            c_old = params_by_keys(getattr(self.critic_old, "module", self.critic_old), critic_keys)
+            if not all(torch.equal(x.detach(), y.detach()) for x, y in zip(a_old[:6], c_old[:6])):
+                raise NotImplementedError("HipDiscreteCRR: the trunks of actor_old and critic_old differ; the engine keeps one "
+                                          "lagged trunk (the reference syncs the two lagged networks together)")
+            return a_old + c_old[6:]
+
+        def _hip_read_scalars(self, eng) -> None:
+            cfg = eng.cfg                                                         # read at every call, as the learning rate
+            cfg.policy_improvement_mode = self._policy_improvement_mode
+            cfg.beta, cfg.ratio_upper_bound = float(self._beta), float(self._ratio_upper_bound)
+            cfg.min_q_weight, cfg.gamma = float(self._min_q_weight), float(self.discounted_return_computation.gamma)
+
+        def _engine(self, c, h, w):
+            if self._hip_engine is None:
+                dev = self._hip_device
+                params = self._hip_live_params()
+                n_act = int(params[8].shape[0])
+                dims = (c, h, w, n_act)
+                _, g = _adam_of(self.optim)
+                cfg = CR.CRRConfig(gamma=float(self.discounted_return_computation.gamma),
+                                   policy_improvement_mode=self._policy_improvement_mode, beta=float(self._beta),
+                                   ratio_upper_bound=float(self._ratio_upper_bound), min_q_weight=float(self._min_q_weight),
+                                   target_update_freq=int(self._freq) if self._target else 0, lr=g["lr"],
+                                   betas=tuple(g["betas"]), adam_eps=g["eps"], max_grad_norm=self.optim._max_grad_norm)
+                eng = CR.CRREngine(c, h, w, n_act, CR.flat_from_torch([p.detach() for p in params], *dims, dev), cfg)
+                eng.iter = self._iter
+                ms, vs, eng.adam_step = adam_state(self.optim._optim, params)
+                eng.adam_m, eng.adam_v = CR.flat_from_torch(ms, *dims, dev), CR.flat_from_torch(vs, *dims, dev)
+                if self._target:
+                    eng.params_old = CR.flat_from_torch([p.detach() for p in self._hip_old_params()], *dims, dev)
+                self._hip_engine = eng
+            return self._hip_engine
+
+        def _hip_write_back(self) -> None:
+            """Engine parameters, lagged parameters and Adam state -> the torch modules and torch.optim: fourteen live tensors
+            (the shared trunk is written once); the lagged trunk into BOTH lagged modules, the lagged actor head into
+            `actor_old`, the lagged critic head into `critic_old`.  Without lagged networks there is nothing more to write."""
+            eng = self.__dict__.get("_hip_engine_obj")
+            if eng is None:
+                return
+            dims = (eng.c, eng.h, eng.w, eng.n_act)
+            params = self._hip_live_params()
+            with torch.no_grad():
+                for p, t in zip(params, CR.flat_to_torch(eng.params, *dims)):
+                    self._hip_put(p, t)
+                if self._target:
+                    a_old = params_by_keys(getattr(self.actor_old, "module", self.actor_old), actor_keys)
+                    c_old = params_by_keys(getattr(self.critic_old, "module", self.critic_old), critic_keys)
+                    old = CR.flat_to_torch(eng.params_old, *dims)
+                    for p, t in zip(a_old + c_old[6:] + c_old[:6], old + old[:6]):
+                        self._hip_put(p, t)
+            store_adam_state(self.optim._optim, params, CR.flat_to_torch(eng.adam_m, *dims), CR.flat_to_torch(eng.adam_v, *dims),
+                             eng.adam_step)
+
+        def _preprocess_batch(self, batch, buffer, indices):
+            batch = super()._preprocess_batch(batch, buffer, indices)            # discrete_crr.py:113-123, on the host, unchanged
+            c, h, w, self._hip_stack = self._layout(buffer, "HipDiscreteCRR")
+            _require_gpu(self._hip_device, "HipDiscreteCRR")
+            _mirror(self, buffer, self._hip_device)
+            self._hip_idx = torch.as_tensor(np.asarray(indices, np.int64), device=self._hip_device)
+            self._engine(c, h, w)
+            return batch
+
+        def _update_with_batch(self, batch):
+            self._hip_refresh_lr()
+            eng, m, idx = self._hip_engine, self._hip_mirror, self._hip_idx
+            obs = D.gather_obs_nhwc(m.obs, m, idx, self._hip_stack, as_u8=True)
+            if m.obs_next is None:                                               # save_only_last_obs: the next slot's stack
+                obs_next = D.gather_obs_nhwc(m.obs, m, m.next(idx), self._hip_stack, as_u8=True)
+            else:
+                obs_next = D.gather_obs_nhwc(m.obs_next, m, idx, self._hip_stack, as_u8=True)
+            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device)
+            self._hip_read_scalars(eng)
+            losses = eng.update_with_batch(obs, obs_next, act, m.rew[idx].float(), m.done[idx])   # no batch.weight: CRR reads none
+            self._iter = eng.iter
+            self._hip_after_update()
+            loss, actor_loss, critic_loss, cql_loss = losses.tolist()            # one transfer for the four numbers
+            return DiscreteCRRTrainingStats(loss=loss, actor_loss=actor_loss, critic_loss=critic_loss,
+                                            cql_loss=cql_loss)                   # discrete_crr.py:162-167
+
+        _layout = staticmethod(_q_layout)
+
+    return HipDiscreteCRR
+
+
 def make_hip_rainbow(ref=None):
     """Returns HipRainbow(RainbowDQN): `_preprocess_batch` / `_update_with_batch` (dqn.py:257-275, rainbow.py:93-101 ->
     c51.py:120-160) on the engine.  Supported model: RainbowNet(is_dueling=True, is_noisy=True)
