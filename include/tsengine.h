@@ -1476,6 +1476,56 @@ int ts_td3bc_update(ts_workspace* ws, const ts_td3_state* st, int64_t critic_ste
                     const ts_mlp_trunk* trunk, const ts_td3_hparams* hp, double bc_alpha, float* stats_out4, float* weight_out,
                     float* grads_out, ts_stream_t stream);
 
+/* ---- continuous CQL (imitation/cql.py:203-400, arXiv 2006.04779, with the Cal-QL option) on SAC's networks and state ----
+ * cql_hp: a plain double array indexed by TS_CQL_HP_* (no struct: the SAC structs carry everything else). */
+#define TS_CQL_HP_GAMMA 0
+#define TS_CQL_HP_CQL_WEIGHT 1
+#define TS_CQL_HP_TEMPERATURE 2
+#define TS_CQL_HP_WITH_LAGRANGE 3      /* 0 / 1 */
+#define TS_CQL_HP_LAGRANGE_THRESHOLD 4
+#define TS_CQL_HP_ALPHA_MIN 5
+#define TS_CQL_HP_ALPHA_MAX 6
+#define TS_CQL_HP_CQL_ALPHA_LR 7       /* < 0: no step on cql_log_alpha */
+#define TS_CQL_HP_MAX_GRAD_NORM 8      /* <= 0: the critic steps are not clipped */
+#define TS_CQL_HP_COUNT 9
+
+/* CQL._update_with_batch (cql.py:268-400) in the reference's order: actor step on the critics BEFORE their update (no clip),
+ * AutoAlpha step, target = rew + !done * gamma * (min(Q1_old, Q2_old)(s', a') - alpha log pi') with the UPDATED actor and
+ * alpha (float32 throughout), critic losses + the CQL term, the Lagrange step, critic 1 / critic 2 Adam each behind
+ * clip_grad_norm_(max_grad_norm) over its own parameters, Polyak.  The live critics run ONE twin pass over the stacked input
+ *   X [B (1 + 3R), kc] = [ (s, a) | (s_rep, random_act) | (s_rep, pi(s)) | (s_rep, pi(s')) ]      (R = num_repeat_actions)
+ * and the updated actor one pass over [obs_next | obs] (2B rows: the R repeated rows of an observation are identical).
+ *   cql_k = mean(logsumexp([random_k, pi_k, next_pi_k] / T, dim 1)) w T - mean(Q_k(s, a)) w, the logsumexp over the three
+ *   kinds of one repeated row (cql.py:321-351), each value first max(value, calib[b]) when calib is given (ties: half the
+ *   gradient); with the Lagrange multiplier cql_alpha = clamp(exp(cql_log_alpha), alpha_min, alpha_max),
+ *   cql_k <- cql_alpha (cql_k - lagrange_threshold), cql_alpha_loss = -(cql_1 + cql_2) / 2 and one Adam step (torch's default
+ *   betas / eps, step number adam_step) on cql_log_alpha; the critic gradients and the statistic use the pre-step cql_alpha.
+ * obs / obs_next float32[B, obs_dim], act [B, act_dim], rew / done (nonzero = done) / calib (nullable) float32[B];
+ * noise_actor / noise_next float32[B, act_dim]; random_act / noise_rep_cur / noise_rep_next float32[B R, act_dim] (row b R + r).
+ * cql_log_alpha3 = {cql_log_alpha, Adam m, Adam v} (device; nullable without the multiplier).
+ * stats_out7 = {actor_loss, critic1_loss, critic2_loss, alpha, alpha_loss, cql_alpha, cql_alpha_loss} (without the multiplier
+ * the last two are 1 and 0); target_out (nullable) float32[B]; grads_out (nullable) = {critic1, critic2, actor} gradients,
+ * the critics' BEFORE clipping.  A negative learning rate skips that optimizer step.
+ * TS_ERR_INVALID_ARG before any HIP call: R < 1, B (1 + 3R) beyond int, temperature <= 0, alpha_min > alpha_max, a
+ * non-finite entry of cql_hp. */
+int ts_cql_update(ts_workspace* ws, const ts_sac_state* st, float* cql_log_alpha3, int64_t adam_step, const float* obs,
+                  const float* act, const float* rew, const float* done, const float* obs_next, const float* calib,
+                  const float* noise_actor, const float* noise_next, const float* random_act, const float* noise_rep_cur,
+                  const float* noise_rep_next, int64_t B, int64_t R, int64_t obs_dim, int64_t act_dim,
+                  const ts_mlp_trunk* trunk, const ts_sac_hparams* hp, const double* cql_hp, float* stats_out7,
+                  float* target_out, float* grads_out, ts_stream_t stream);
+
+/* The loss kernels of ts_cql_update alone, on caller-supplied dense arrays of BOTH critics (critic 1 first):
+ * q_data float32[2, B], target [B], q_rand / q_cur / q_next [2, B R] (the critics' raw outputs), logp_cur / logp_next [B R],
+ * calib nullable [B], cql_log_alpha one device float (read only; nullable without the multiplier).
+ * d_data_out float32[2, B] and d_rep_out [2, 3, B R] = d(critic_k_loss) / d(the Q arrays, in the order random, pi, next);
+ * loss_out9 = {mse_1, mse_2, mean logsumexp 1, 2, cql_1, cql_2, cql_alpha, cql_alpha_loss, d cql_alpha_loss / d cql_log_alpha}
+ * (critic_k_loss = mse_k + cql_k).  cql_hp and the refusals as in ts_cql_update (gamma, the rate and the norm are unused). */
+int ts_cql_loss(ts_workspace* ws, const float* q_data, const float* target, const float* q_rand, const float* q_cur,
+                const float* q_next, const float* logp_cur, const float* logp_next, const float* calib,
+                const float* cql_log_alpha, int64_t B, int64_t R, int64_t act_dim, const double* cql_hp, float* d_data_out,
+                float* d_rep_out, float* loss_out9, ts_stream_t stream);
+
 /* ---- data-parallel exchange ------------------------------------------------------------------
  * One process per GPU; the reference has no distributed path (its only multi-GPU mechanism is single-process
  * nn.DataParallel, tianshou/utils/net/common.py:473-515).  In-place sum all-reduce of a flat fp32 buffer over RCCL

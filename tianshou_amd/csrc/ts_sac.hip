@@ -365,14 +365,15 @@ __device__ __forceinline__ void sac_policy_item(int64_t t, const float* __restri
                                                 int64_t B, int A, int head_cols, int obs_dim, int kc, float bound,
                                                 float* __restrict__ x_c, float* __restrict__ act_out,
                                                 float* __restrict__ logp_out, float* __restrict__ keep,
-                                                float* __restrict__ mu_out, float* __restrict__ sigma_out) {
+                                                float* __restrict__ mu_out, float* __restrict__ sigma_out, int rep = 1) {
     // half a wavefront per sample, lane j = action dimension j (A <= 32); the two sums over j are butterfly
     // reductions inside the half-wave (fixed order)
     const int64_t b = t >> 5;
     const int j = (int)(t & 31);
     float lp = 0.f, corr = 0.f;
     if (b < B && j < A) {
-        const float* hb = head + b * head_cols;
+        // rep > 1 (CQL's repeated observations): samples b = i * rep .. i * rep + rep - 1 share head row i
+        const float* hb = head + (rep == 1 ? b : b / rep) * head_cols;
         // `bound` > 0: ContinuousActorProbabilistic(unbounded=False), the class default -- mu = max_action * tanh(mu)
         // (continuous.py:230-231) in front of the Gaussian; 0 = the examples' unbounded actor
         const float mu = bound > 0.f ? bound * tanhf(hb[j]) : hb[j];
@@ -2484,6 +2485,475 @@ int ts_redq_update(ts_workspace* ws, const ts_redq_state* st, int64_t E, int64_t
     if (hp->tau > 0.0)
         hipLaunchKernelGGL(polyak1_kernel, dim3((unsigned)ts::ceil_div((int64_t)E * pc, 256)), dim3(256), 0, s, st->critics_old,
                            st->critics, (int64_t)E * pc, (float)hp->tau, (float)(1.0 - hp->tau));
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+}  // extern "C"
+
+// ---- CQL (continuous, imitation/cql.py:203-400, arXiv 2006.04779 with the Cal-QL option) -----------------------------
+// SAC's networks, actor, entropy and target arithmetic plus the conservative term: the live critics see ONE stacked input
+//   X [B (1 + 3R), kc] = [ (s, a) | (s_rep, random) | (s_rep, pi(s)) | (s_rep, pi(s')) ]      (s_rep: every row R times)
+// in one twin forward / backward pass.  Order of an update (cql.py:268-390, not SAC's): actor step on the critics BEFORE
+// their update, alpha step, target with the updated actor and alpha, critic losses + CQL term, Lagrange step, the two
+// clipped critic steps, Polyak.
+namespace {
+
+struct CqlLossArgs {
+    // per critic k: Q of the data rows [B] and of the three repeated groups [B R] each, element i at q[i * qs] (qs = 32: the
+    // first column of a head block; 1: dense arrays), and the upstream gradients in the same layout
+    const float* q_data[2]; const float* q_rand[2]; const float* q_cur[2]; const float* q_next[2];
+    float* d_data[2]; float* d_rand[2]; float* d_cur[2]; float* d_next[2];
+    int qs;
+    const float* logp_cur; const float* logp_next;      // [B R], detached
+    const float* calib;                                  // nullable [B]: Cal-QL's calibration returns
+    const float* target;                                 // nullable [B]: else formed from the lagged critics' outputs below
+    const float* tq[2]; const float* logp_n; const float* log_alpha; float fixed_alpha;
+    const float* rew; const float* done; float gamma; float* target_out;
+    const float* cql_log_alpha;                          // nullable (no Lagrange multiplier: c = 1)
+    float alpha_min, alpha_max, weight, temp, rand_logp;
+    int64_t B; int R;
+    float* part;                                         // [2][3][gridDim.x]: sums of td^2, Q(s, a), logsumexp per workgroup
+};
+
+__device__ __forceinline__ float cql_alpha_value(const float* la, float lo, float hi) {
+    return la ? fminf(fmaxf(expf(*la), lo), hi) : 1.f;
+}
+
+// one thread per repeated row (and, for the first B of them, per data row); blockIdx.y = critic
+__global__ __launch_bounds__(256) void cql_loss_kernel(CqlLossArgs a) {
+    __shared__ float red[4];
+    const int k = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t BR = a.B * a.R;
+    const float c = cql_alpha_value(a.cql_log_alpha, a.alpha_min, a.alpha_max);      // the PRE-step multiplier
+    const float wc = a.weight * c;
+    float s_td = 0.f, s_q = 0.f, s_lse = 0.f;
+    if (i < a.B) {
+        float tgt;
+        if (a.target) tgt = a.target[i];
+        else {
+            const float alpha = a.log_alpha ? expf(*a.log_alpha) : a.fixed_alpha;
+            const float tq = sac_target_value(a.tq[0][i * 32], a.tq[1][i * 32], alpha, a.logp_n[i]);
+            tgt = a.rew[i] + (a.done[i] != 0.f ? 0.f : a.gamma) * tq;                  // cql.py:290, float32 throughout
+        }
+        if (k == 0 && a.target_out) a.target_out[i] = tgt;
+        const float q = a.q_data[k][i * a.qs];
+        const float td = q - tgt;
+        s_td = td * td;
+        s_q = q;
+        const float g = 2.f * td / (float)a.B - wc / (float)a.B;
+        if (a.qs == 32) store_head_row(a.d_data[k] + i * 32, g); else a.d_data[k][i] = g;
+    }
+    if (i < BR) {
+        const int64_t b = i / a.R;
+        float v[3] = {a.q_rand[k][i * a.qs] - a.rand_logp, a.q_cur[k][i * a.qs] - a.logp_cur[i],
+                      a.q_next[k][i * a.qs] - a.logp_next[i]};
+        float mask[3] = {1.f, 1.f, 1.f};
+        if (a.calib) {                                   // torch.max(value, returns): ties split the gradient
+            const float r = a.calib[b];
+#pragma unroll
+            for (int g = 0; g < 3; ++g) {
+                mask[g] = v[g] > r ? 1.f : (v[g] == r ? 0.5f : 0.f);
+                v[g] = fmaxf(v[g], r);
+            }
+        }
+        float z[3];
+#pragma unroll
+        for (int g = 0; g < 3; ++g) z[g] = v[g] / a.temp;
+        const float zm = fmaxf(fmaxf(z[0], z[1]), z[2]);                               // |Q| / T of any size: no overflow
+        const float se = expf(z[0] - zm) + expf(z[1] - zm) + expf(z[2] - zm);
+        const float lse = logf(se) + zm;
+        s_lse = lse;
+        const float up = wc / (float)BR;
+        float* dst[3] = {a.d_rand[k], a.d_cur[k], a.d_next[k]};
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            const float gr = up * expf(z[g] - lse) * mask[g];
+            if (a.qs == 32) store_head_row(dst[g] + i * 32, gr); else dst[g][i] = gr;
+        }
+    }
+    float* part = a.part + (size_t)k * 3 * gridDim.x;
+    const float t0 = block_sum_256(s_td, red);
+    __syncthreads();
+    const float t1 = block_sum_256(s_q, red);
+    __syncthreads();
+    const float t2 = block_sum_256(s_lse, red);
+    if (threadIdx.x == 0) { part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = t1; part[2 * gridDim.x + blockIdx.x] = t2; }
+}
+
+// one workgroup: the six partial-sum rows in workgroup order, the losses, cql_alpha / cql_alpha_loss and the Adam step of
+// the Lagrange multiplier (torch.optim.Adam's defaults, cql.py:190).  out9 = {mse1, mse2, logsumexp mean 1, 2, cql1, cql2,
+// cql_alpha, cql_alpha_loss, d cql_alpha_loss / d cql_log_alpha}; stats (nullable): ts_cql_update's slots 1, 2, 5, 6.
+struct CqlFinishArgs {
+    const float* part; int n_part; int64_t B; int R;
+    float weight, temp, threshold, alpha_min, alpha_max;
+    float* cql_log_alpha; float* m; float* v;            // nullable log_alpha: no Lagrange multiplier
+    int step_on; float lr_step, bc2_sqrt;
+    float* out9; float* stats;
+};
+__global__ __launch_bounds__(256) void cql_finish_kernel(CqlFinishArgs a) {
+    __shared__ float red[4];
+    __shared__ float tot[6];
+    for (int r = 0; r < 6; ++r) {
+        float s = 0.f;
+        for (int j = threadIdx.x; j < a.n_part; j += 256) s += a.part[(size_t)r * a.n_part + j];
+        const float t = block_sum_256(s, red);
+        if (threadIdx.x == 0) tot[r] = t;
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const float inv_b = 1.f / (float)a.B, inv_br = 1.f / (float)(a.B * a.R);
+    float mse[2], lse[2], raw[2], cql[2];
+    for (int k = 0; k < 2; ++k) {
+        mse[k] = tot[3 * k] * inv_b;
+        lse[k] = tot[3 * k + 2] * inv_br;
+        raw[k] = lse[k] * a.weight * a.temp - tot[3 * k + 1] * inv_b * a.weight;     // cql.py:353-364
+        cql[k] = raw[k];
+    }
+    float c = 1.f, c_loss = 0.f, g = 0.f;
+    if (a.cql_log_alpha) {
+        const float la = *a.cql_log_alpha;
+        const float e = expf(la);
+        c = fminf(fmaxf(e, a.alpha_min), a.alpha_max);
+        const float r0 = raw[0] - a.threshold, r1 = raw[1] - a.threshold;
+        cql[0] = c * r0; cql[1] = c * r1;
+        c_loss = -(cql[0] + cql[1]) * 0.5f;
+        // torch.clamp passes the gradient inside [min, max], bounds included
+        g = (e >= a.alpha_min && e <= a.alpha_max) ? -(r0 + r1) * 0.5f * e : 0.f;
+        if (a.step_on) {
+            float m = *a.m, v = *a.v;
+            m = m + (g - m) * 0.1f;
+            v = v * 0.999f + 0.001f * g * g;
+            const float denom = sqrtf(v) / a.bc2_sqrt + 1e-8f;
+            *a.cql_log_alpha = la + (-a.lr_step * m) / denom;
+            *a.m = m; *a.v = v;
+        }
+    }
+    if (a.out9) {
+        a.out9[0] = mse[0]; a.out9[1] = mse[1]; a.out9[2] = lse[0]; a.out9[3] = lse[1]; a.out9[4] = cql[0]; a.out9[5] = cql[1];
+        a.out9[6] = c; a.out9[7] = c_loss; a.out9[8] = g;
+    }
+    if (a.stats) { a.stats[1] = mse[0] + cql[0]; a.stats[2] = mse[1] + cql[1]; a.stats[5] = c; a.stats[6] = c_loss; }
+}
+
+// X [B (1 + 3R), kc]: the observation columns of every row, the batch's actions in the data rows and the random actions in
+// the first repeated group; the two policy groups' action columns are zero here (cql_policy_rep_kernel writes them), and so
+// is the padding.  Four columns per thread.
+__global__ __launch_bounds__(256) void cql_pack_kernel(const float* __restrict__ obs, const float* __restrict__ act,
+                                                       const float* __restrict__ random_act, int64_t B, int R, int obs_dim,
+                                                       int act_dim, int kc, float* __restrict__ X) {
+    using f32x4 = __attribute__((ext_vector_type(4))) float;
+    const int w4 = kc / 4;
+    const int64_t BR = B * R, N = B + 3 * BR;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= N * w4) return;
+    const int64_t row = t / w4;
+    const int j = (int)(t - row * w4) * 4;
+    int64_t b = row, i = 0;
+    int grp = -1;                                         // -1 data rows, 0 random, 1 pi(s), 2 pi(s')
+    if (row >= B) {
+        grp = (int)((row - B) / BR);
+        i = row - B - (int64_t)grp * BR;
+        b = i / R;
+    }
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int col = j + e;
+        float x = 0.f;
+        if (col < obs_dim) x = obs[b * obs_dim + col];
+        else if (col < obs_dim + act_dim) {
+            if (grp < 0) x = act[b * act_dim + col - obs_dim];
+            else if (grp == 0) x = random_act[i * act_dim + col - obs_dim];
+        }
+        v[e] = x;
+    }
+    *reinterpret_cast<f32x4*>(X + row * kc + j) = v;
+}
+
+// The updated actor ran once on [obs_next | obs] (2B head rows; the R repeated rows of an observation are identical).
+// Blocks [0, nb): the target's a' ~ pi(s') into xn_c and log pi'; [nb, nb + nr): R actions per row from pi(s) into X's
+// third group; [nb + nr, nb + 2 nr): R actions per row from pi(s') into X's fourth group (evaluated at s, cql.py:317).
+struct CqlPolicyArgs {
+    const float* head; const float* noise_next; const float* noise_cur_rep; const float* noise_next_rep;
+    int64_t B; int R, A, obs_dim, kc; float bound; unsigned nb, nr;
+    float* xn_c; float* logp_n; float* x_cur; float* logp_cur; float* x_next; float* logp_next;
+};
+__global__ __launch_bounds__(256) void cql_policy_rep_kernel(CqlPolicyArgs a) {
+    const int64_t BR = a.B * a.R;
+    if (blockIdx.x < a.nb)
+        sac_policy_item((int64_t)blockIdx.x * 256 + threadIdx.x, a.head, a.noise_next, a.B, a.A, 64, a.obs_dim, a.kc, a.bound, a.xn_c,
+                        nullptr, a.logp_n, nullptr, nullptr, nullptr);
+    else if (blockIdx.x < a.nb + a.nr)
+        sac_policy_item((int64_t)(blockIdx.x - a.nb) * 256 + threadIdx.x, a.head + a.B * 64, a.noise_cur_rep, BR, a.A, 64, a.obs_dim,
+                        a.kc, a.bound, a.x_cur, nullptr, a.logp_cur, nullptr, nullptr, nullptr, a.R);
+    else
+        sac_policy_item((int64_t)(blockIdx.x - a.nb - a.nr) * 256 + threadIdx.x, a.head, a.noise_next_rep, BR, a.A, 64, a.obs_dim,
+                        a.kc, a.bound, a.x_next, nullptr, a.logp_next, nullptr, nullptr, nullptr, a.R);
+}
+
+struct CqlHp { double gamma, weight, temp, threshold, amin, amax, lr, max_norm; bool lagrange; };
+
+int cql_hparams(const char* who, const double* h, int64_t B, int64_t R, CqlHp* o) {
+    TS_REQUIRE(h != nullptr, TS_ERR_INVALID_ARG, "%s: cql_hp is NULL", who);
+    for (int i = 0; i < TS_CQL_HP_COUNT; ++i)
+        TS_REQUIRE(std::isfinite(h[i]), TS_ERR_INVALID_ARG, "%s: cql_hp[%d] is not finite", who, i);
+    TS_REQUIRE(B >= 1 && R >= 1, TS_ERR_INVALID_ARG, "%s: B and R (num_repeat_actions) must be >= 1", who);
+    TS_REQUIRE(R <= 2147483647 && B <= 2147483647 / (1 + 3 * R), TS_ERR_INVALID_ARG, "%s: B (1 + 3 R) rows do not fit an int", who);
+    o->gamma = h[TS_CQL_HP_GAMMA]; o->weight = h[TS_CQL_HP_CQL_WEIGHT]; o->temp = h[TS_CQL_HP_TEMPERATURE];
+    o->lagrange = h[TS_CQL_HP_WITH_LAGRANGE] != 0.0; o->threshold = h[TS_CQL_HP_LAGRANGE_THRESHOLD];
+    o->amin = h[TS_CQL_HP_ALPHA_MIN]; o->amax = h[TS_CQL_HP_ALPHA_MAX]; o->lr = h[TS_CQL_HP_CQL_ALPHA_LR];
+    o->max_norm = h[TS_CQL_HP_MAX_GRAD_NORM];
+    TS_REQUIRE(o->temp > 0.0, TS_ERR_INVALID_ARG, "%s: temperature must be > 0", who);
+    TS_REQUIRE(o->amin <= o->amax, TS_ERR_INVALID_ARG, "%s: alpha_min > alpha_max", who);
+    return TS_OK;
+}
+
+void cql_finish_args(CqlFinishArgs* f, const CqlHp& h, int64_t B, int64_t R, const float* part, int n_part, float* la3,
+                     int64_t adam_step) {
+    f->part = part; f->n_part = n_part; f->B = B; f->R = (int)R;
+    f->weight = (float)h.weight; f->temp = (float)h.temp; f->threshold = (float)h.threshold;
+    f->alpha_min = (float)h.amin; f->alpha_max = (float)h.amax;
+    f->cql_log_alpha = h.lagrange ? la3 : nullptr; f->m = la3 ? la3 + 1 : nullptr; f->v = la3 ? la3 + 2 : nullptr;
+    f->step_on = h.lagrange && h.lr >= 0.0 && adam_step >= 1;
+    const double st = (double)std::max<int64_t>(adam_step, 1);
+    f->lr_step = (float)(h.lr / (1.0 - pow(0.9, st)));
+    f->bc2_sqrt = (float)sqrt(1.0 - pow(0.999, st));
+}
+
+}  // namespace
+
+extern "C" {
+
+int ts_cql_loss(ts_workspace* ws, const float* q_data, const float* target, const float* q_rand, const float* q_cur,
+                const float* q_next, const float* logp_cur, const float* logp_next, const float* calib,
+                const float* cql_log_alpha, int64_t B, int64_t R, int64_t act_dim, const double* cql_hp, float* d_data_out,
+                float* d_rep_out, float* loss_out9, ts_stream_t stream) {
+    CqlHp h;
+    if (int rc = cql_hparams("ts_cql_loss", cql_hp, B, R, &h)) return rc;
+    TS_REQUIRE(act_dim >= 1 && act_dim <= 32, TS_ERR_INVALID_ARG, "ts_cql_loss: act_dim in [1, 32]");
+    TS_REQUIRE(q_data && target && q_rand && q_cur && q_next && logp_cur && logp_next && d_data_out && d_rep_out && loss_out9 &&
+                   (!h.lagrange || cql_log_alpha),
+               TS_ERR_INVALID_ARG, "ts_cql_loss: NULL argument");
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_cql_loss: workspace is NULL");
+    hipStream_t s = ts::as_stream(stream);
+    const int64_t BR = B * R;
+    const unsigned gb = (unsigned)ts::ceil_div(BR, 256);
+    if (int rc = ts::ws_reserve(ws, al(4 * 6 * (size_t)gb) + 4096)) return rc;
+    Carve c{static_cast<char*>(ws->base)};
+    float* part = c.take<float>(6 * (size_t)gb);
+    CqlLossArgs a{};
+    for (int k = 0; k < 2; ++k) {
+        a.q_data[k] = q_data + k * B; a.q_rand[k] = q_rand + k * BR; a.q_cur[k] = q_cur + k * BR; a.q_next[k] = q_next + k * BR;
+        a.d_data[k] = d_data_out + k * B;
+        a.d_rand[k] = d_rep_out + (3 * k) * BR; a.d_cur[k] = d_rep_out + (3 * k + 1) * BR; a.d_next[k] = d_rep_out + (3 * k + 2) * BR;
+    }
+    a.qs = 1; a.logp_cur = logp_cur; a.logp_next = logp_next; a.calib = calib; a.target = target;
+    a.cql_log_alpha = h.lagrange ? cql_log_alpha : nullptr;
+    a.alpha_min = (float)h.amin; a.alpha_max = (float)h.amax; a.weight = (float)h.weight; a.temp = (float)h.temp;
+    a.rand_logp = (float)log(pow(0.5, (double)act_dim));                                // cql.py:236
+    a.B = B; a.R = (int)R; a.part = part;
+    hipLaunchKernelGGL(cql_loss_kernel, dim3(gb, 2), dim3(256), 0, s, a);
+    CqlFinishArgs f{};
+    cql_finish_args(&f, h, B, R, part, (int)gb, const_cast<float*>(cql_log_alpha), 0);      // (step 0: no Adam step, read only)
+    f.out9 = loss_out9;
+    hipLaunchKernelGGL(cql_finish_kernel, dim3(1), dim3(256), 0, s, f);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+int ts_cql_update(ts_workspace* ws, const ts_sac_state* st, float* cql_log_alpha3, int64_t adam_step, const float* obs,
+                  const float* act, const float* rew, const float* done, const float* obs_next, const float* calib,
+                  const float* noise_actor, const float* noise_next, const float* random_act, const float* noise_rep_cur,
+                  const float* noise_rep_next, int64_t B, int64_t R, int64_t obs_dim, int64_t act_dim,
+                  const ts_mlp_trunk* trunk, const ts_sac_hparams* hp, const double* cql_hp, float* stats_out7,
+                  float* target_out, float* grads_out, ts_stream_t stream) {
+    CqlHp h;
+    if (int rc = cql_hparams("ts_cql_update", cql_hp, B, R, &h)) return rc;
+    TS_REQUIRE(st && hp && obs && act && rew && done && obs_next && noise_actor && noise_next && random_act && noise_rep_cur &&
+                   noise_rep_next && stats_out7 && adam_step >= 1 && (!h.lagrange || cql_log_alpha3),
+               TS_ERR_INVALID_ARG, "ts_cql_update: bad argument");
+    TS_REQUIRE(st->actor && st->critic1 && st->critic2 && st->critic1_old && st->critic2_old && st->actor_m && st->actor_v &&
+                   st->critic1_m && st->critic1_v && st->critic2_m && st->critic2_v,
+               TS_ERR_INVALID_ARG, "ts_cql_update: NULL state pointer");
+    TS_REQUIRE(!hp->auto_alpha || (st->log_alpha && st->log_alpha_m && st->log_alpha_v), TS_ERR_INVALID_ARG,
+               "ts_cql_update: auto alpha needs log_alpha and its Adam moments");
+    Dims d;
+    if (int rc = make_dims(trunk, obs_dim, act_dim, &d)) return rc;
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_cql_update: workspace is NULL");
+    hipStream_t s = ts::as_stream(stream);
+    const int64_t BR = B * R, N = B + 3 * BR;
+    const Mlp ma = make_mlp((int)B, d.ka, 64, d.hid, d.depth, d.fn), ma2 = make_mlp((int)(2 * B), d.ka, 64, d.hid, d.depth, d.fn);
+    const Mlp mc = make_mlp((int)B, d.kc, 32, d.hid, d.depth, d.fn), mx = make_mlp((int)N, d.kc, 32, d.hid, d.depth, d.fn);
+    const size_t slab = std::max(std::max(slab_floats(ma), slab_floats(mc)), slab_floats(mx));
+    const size_t spl = std::max(std::max(split_floats(ma2), split_floats(mc)), std::max(split_floats(ma), split_floats(mx)));
+    const int64_t pa = ma.total(), pc = mc.total();
+    const unsigned gb = (unsigned)ts::ceil_div(B, 256), gr = (unsigned)ts::ceil_div(BR, 256);
+
+    // the workspace is carved twice with the same code: once from address 0 for its size, once for real
+    struct Bufs {
+        float *x_a2, *x_p, *xn_c, *X, *dx1, *dx2, *d_q1, *d_q2, *d_head, *dX, *logp, *keep, *logp_n, *logp_cur, *logp_next;
+        float *grad_a, *grad_c[2], *split[2], *norm_part, *loss_part, *part, *alpha3;
+        Act aa, aa2, a1, a2, t1, t2, x1, x2;
+        BwdScratch sc[2], scx[2];
+    } w;
+    auto carve = [&](char* base) {
+        Carve c{base};
+        w.x_a2 = c.take<float>(2 * B * d.ka); w.x_p = c.take<float>(B * d.kc); w.xn_c = c.take<float>(B * d.kc);
+        w.X = c.take<float>(N * d.kc);
+        w.dx1 = c.take<float>(B * d.kc); w.dx2 = c.take<float>(B * d.kc);
+        w.d_q1 = c.take<float>(B * 32); w.d_q2 = c.take<float>(B * 32); w.d_head = c.take<float>(B * 64);
+        w.dX = c.take<float>(2 * N * 32);
+        w.logp = c.take<float>(B); w.keep = c.take<float>(B * 3 * d.act); w.logp_n = c.take<float>(B);
+        w.logp_cur = c.take<float>(BR); w.logp_next = c.take<float>(BR);
+        w.grad_a = c.take<float>(pa); w.grad_c[0] = c.take<float>(pc); w.grad_c[1] = c.take<float>(pc);
+        w.split[0] = c.take<float>(spl); w.split[1] = c.take<float>(spl);
+        w.norm_part = c.take<float>(1024); w.loss_part = c.take<float>(gb); w.part = c.take<float>(6 * (size_t)gr);
+        w.alpha3 = c.take<float>(4);
+        w.aa = take_act(c, B, 64, d.hid, d.depth); w.aa2 = take_act(c, 2 * B, 64, d.hid, d.depth);
+        w.a1 = take_act(c, B, 32, d.hid, d.depth); w.a2 = take_act(c, B, 32, d.hid, d.depth);
+        w.t1 = take_act(c, B, 32, d.hid, d.depth); w.t2 = take_act(c, B, 32, d.hid, d.depth);
+        w.x1 = take_act(c, N, 32, d.hid, d.depth); w.x2 = take_act(c, N, 32, d.hid, d.depth);
+        for (int k = 0; k < 2; ++k) w.sc[k] = take_scratch(c, B, d.hid, d.depth, slab);
+        for (int k = 0; k < 2; ++k) w.scx[k] = take_scratch(c, N, d.hid, d.depth, slab);
+        return (size_t)(c.p - base);
+    };
+    const size_t bytes = carve(nullptr) + 4096;
+    if (int rc = ts::ws_reserve(ws, bytes)) return rc;
+    carve(static_cast<char*>(ws->base));
+
+    const float* log_alpha = hp->auto_alpha ? st->log_alpha : nullptr;
+    float* crit[2] = {st->critic1, st->critic2};
+    float* crit_m[2] = {st->critic1_m, st->critic2_m};
+    float* crit_v[2] = {st->critic1_v, st->critic2_v};
+    float* g_c[2] = {grads_out ? grads_out : w.grad_c[0], grads_out ? grads_out + pc : w.grad_c[1]};
+    float* g_a = grads_out ? grads_out + 2 * pc : w.grad_a;
+    float* x_a = w.x_a2 + B * d.ka;                        // x_a2 = [obs_next | obs]
+
+    // packing: the actor's inputs of both observations, the observation columns of the actor pass's and the target's critic
+    // inputs, and X
+    const unsigned pkb = (unsigned)ts::ceil_div(B * (d.ka + d.kc) / 4, 256);
+    hipLaunchKernelGGL(sac_pack_kernel, dim3(pkb), dim3(256), 0, s, obs_next, (const float*)nullptr, B, d.obs, d.act, d.ka, d.kc,
+                       w.x_a2, w.xn_c, (float*)nullptr);
+    hipLaunchKernelGGL(sac_pack_kernel, dim3(pkb), dim3(256), 0, s, obs, (const float*)nullptr, B, d.obs, d.act, d.ka, d.kc, x_a,
+                       w.x_p, (float*)nullptr);
+    hipLaunchKernelGGL(cql_pack_kernel, dim3((unsigned)ts::ceil_div(N * (d.kc / 4), 256)), dim3(256), 0, s, obs, act, random_act, B,
+                       (int)R, d.obs, d.act, d.kc, w.X);
+    TS_LAUNCH_CHECK();
+
+    // 1. actor step (cql.py:275-276) on the critics before their update: SAC's launches, no gradient clipping
+    const Act a12[2] = {w.a1, w.a2};
+    if (int rc = mlp_forward(s, ws, ma, st->actor, x_a, w.aa, w.split[0])) return rc;
+    hipLaunchKernelGGL(sac_policy_kernel, dim3((unsigned)ts::ceil_div(B * 32, 256)), dim3(256), 0, s, w.aa.out, noise_actor, B, d.act,
+                       64, d.obs, d.kc, d.bound, w.x_p, (float*)nullptr, w.logp, w.keep);
+    TS_LAUNCH_CHECK();
+    if (int rc = mlp_forward_twin(s, ws, mc, crit, w.x_p, a12, w.split)) return rc;
+    hipLaunchKernelGGL(sac_actor_loss_mb_kernel, dim3(gb), dim3(256), 0, s, w.a1.out, w.a2.out, w.logp, log_alpha, (float)hp->alpha, B,
+                       w.d_q1, w.d_q2, w.loss_part);
+    TS_LAUNCH_CHECK();
+    {
+        const float* dq[2] = {w.d_q1, w.d_q2};
+        float* dxs[2] = {w.dx1, w.dx2};
+        if (int rc = mlp_backward_twin(s, ws, mc, crit, w.x_p, a12, dq, dxs, d.obs, d.obs + d.act, w.sc)) return rc;
+    }
+    hipLaunchKernelGGL(sac_policy_bwd_kernel, dim3((unsigned)ts::ceil_div(B * 32, 256)), dim3(256), 0, s, w.aa.out, noise_actor, w.keep,
+                       w.dx1, w.dx2, log_alpha, (float)hp->alpha, B, d.act, 64, d.obs, d.kc, d.bound, w.d_head);
+    TS_LAUNCH_CHECK();
+    if (int rc = mlp_backward(s, ws, ma, st->actor, x_a, w.aa, w.d_head, g_a, nullptr, 0, 0, w.sc[0])) return rc;
+    if (hp->actor_lr >= 0.0)
+        if (int rc = ts::adam_step(s, st->actor, st->actor_m, st->actor_v, g_a, pa, adam_step, hp->actor_lr, hp->beta1, hp->beta2,
+                                   hp->adam_eps, 0.0, w.norm_part))
+            return rc;
+
+    // 2. alpha.update(-log_pi) (cql.py:278-279); the actor loss statistic
+    {
+        AlphaArgs al2{};
+        al2.logp = w.logp; al2.B = B; al2.target_entropy = (float)hp->target_entropy;
+        al2.log_alpha = hp->auto_alpha ? st->log_alpha : nullptr; al2.m = st->log_alpha_m; al2.v = st->log_alpha_v;
+        double alr = hp->alpha_lr;
+        if (hp->auto_alpha && alr < 0.0) {                 // a negative rate skips the step: the kernel steps a scratch copy by 0
+            TS_HIP_CHECK(hipMemcpyAsync(w.alpha3, st->log_alpha, sizeof(float), hipMemcpyDeviceToDevice, s));
+            TS_HIP_CHECK(hipMemsetAsync(w.alpha3 + 1, 0, 2 * sizeof(float), s));
+            al2.log_alpha = w.alpha3; al2.m = w.alpha3 + 1; al2.v = w.alpha3 + 2;
+            alr = 0.0;
+        }
+        const double bc1 = 1.0 - pow(hp->beta1, (double)adam_step), bc2 = 1.0 - pow(hp->beta2, (double)adam_step);
+        al2.lr_step = (float)(alr / bc1); al2.beta1 = (float)hp->beta1; al2.beta2 = (float)hp->beta2;
+        al2.omb1 = (float)(1.0 - hp->beta1); al2.omb2 = (float)(1.0 - hp->beta2);
+        al2.bc2_sqrt = (float)sqrt(bc2); al2.eps = (float)hp->adam_eps;
+        al2.alpha_loss = stats_out7 + 4; al2.alpha_out = stats_out7 + 3; al2.fixed_alpha = (float)hp->alpha;
+        hipLaunchKernelGGL(sac_alpha_kernel, dim3(1), dim3(1024), 0, s, al2);
+        hipLaunchKernelGGL(sac_loss_finish_kernel, dim3(1), dim3(64), 0, s, w.loss_part, stats_out7, (const float*)nullptr,
+                           (float*)nullptr, (int)gb, B);
+        TS_LAUNCH_CHECK();
+    }
+
+    // 3. the updated actor on [obs_next | obs]: a' and log pi' of the target, R actions per row for X's two policy groups
+    if (int rc = mlp_forward(s, ws, ma2, st->actor, w.x_a2, w.aa2, w.split[0])) return rc;
+    {
+        CqlPolicyArgs p{};
+        p.head = w.aa2.out; p.noise_next = noise_next; p.noise_cur_rep = noise_rep_cur; p.noise_next_rep = noise_rep_next;
+        p.B = B; p.R = (int)R; p.A = d.act; p.obs_dim = d.obs; p.kc = d.kc; p.bound = d.bound;
+        p.nb = (unsigned)ts::ceil_div(B * 32, 256); p.nr = (unsigned)ts::ceil_div(BR * 32, 256);
+        p.xn_c = w.xn_c; p.logp_n = w.logp_n;
+        p.x_cur = w.X + (B + BR) * d.kc; p.logp_cur = w.logp_cur;
+        p.x_next = w.X + (B + 2 * BR) * d.kc; p.logp_next = w.logp_next;
+        hipLaunchKernelGGL(cql_policy_rep_kernel, dim3(p.nb + 2 * p.nr), dim3(256), 0, s, p);
+        TS_LAUNCH_CHECK();
+    }
+    // the lagged critics on (s', a'); the live critics on X
+    {
+        const float* lag[2] = {st->critic1_old, st->critic2_old};
+        const Act t12[2] = {w.t1, w.t2};
+        if (int rc = mlp_forward_twin(s, ws, mc, lag, w.xn_c, t12, w.split)) return rc;
+    }
+    const Act x12[2] = {w.x1, w.x2};
+    if (int rc = mlp_forward_twin(s, ws, mx, crit, w.X, x12, w.split)) return rc;
+
+    // 4. target, critic losses, CQL term and every upstream gradient row; 5. the Lagrange step
+    float* dXk[2] = {w.dX, w.dX + N * 32};
+    {
+        CqlLossArgs a{};
+        for (int k = 0; k < 2; ++k) {
+            const float* q = x12[k].out;
+            a.q_data[k] = q; a.q_rand[k] = q + B * 32; a.q_cur[k] = q + (B + BR) * 32; a.q_next[k] = q + (B + 2 * BR) * 32;
+            a.d_data[k] = dXk[k]; a.d_rand[k] = dXk[k] + B * 32; a.d_cur[k] = dXk[k] + (B + BR) * 32;
+            a.d_next[k] = dXk[k] + (B + 2 * BR) * 32;
+        }
+        a.qs = 32; a.logp_cur = w.logp_cur; a.logp_next = w.logp_next; a.calib = calib; a.target = nullptr;
+        a.tq[0] = w.t1.out; a.tq[1] = w.t2.out; a.logp_n = w.logp_n; a.log_alpha = log_alpha; a.fixed_alpha = (float)hp->alpha;
+        a.rew = rew; a.done = done; a.gamma = (float)h.gamma; a.target_out = target_out;
+        a.cql_log_alpha = h.lagrange ? cql_log_alpha3 : nullptr;
+        a.alpha_min = (float)h.amin; a.alpha_max = (float)h.amax; a.weight = (float)h.weight; a.temp = (float)h.temp;
+        a.rand_logp = (float)log(pow(0.5, (double)d.act));
+        a.B = B; a.R = (int)R; a.part = w.part;
+        hipLaunchKernelGGL(cql_loss_kernel, dim3(gr, 2), dim3(256), 0, s, a);
+        CqlFinishArgs f{};
+        cql_finish_args(&f, h, B, R, w.part, (int)gr, cql_log_alpha3, adam_step);
+        f.stats = stats_out7;
+        hipLaunchKernelGGL(cql_finish_kernel, dim3(1), dim3(256), 0, s, f);
+        TS_LAUNCH_CHECK();
+    }
+
+    // 6. the live critics' backward on X (no input gradient), each critic's clipped Adam step; 7. Polyak
+    if (fused_backward(mx, false, 0, 0)) {
+        const float* dh2[2] = {dXk[0], dXk[1]};
+        const float* xs2[2] = {w.X, w.X};
+        if (int rc = mlp_backward_twin(s, ws, mx, crit, w.X, x12, dh2, nullptr, 0, 0, w.scx)) return rc;
+        if (int rc = mlp_weight_grads(s, ws, 2, mx, xs2, x12, dh2, g_c, w.scx)) return rc;
+    } else {
+        for (int k = 0; k < 2; ++k)
+            if (int rc = mlp_backward(s, ws, mx, crit[k], w.X, x12[k], dXk[k], g_c[k], nullptr, 0, 0, w.scx[k])) return rc;
+    }
+    if (hp->critic_lr >= 0.0)
+        for (int k = 0; k < 2; ++k)
+            if (int rc = ts::adam_step(s, crit[k], crit_m[k], crit_v[k], g_c[k], pc, adam_step, hp->critic_lr, hp->beta1, hp->beta2,
+                                       hp->adam_eps, h.max_norm > 0.0 ? h.max_norm : 0.0, w.norm_part))
+                return rc;
+    if (hp->tau > 0.0)
+        hipLaunchKernelGGL(polyak2_kernel, dim3((unsigned)ts::ceil_div(pc, 256)), dim3(256), 0, s, st->critic1_old, st->critic1,
+                           st->critic2_old, st->critic2, pc, (float)hp->tau, (float)(1.0 - hp->tau));
     TS_LAUNCH_CHECK();
     return TS_OK;
 }

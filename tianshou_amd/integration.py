@@ -2823,3 +2823,192 @@ def make_hip_td3bc(ref=None):
     `weight`; a prioritized buffer works as well.  `alpha` is read from the algorithm at every update; the statistics are
     TD3TrainingStats.  `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
     return _make_hip_det(True, ref, bc=True)
+
+
+# ---------------------------------------------------------------------------------------------------
+# continuous CQL (imitation/cql.py) on the nets of examples/offline/d4rl_cql.py
+# ---------------------------------------------------------------------------------------------------
+def make_hip_cql(ref=None):
+    """Returns HipCQL(CQL): `_update_with_batch` of imitation/cql.py:268-400 on the engine (tianshou_amd/cql.py over
+    ts_cql_update).  Networks as HipSAC's (Net trunks of one depth, single-Linear mu / sigma / Q heads), Adam on the three
+    optimizers, a fixed alpha or AutoAlpha.  `_preprocess_batch` only takes the device mirror of the buffer and the indices;
+    `_update_with_batch` gathers the rows on the device: obs, act, rew, obs_next and `done` from the mirror,
+    `calibration_returns` (calibrated=True; `process_buffer` stays the reference's and adds it to the buffer once) from a column
+    uploaded once per mirror.  The five random tensors of an update are drawn from torch's default generator in the reference's
+    order and calls (`update_noise="torch"`: randn [B, A] twice, `FloatTensor(B R, A).uniform_(-min_action, max_action)`, randn
+    [B R, A] twice -- with the defaults min_action = -1, max_action = 1 that is uniform_(1, 1), every random action 1.0, as in the
+    reference) or from the engine's Philox stream (`"device"`, the default, keyed as in HipSAC).  `cql_weight`, `temperature`,
+    `lagrange_threshold` and the learning rates are read from the algorithm at every update.
+    The Lagrange multiplier LEARNS, as in the reference on the CPU; on a cuda device the reference's `cql_log_alpha.to(device)`
+    is a copy its optimizer never steps.  The write-back stores `cql_log_alpha` and `cql_alpha_optim`'s Adam state (step = the
+    number of updates); since the reference keeps neither in `state_dict()`, HipCQL adds them under `_hip_cql_alpha` and loads
+    them from there, so a checkpoint resumes.  The collector's `policy.forward` stays the reference's.
+    `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    CQL = _ref(ref, "tianshou.algorithm.imitation.cql", "CQL")
+    CQLTrainingStats = _ref(ref, "tianshou.algorithm.imitation.cql", "CQLTrainingStats")
+    AutoAlpha = _ref(ref, "tianshou.algorithm.modelfree.sac", "AutoAlpha")
+
+    from . import cql as Q
+    from . import sac as S
+
+    class HipCQL(_HipGlue, CQL):
+        _HIP_LR = (("actor_lr", "policy_optim"), ("critic_lr", "critic_optim"), ("critic_lr", "critic2_optim"),
+                   ("alpha_lr", "alpha"), ("cql_alpha_lr", "cql_alpha_optim"))
+        _HIP_STATE_KEY = "_hip_cql_alpha"
+
+        def __init__(self, *args, device="cuda", update_noise="device", noise_seed=None, **kwargs):
+            super().__init__(*args, **kwargs)
+            if update_noise not in ("device", "torch"):
+                raise ValueError("update_noise must be 'device' or 'torch'")
+            self._hip_update_noise, self._hip_noise_calls = update_noise, 0
+            self._hip_noise_key = int(torch.initial_seed() % (2**31 - 1)) if noise_seed is None else int(noise_seed)
+            self._hip_device = torch.device(device)
+            keys = _ac_nets(self, "HipCQL", "networks must be those of examples/offline/d4rl_cql.py (Net trunks of one depth, "
+                            "1 .. 6 hidden layers, single-Linear mu / sigma / Q heads)",
+                            (("actor", self.policy.actor, S.actor_keys), ("critic1", self.critic, S.critic_keys),
+                             ("critic2", self.critic2, S.critic_keys)), (self.policy_optim, self.critic_optim, self.critic2_optim))
+            self._hip_akeys, self._hip_ckeys = keys["actor"], keys["critic1"]
+            self._hip_bound = _actor_bound(self.policy.actor)
+            g = self.cql_alpha_optim.param_groups[0]
+            if type(self.cql_alpha_optim).__name__ != "Adam" or tuple(g["betas"]) != (0.9, 0.999) or g["eps"] != 1e-8:
+                raise NotImplementedError("HipCQL: cql_alpha_optim must be torch.optim.Adam with its default betas / eps")
+            self._hip_engine = None
+            self._hip_glue_init()
+
+        def hip_extra_state(self) -> dict:
+            return {"update_noise_calls": int(self._hip_noise_calls)}
+
+        def load_hip_extra_state(self, state: dict) -> None:
+            if "update_noise_calls" in state:
+                self._hip_noise_calls = int(state["update_noise_calls"])
+
+        def _hip_cql_leaf(self):
+            """The tensor `cql_alpha_optim` steps (cql.py:188-191: `self.cql_log_alpha` itself on the CPU, its source on cuda)."""
+            return self.cql_alpha_optim.param_groups[0]["params"][0]
+
+        def _hip_cql_fields(self) -> dict:
+            mg = self.critic_optim._max_grad_norm
+            return dict(cql_alpha_lr=float(self.cql_alpha_optim.param_groups[0]["lr"]), cql_weight=float(self.cql_weight),
+                        temperature=float(self.temperature), with_lagrange=bool(self.with_lagrange),
+                        lagrange_threshold=float(self.lagrange_threshold), min_action=float(self.min_action),
+                        max_action=float(self.max_action), num_repeat_actions=int(self.num_repeat_actions),
+                        alpha_min=float(self.alpha_min), alpha_max=float(self.alpha_max), max_grad_norm=0.0 if mg is None else float(mg),
+                        calibrated=bool(self.calibrated))
+
+        def _engine(self):
+            if self._hip_engine is None:
+                ga, gc = _adam_of(self.policy_optim)[1], _adam_of(self.critic_optim)[1]
+                flats = {p.name: p.flat() for p in self._hip_parts()}
+                cfg = Q.CQLConfig(gamma=self.gamma, tau=self.tau, actor_lr=ga["lr"], critic_lr=gc["lr"], betas=tuple(ga["betas"]),
+                                  adam_eps=ga["eps"], **_ac_entropy_fields(self, AutoAlpha), **self._hip_cql_fields())
+                eng = Q.CQLEngine(self._hip_obs_dim, self._hip_act_dim, flats["actor"], flats["critic1"], flats["critic2"], cfg,
+                                  hidden=self._hip_hidden, depth=self._hip_depth, max_action=self._hip_bound, activation=self._hip_actfn)
+                eng = _ac_load(self, eng)                      # resume: lagged critics, Adam moments / steps of a loaded checkpoint
+                leaf = self._hip_cql_leaf()
+                eng.cql_log_alpha[0] = float(leaf.detach().reshape(-1)[0])
+                st = self.cql_alpha_optim.state.get(leaf, {})
+                if "exp_avg" in st:
+                    eng.cql_log_alpha_m[0], eng.cql_log_alpha_v[0] = float(st["exp_avg"]), float(st["exp_avg_sq"])
+                    eng.adam_step = max(eng.adam_step, int(float(st["step"])))
+                self._hip_engine = eng
+            return self._hip_engine
+
+        def _hip_parts(self):
+            o, a, h, dev, sz = self._hip_obs_dim, self._hip_act_dim, self._hip_hidden, self._hip_device, self._hip_sizes
+
+            def part(name, mod, old, optim, keys, fwd, back):
+                return _ACPart(name, mod, old, optim, keys, lambda t: fwd(t, o, a, dev, hidden=h),
+                               lambda f: back(f, o, a, h, sizes=sz[name]), "adam_step", True)
+
+            return (part("actor", self.policy.actor, None, self.policy_optim, self._hip_akeys, S.actor_flat_from_torch, S.actor_flat_to_torch),
+                    part("critic1", self.critic, self.critic_old.module, self.critic_optim, self._hip_ckeys,
+                         S.critic_flat_from_torch, S.critic_flat_to_torch),
+                    part("critic2", self.critic2, self.critic2_old.module, self.critic2_optim, self._hip_ckeys,
+                         S.critic_flat_from_torch, S.critic_flat_to_torch))
+
+        def _preprocess_batch(self, batch, buffer, indices):
+            _ac_begin(self, "HipCQL", buffer, indices)         # the mirror and the indices; the rows are gathered on the device
+            return batch
+
+        def _hip_calibration_column(self, buffer, m):
+            """`calibration_returns` of the buffer (cql.py:244-266) as a float32 device column, uploaded once per mirror."""
+            have = self.__dict__.get("_hip_calib")
+            if have is None or have[0] is not m:
+                col = getattr(buffer._meta, "calibration_returns", None)
+                if col is None:
+                    raise RuntimeError("HipCQL: calibrated=True needs `calibration_returns` in the buffer (call process_buffer first)")
+                have = self.__dict__["_hip_calib"] = (m, torch.as_tensor(np.asarray(col, np.float32), device=self._hip_device))
+            return have[1]
+
+        def _hip_noises(self, b: int, r: int, a: int):
+            """The five random tensors of one update, in the reference's draw order."""
+            if self._hip_update_noise == "torch":
+                n1, n2 = torch.randn(b, a), torch.randn(b, a)
+                ra = torch.FloatTensor(b * r, a).uniform_(-self.min_action, self.max_action)          # cql.py:303-307
+                return n1, n2, ra, torch.randn(b * r, a), torch.randn(b * r, a)
+            from .buffer import normal_noise
+
+            key, c = self._hip_noise_key ^ 0xC91, self._hip_noise_calls
+            self._hip_noise_calls += 5
+            dev = self._hip_device
+            n = [normal_noise(s, key, c + i, dev) for i, s in enumerate(((b, a), (b, a), (b * r, a), (b * r, a), (b * r, a)), 1)]
+            # uniform_(lo, hi) from the third stream: Phi(z) is uniform on (0, 1)
+            lo, hi = -float(self.min_action), float(self.max_action)
+            ra = lo + (hi - lo) * (0.5 * (1.0 + torch.erf(n[2] * 0.7071067811865476)))
+            return n[0], n[1], ra, n[3], n[4]
+
+        def _update_with_batch(self, batch):
+            self._hip_refresh_lr()
+            from .buffer import gather_rows_multi
+
+            eng, m, idx = self._hip_engine, self._hip_mirror, self._hip_idx
+            for k, v in self._hip_cql_fields().items():          # read at every update, as the learning rates
+                if k in ("num_repeat_actions", "calibrated", "with_lagrange") and getattr(eng.cfg, k) != v:
+                    raise NotImplementedError(f"HipCQL: `{k}` changed after the engine was built (call hip_invalidate())")
+                setattr(eng.cfg, k, v)
+            obs, act, obs_next = gather_rows_multi([m.obs, m.act, m.obs_next], idx)
+            rew, done = m.rew[idx].to(torch.float32), m.done[idx].to(torch.float32)
+            calib = self._hip_calibration_column(self._hip_mirror_src, m)[idx] if eng.cfg.calibrated else None
+            b = int(idx.numel())
+            stats = eng.update_with_batch(obs, act, rew, done, obs_next, *self._hip_noises(b, eng.cfg.num_repeat_actions, eng.act_dim),
+                                          calib=calib)
+            s = stats.cpu().numpy()                                               # one D2H per update()
+            self._hip_after_update()
+            auto, lag = eng.cfg.auto_alpha, eng.cfg.with_lagrange
+            return CQLTrainingStats(actor_loss=float(s[0]), critic1_loss=float(s[1]), critic2_loss=float(s[2]), alpha=float(s[3]),
+                                    alpha_loss=float(s[4]) if auto else None, cql_alpha_loss=float(s[6]) if lag else None,
+                                    cql_alpha=float(s[5]) if lag else None)
+
+        def _hip_write_back(self) -> None:
+            _ac_write_back(self)
+            eng = self.__dict__.get("_hip_engine_obj")
+            if eng is None or not eng.cfg.with_lagrange:
+                return
+            leaf = self._hip_cql_leaf()
+            with torch.no_grad():
+                leaf.copy_(eng.cql_log_alpha.reshape(leaf.shape))
+                if self.cql_log_alpha is not leaf:
+                    self.cql_log_alpha.copy_(eng.cql_log_alpha.reshape(self.cql_log_alpha.shape))
+            if eng.adam_step:
+                store_adam_state(self.cql_alpha_optim, [leaf], [eng.cql_log_alpha_m], [eng.cql_log_alpha_v], eng.adam_step)
+
+        def state_dict(self, *args, **kwargs):
+            d = super().state_dict(*args, **kwargs)
+            d[self._HIP_STATE_KEY] = {"cql_log_alpha": self._hip_cql_leaf().detach().clone(), "optim": self.cql_alpha_optim.state_dict()}
+            return d
+
+        def load_state_dict(self, state_dict, *args, **kwargs):
+            state_dict = dict(state_dict)
+            extra = state_dict.pop(self._HIP_STATE_KEY, None)
+            out = super().load_state_dict(state_dict, *args, **kwargs)
+            if extra is not None:
+                leaf = self._hip_cql_leaf()
+                with torch.no_grad():
+                    leaf.copy_(extra["cql_log_alpha"].reshape(leaf.shape))
+                    if self.cql_log_alpha is not leaf:
+                        self.cql_log_alpha.copy_(extra["cql_log_alpha"].reshape(self.cql_log_alpha.shape))
+                self.cql_alpha_optim.load_state_dict(extra["optim"])
+                self._hip_invalidate()
+            return out
+
+    return HipCQL
