@@ -496,6 +496,13 @@ struct LearnGraphs {
     hipStream_t origin;             // the stream the enqueue is captured from
 };
 static void learn_graphs_drop(LearnGraphs* g) {
+    // The last replay may still be running (the caller does not synchronise between updates: a changed seed key drops the
+    // graphs one call after their launch): hipGraphExecDestroy does not wait for it, and an executable graph freed under its
+    // own launch takes the process down.  Every replay ends on the stream of the key it was captured for.
+    bool any = false;
+    for (auto& row : g->exec)
+        for (auto& e : row) any = any || e != nullptr;
+    if (any) (void)hipStreamSynchronize(g->key.stream);
     for (auto& row : g->exec)
         for (auto& e : row)
             if (e) { (void)hipGraphExecDestroy(e); e = nullptr; }

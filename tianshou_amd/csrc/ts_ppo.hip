@@ -341,6 +341,22 @@ __device__ __forceinline__ void trunk_forward(const float* lds, int net, const f
     }
 }
 
+// the first N (<= 4) of four consecutive per-action floats (a half of a head-weight row, of a broadcast `dout` row): the
+// read is as wide as the actions that are used -- b128 for 3 or 4, b64 for 2, b32 for 1, none for N <= 0 (zeros)
+template <int N>
+__device__ __forceinline__ f32x4 ld_head(const float* p) {
+    if constexpr (N >= 3) {
+        return *reinterpret_cast<const f32x4*>(p);
+    } else if constexpr (N == 2) {
+        const f32x2 v = *reinterpret_cast<const f32x2*>(p);
+        return f32x4{v[0], v[1], 0.f, 0.f};
+    } else if constexpr (N == 1) {
+        return f32x4{p[0], 0.f, 0.f, 0.f};
+    } else {
+        return f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+
 // head on the VALU: out[a] = sum_f h2[f] * WH[a][f] over the lane's 32 features, halves combined
 template <int KS1, int NN, int NA>
 __device__ __forceinline__ void head_forward(const float* lds, int net, int h, const f32x16 (&h2)[2],
@@ -357,11 +373,11 @@ __device__ __forceinline__ void head_forward(const float* lds, int net, int h, c
             if constexpr (NA == 1) {
                 out[0] += h2[t][r] * p[0];
             } else {
-                const f32x4 w0 = *reinterpret_cast<const f32x4*>(p);
-                const f32x4 w1 = *reinterpret_cast<const f32x4*>(p + 4);
+                const f32x4 w0 = ld_head<NA>(p);
+                const f32x4 w1 = ld_head<NA - 4>(p + 4);
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
-                    out[a] += h2[t][r] * w0[a];
+                    if (a < NA) out[a] += h2[t][r] * w0[a];
                     if (a + 4 < NA) out[a + 4] += h2[t][r] * w1[a];
                 }
             }
@@ -747,17 +763,27 @@ __device__ __forceinline__ void dw1_wave(const float* T, int wave, int lane, flo
     }
 }
 
+// a[k] for k < N, 0 beyond (k is a constant wherever this is used)
+template <int N>
+__device__ __forceinline__ float at_or_zero(const float (&a)[N], int k) { return k < N ? a[k] : 0.f; }
+
 // forward, loss and backward of one net for the wave's 32 samples, up to dZ2 (returned in h2), dZ1, the head-weight
-// gradients gw (lane = feature) and the `misc` row (lanes 0..7 head-bias gradients, 8..15 sigma gradients, 16 loss sum)
-template <int KS1, bool ACTOR, bool BOUNDED = false>
+// gradients gw (lane = feature) and the `misc` row (lanes 0..7 head-bias gradients, 8..15 sigma gradients, 16 loss sum).
+// NACT (actor only): the action count the head, the loss and their gradients are unrolled to -- the real count or the next
+// instantiated one above it (step_nact).  The layouts are the ACT_PAD-wide ones whatever NACT is (head-weight stride, SMALL
+// block, Qt rows 8.. / 16, M slots): only loops and reads narrow.  Every term of an action beyond the real count is an exact
+// zero that the ACT_PAD-wide loops add last (dlt = 0, zero weights, log sigma = 0), and out / gw / the Qt and M rows are
+// independent per action, so all NACT >= act give the same bits (up to the sign of an exact zero in dZ2).
+template <int KS1, bool ACTOR, bool BOUNDED = false, int NACT = ACT_PAD>
 __device__ __forceinline__ void net_fwd_bwd(float* lds, float* scratch, const StepArgs& g, const Dims& d,
                                             const TileIn<KS1>& in, int lane_in, f32x16 (&h1)[2], f32x16 (&h2)[2],
-                                            f32x16 (&dz1)[2], float (&gw)[ACTOR ? ACT_PAD : 1], float& misc) {
+                                            f32x16 (&dz1)[2], float (&gw)[ACTOR ? NACT : 1], float& misc) {
     using L = Lds<KS1, 1>;
+    static_assert(NACT >= 1 && NACT <= ACT_PAD, "action count");
     int lane = lane_in;
     asm volatile("" : "+v"(lane));          // see net_tile: keeps lane-dependent addresses out of the prologue
     [[maybe_unused]] constexpr int MK = ACTOR ? 2 : 10;
-    constexpr int NA = ACTOR ? ACT_PAD : 1;
+    constexpr int NA = ACTOR ? NACT : 1;
     const int i = lane & 31, h = lane >> 5;
     trunk_forward<KS1, 1>(lds, 0, in.x, i, h, h1, h2);
     TS_MARK(g, MK + 0);
@@ -767,11 +793,12 @@ __device__ __forceinline__ void net_fwd_bwd(float* lds, float* scratch, const St
     const float* sm = lds + L::SMALL;
     float* Qt = scratch;                     // [17][TILE_PITCH]: per-sample quantities, transposed, for the row sums
     if constexpr (ACTOR) {
-        float mu[ACT_PAD];
-        head_forward<KS1, 1, ACT_PAD>(lds, 0, h, h2, mu);
-        const f32x4 b0 = ld4(sm), b1 = ld4(sm + 4), v0 = ld4(sm + 8), v1 = ld4(sm + 12), s0 = ld4(sm + 16), s1 = ld4(sm + 20);
-        float dlt[ACT_PAD], inv_var[ACT_PAD];
-        [[maybe_unused]] float bgrad[ACT_PAD];              // bounded actor: 1 - tanh^2 of the head output
+        float mu[NA];
+        head_forward<KS1, 1, NA>(lds, 0, h, h2, mu);
+        const f32x4 b0 = ld_head<NA>(sm), b1 = ld_head<NA - 4>(sm + 4), v0 = ld_head<NA>(sm + 8), v1 = ld_head<NA - 4>(sm + 12),
+                    s0 = ld_head<NA>(sm + 16), s1 = ld_head<NA - 4>(sm + 20);
+        float dlt[NA], inv_var[NA];
+        [[maybe_unused]] float bgrad[NA];                   // bounded actor: 1 - tanh^2 of the head output
         // ContinuousActorProbabilistic(unbounded=False): a template parameter, not a kernel argument -- the uniform branch
         // alone cost the unbounded (headline) kernel 1.4 us per launch through register allocation (profiles/r06_bounded_branch_ab.txt)
         constexpr bool bounded = BOUNDED;
@@ -779,8 +806,8 @@ __device__ __forceinline__ void net_fwd_bwd(float* lds, float* scratch, const St
         int n_act = d.act;
         asm volatile("" : "+s"(n_act));      // otherwise the 8 per-action constants are hoisted into (spilled) VGPRs
 #pragma unroll
-        for (int k = 0; k < ACT_PAD; ++k) {
-            // padding actions (k >= act): zero weights, bias 0, sigma_param 0 -> mu = 0, act = 0, log sigma = 0: the
+        for (int k = 0; k < NA; ++k) {
+            // padding actions (act <= k < NACT): zero weights, bias 0, sigma_param 0 -> mu = 0, act = 0, log sigma = 0: the
             // term is an exact -0; only the constant has to be switched off
             const float bm = k < 4 ? b0[k & 3] : b1[k & 3], iv = k < 4 ? v0[k & 3] : v1[k & 3], ls = k < 4 ? s0[k & 3] : s1[k & 3];
             float m = mu[k] + bm;
@@ -814,17 +841,18 @@ __device__ __forceinline__ void net_fwd_bwd(float* lds, float* scratch, const St
         basek = a2c ? A : basek;
         const float dlogp = -basek * ratio * w;
         const float ent_w = g.ent_coef * w;
-        float dsig[ACT_PAD];
+        float dsig[NA];
 #pragma unroll
-        for (int k = 0; k < ACT_PAD; ++k) {
+        for (int k = 0; k < NA; ++k) {
             dout[k] = dlogp * dlt[k] * inv_var[k];                                   // 0 for padding actions (dlt = 0)
             if (bounded) dout[k] = (dout[k] * g.mu_bound) * bgrad[k];               // MulBackward, then TanhBackward
             const float ds = dlogp * (dlt[k] * dlt[k] * inv_var[k] - 1.f) - ent_w;   // entropy: d/ds = 1
             dsig[k] = k < n_act ? ds : 0.f;
         }
         // rows 0..7 dout, 8..15 dsig, 16 loss term: half 0 writes the dout rows and the loss row, half 1 the dsig rows
+        // (rows NACT..7 and 8 + NACT..15 are not written: their sums are switched off below and never stored)
 #pragma unroll
-        for (int k = 0; k < ACT_PAD; ++k) Qt[(8 * h + k) * TILE_PITCH + i] = h ? dsig[k] : dout[k];
+        for (int k = 0; k < NA; ++k) Qt[(8 * h + k) * TILE_PITCH + i] = h ? dsig[k] : dout[k];
         if (h == 0) Qt[16 * TILE_PITCH + i] = term * w;
     } else {
         float v[1];
@@ -858,7 +886,7 @@ __device__ __forceinline__ void net_fwd_bwd(float* lds, float* scratch, const St
         float sacc = 0.f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) sacc += (q[k][0] + q[k][1]) + (q[k][2] + q[k][3]);
-        const bool mine = ACTOR ? (lane <= 16) : (lane == 0 || lane == 16);
+        const bool mine = ACTOR ? (lane == 16 || (lane < 16 && (lane & 7) < NA)) : (lane == 0 || lane == 16);
         misc = mine ? sacc : 0.f;
     }
     wave_lds_sync();
@@ -874,10 +902,12 @@ __device__ __forceinline__ void net_fwd_bwd(float* lds, float* scratch, const St
     tile_write(SB, h2[1], i, h);
     if (lane < 32) {
         if constexpr (ACTOR) {
-            const f32x4 d0 = {dout[0], dout[1], dout[2], dout[3]};
-            const f32x4 d1 = {dout[4], dout[5], dout[6], dout[7]};
+            const f32x4 d0 = {at_or_zero(dout, 0), at_or_zero(dout, 1), at_or_zero(dout, 2), at_or_zero(dout, 3)};
             *reinterpret_cast<f32x4*>(SA + lane * TILE_PITCH + 32) = d0;
-            *reinterpret_cast<f32x4*>(SB + lane * TILE_PITCH + 32) = d1;
+            if constexpr (NA > 4) {                              // (NACT <= 4: the second broadcast row is never read)
+                const f32x4 d1 = {at_or_zero(dout, 4), at_or_zero(dout, 5), at_or_zero(dout, 6), at_or_zero(dout, 7)};
+                *reinterpret_cast<f32x4*>(SB + lane * TILE_PITCH + 32) = d1;
+            }
         } else {
             SA[lane * TILE_PITCH + 32] = dout[0];
         }
@@ -894,12 +924,12 @@ __device__ __forceinline__ void net_fwd_bwd(float* lds, float* scratch, const St
             for (int e = 0; e < 4; ++e) {
                 const int smp = 4 * q + e;
                 if constexpr (ACTOR) {
-                    const f32x4 d0 = ld4(SA + smp * TILE_PITCH + 32);        // uniform address
-                    const f32x4 d1 = ld4(SB + smp * TILE_PITCH + 32);
+                    const f32x4 d0 = ld_head<NA>(SA + smp * TILE_PITCH + 32);        // uniform address
+                    const f32x4 d1 = ld_head<NA - 4>(SB + smp * TILE_PITCH + 32);
 #pragma unroll
                     for (int a = 0; a < 4; ++a) {
-                        gw[a] += d0[a] * hv[e];
-                        gw[a + 4] += d1[a] * hv[e];
+                        if (a < NA) gw[a] += d0[a] * hv[e];
+                        if (a + 4 < NA) gw[a + 4] += d1[a] * hv[e];
                     }
                 } else {
                     gw[0] += SA[smp * TILE_PITCH + 32] * hv[e];
@@ -911,14 +941,16 @@ __device__ __forceinline__ void net_fwd_bwd(float* lds, float* scratch, const St
     __builtin_amdgcn_sched_barrier(0);
     TS_MARK(g, MK + 2);
 
-    // ---- dZ2 = (dout . Whead) * (1 - h2^2)   (in place in h2).  Actor: the eight products of a value run as four packed
-    // multiply-adds over action pairs (even / odd partial sums, added at the end); tanh' on register pairs.
+    // ---- dZ2 = (dout . Whead) * (1 - h2^2)   (in place in h2): the products of a value are added in action order, so the
+    // ACT_PAD-wide sum only appends exact zeros to the NACT-wide one.  (TS_PK >= 3, an experiment: the products run as packed
+    // multiply-adds over action pairs, even / odd partial sums added at the end -- whole pairs beyond NACT are left out,
+    // which appends zeros to both partial sums in the same way.)  tanh' on register pairs.
     {
         const float* wh = lds + L::WH + h * (2 * 16 * ACT_PAD);
         [[maybe_unused]] f32x2 d01, d23, d45, d67;
         if constexpr (ACTOR) {
-            d01 = f32x2{dout[0], dout[1]}; d23 = f32x2{dout[2], dout[3]};
-            d45 = f32x2{dout[4], dout[5]}; d67 = f32x2{dout[6], dout[7]};
+            d01 = f32x2{at_or_zero(dout, 0), at_or_zero(dout, 1)}; d23 = f32x2{at_or_zero(dout, 2), at_or_zero(dout, 3)};
+            d45 = f32x2{at_or_zero(dout, 4), at_or_zero(dout, 5)}; d67 = f32x2{at_or_zero(dout, 6), at_or_zero(dout, 7)};
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -927,17 +959,24 @@ __device__ __forceinline__ void net_fwd_bwd(float* lds, float* scratch, const St
             for (int r = 0; r < 16; ++r) {
                 const float* p = wh + (t * 16 + r) * ACT_PAD;
                 if constexpr (ACTOR) {
-                    const f32x4 w0 = ld4(p);
-                    const f32x4 w1 = ld4(p + 4);
+                    const f32x4 w0 = ld_head<NA>(p);
+                    const f32x4 w1 = ld_head<NA - 4>(p + 4);
 #if TS_PK < 3
-                    dhv[r] = dout[0] * w0[0] + dout[1] * w0[1] + dout[2] * w0[2] + dout[3] * w0[3] +
-                             dout[4] * w1[0] + dout[5] * w1[1] + dout[6] * w1[2] + dout[7] * w1[3];
+                    if constexpr (NA == ACT_PAD) {
+                        dhv[r] = dout[0] * w0[0] + dout[1] * w0[1] + dout[2] * w0[2] + dout[3] * w0[3] +
+                                 dout[4] * w1[0] + dout[5] * w1[1] + dout[6] * w1[2] + dout[7] * w1[3];
+                    } else {                    // the same sum without its last ACT_PAD - NACT terms
+                        float sacc = dout[0] * w0[0];
+#pragma unroll
+                        for (int a = 1; a < NA; ++a) sacc = sacc + dout[a] * (a < 4 ? w0[a & 3] : w1[a & 3]);
+                        dhv[r] = sacc;
+                    }
                     continue;
 #endif
                     f32x2 sacc = d01 * f32x2{w0[0], w0[1]};
-                    sacc = d23 * f32x2{w0[2], w0[3]} + sacc;
-                    sacc = d45 * f32x2{w1[0], w1[1]} + sacc;
-                    sacc = d67 * f32x2{w1[2], w1[3]} + sacc;
+                    if constexpr (NA > 2) sacc = d23 * f32x2{w0[2], w0[3]} + sacc;
+                    if constexpr (NA > 4) sacc = d45 * f32x2{w1[0], w1[1]} + sacc;
+                    if constexpr (NA > 6) sacc = d67 * f32x2{w1[2], w1[3]} + sacc;
                     dhv[r] = sacc[0] + sacc[1];
                 } else {
                     dhv[r] = dout[0] * p[0];
@@ -971,13 +1010,13 @@ __device__ __forceinline__ void net_fwd_bwd(float* lds, float* scratch, const St
 }
 
 // the weight-gradient half of one net: shared 128-sample tiles, whole output tiles per wave, direct slab stores
-template <int KS1, bool ACTOR>
+template <int KS1, bool ACTOR, int NACT = ACT_PAD>
 __device__ __forceinline__ void net_wgrad(float* lds, const StepArgs& g, const Dims& d, const TileIn<KS1>& in,
                                           const f32x16 (&h1)[2], const f32x16 (&dz2)[2], const f32x16 (&dz1)[2],
-                                          const float (&gw)[ACTOR ? ACT_PAD : 1], float misc, int wave, int lane_in,
+                                          const float (&gw)[ACTOR ? NACT : 1], float misc, int wave, int lane_in,
                                           float* slab, const Slab2& SL, bool first) {
     [[maybe_unused]] constexpr int MK = ACTOR ? 2 : 10;
-    constexpr int NA = ACTOR ? ACT_PAD : 1;
+    constexpr int NA = ACTOR ? NACT : 1;
     constexpr int net = ACTOR ? 0 : 1;
     // lane, wave and the slab pointer are made opaque here: otherwise LLVM hoists the (loop-invariant) store and tile
     // addresses of the fully unrolled body out of the tile loop into the kernel prologue, where they are spilled
@@ -1032,6 +1071,7 @@ __device__ __forceinline__ void net_wgrad(float* lds, const StepArgs& g, const D
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int row = 2 * wave + q;
+                if (NA < ACT_PAD && row >= NA) continue;          // (rows NACT.. of the slots are not written)
                 float v = 0.f;
 #pragma unroll
                 for (int sl = 0; sl < STEP_WAVES; ++sl) v += M[sl * MISC_SLOT + row * 64 + lane];
@@ -1055,7 +1095,7 @@ __device__ __forceinline__ void net_wgrad(float* lds, const StepArgs& g, const D
     TS_MARK(g, MK + 6);
 }
 
-template <int KS1, bool BOUNDED = false>
+template <int KS1, bool BOUNDED = false, int NACT = ACT_PAD>
 __global__ __launch_bounds__(STEP_THREADS, 2) void ppo_step2_kernel(StepArgs g, Dims d) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     using L = Lds<KS1, 1>;
@@ -1096,9 +1136,9 @@ __global__ __launch_bounds__(STEP_THREADS, 2) void ppo_step2_kernel(StepArgs g, 
         f32x16 h1[2], h2[2], dz1[2];
         float misc;
         {
-            float gw[ACT_PAD];
-            net_fwd_bwd<KS1, true, BOUNDED>(lds, scratch, g, d, in, lane, h1, h2, dz1, gw, misc);
-            net_wgrad<KS1, true>(lds, g, d, in, h1, h2, dz1, gw, misc, wave, lane, slab, SL, first);
+            float gw[NACT];
+            net_fwd_bwd<KS1, true, BOUNDED, NACT>(lds, scratch, g, d, in, lane, h1, h2, dz1, gw, misc);
+            net_wgrad<KS1, true, NACT>(lds, g, d, in, h1, h2, dz1, gw, misc, wave, lane, slab, SL, first);
         }
         __syncthreads();                      // phase-B readers of the actor are done: the image region is free
         TS_MARK(g, 18);
@@ -1124,7 +1164,7 @@ __global__ __launch_bounds__(STEP_THREADS, 2) void ppo_step2_kernel(StepArgs g, 
 // slab reduction, the global norm and Adam see a zero gradient for it.  For callers whose other network is a stand-in:
 // Reinforce's minibatch steps (A2C's actor loss with adv := returns; no critic exists) and the critic iterations of
 // NPG / TRPO (A2C steps with a zero advantage; the actor takes no gradient there).
-template <int KS1, bool BOUNDED = false>
+template <int KS1, bool BOUNDED = false, int NACT = ACT_PAD>
 __global__ __launch_bounds__(STEP_THREADS, 2) void ppo_step1_kernel(StepArgs g, Dims d, int net) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     using L = Lds<KS1, 1>;
@@ -1158,9 +1198,9 @@ __global__ __launch_bounds__(STEP_THREADS, 2) void ppo_step1_kernel(StepArgs g, 
         f32x16 h1[2], h2[2], dz1[2];
         float misc;
         if (net == 0) {
-            float gw[ACT_PAD];
-            net_fwd_bwd<KS1, true, BOUNDED>(lds, scratch, g, d, in, lane, h1, h2, dz1, gw, misc);
-            net_wgrad<KS1, true>(lds, g, d, in, h1, h2, dz1, gw, misc, wave, lane, slab, SL, first);
+            float gw[NACT];
+            net_fwd_bwd<KS1, true, BOUNDED, NACT>(lds, scratch, g, d, in, lane, h1, h2, dz1, gw, misc);
+            net_wgrad<KS1, true, NACT>(lds, g, d, in, h1, h2, dz1, gw, misc, wave, lane, slab, SL, first);
         } else {
             float gw[1];
             net_fwd_bwd<KS1, false>(lds, scratch, g, d, in, lane, h1, h2, dz1, gw, misc);
@@ -1452,33 +1492,57 @@ int n_compute_units() {
     return cus;
 }
 
+// The action count the 128-sample step kernels are unrolled to (net_fwd_bwd's NACT): the next instantiated count at or above
+// `act`, the way supported_ks rounds the first layer's width up.  TS_PPO_NACT=8 forces the ACT_PAD-wide instantiation -- the
+// kernel as it was before the count became a template parameter: the A/B arm, and the arm the tests compare against (read
+// per call, not cached: they flip it inside one process).
+inline int step_nact(int act) {
+    const char* e = getenv("TS_PPO_NACT");
+    if (e && atoi(e) == ACT_PAD) return ACT_PAD;
+    const int avail[] = {2, 4, 6, ACT_PAD};
+    for (int a : avail) if (a >= act) return a;
+    return ACT_PAD;
+}
+
 // launches forward/backward of one minibatch into the slabs
-template <int KS1>
-int launch_step(ts_workspace* ws, const StepArgs& g, const Dims& d, int n_wg, hipStream_t s) {
+template <int KS1, int NACT>
+int launch_step_nact(ts_workspace* ws, const StepArgs& g, const Dims& d, int n_wg, hipStream_t s) {
     const size_t lds = sizeof(float) * (size_t)T2_FLOATS;
     static ts::DynLds attr2, attr1, attr2b, attr1b;      // per device (ts_common.h)
     const bool bounded = g.mu_bound > 0.f;               // (its own instantiation: see net_fwd_bwd)
+    // the bounded actor keeps the ACT_PAD-wide kernels at every action count: exact counts there would double the file's
+    // kernels once more (and its compile time) for a path no benchmark row runs
     if (g.nets == 1 || g.nets == 2) {            // one network only (ts_ppo_hparams.nets)
         if (bounded) {
             if (int rc = attr1b.allow(reinterpret_cast<const void*>(&ppo_step1_kernel<KS1, true>), lds)) return rc;
         } else {
-            if (int rc = attr1.allow(reinterpret_cast<const void*>(&ppo_step1_kernel<KS1, false>), lds)) return rc;
+            if (int rc = attr1.allow(reinterpret_cast<const void*>(&ppo_step1_kernel<KS1, false, NACT>), lds)) return rc;
         }
         ts::ProfScope prof(ws, TS_KIND_PPO_STEP, s);
         if (bounded) hipLaunchKernelGGL((ppo_step1_kernel<KS1, true>), dim3(n_wg), dim3(STEP_THREADS), lds, s, g, d, g.nets - 1);
-        else hipLaunchKernelGGL((ppo_step1_kernel<KS1, false>), dim3(n_wg), dim3(STEP_THREADS), lds, s, g, d, g.nets - 1);
+        else hipLaunchKernelGGL((ppo_step1_kernel<KS1, false, NACT>), dim3(n_wg), dim3(STEP_THREADS), lds, s, g, d, g.nets - 1);
     } else {
         if (bounded) {
             if (int rc = attr2b.allow(reinterpret_cast<const void*>(&ppo_step2_kernel<KS1, true>), lds)) return rc;
         } else {
-            if (int rc = attr2.allow(reinterpret_cast<const void*>(&ppo_step2_kernel<KS1, false>), lds)) return rc;
+            if (int rc = attr2.allow(reinterpret_cast<const void*>(&ppo_step2_kernel<KS1, false, NACT>), lds)) return rc;
         }
         ts::ProfScope prof(ws, TS_KIND_PPO_STEP, s);
         if (bounded) hipLaunchKernelGGL((ppo_step2_kernel<KS1, true>), dim3(n_wg), dim3(STEP_THREADS), lds, s, g, d);
-        else hipLaunchKernelGGL((ppo_step2_kernel<KS1, false>), dim3(n_wg), dim3(STEP_THREADS), lds, s, g, d);
+        else hipLaunchKernelGGL((ppo_step2_kernel<KS1, false, NACT>), dim3(n_wg), dim3(STEP_THREADS), lds, s, g, d);
     }
     TS_LAUNCH_CHECK();
     return TS_OK;
+}
+
+template <int KS1>
+int launch_step(ts_workspace* ws, const StepArgs& g, const Dims& d, int n_wg, hipStream_t s) {
+    switch (step_nact(d.act)) {
+        case 2: return launch_step_nact<KS1, 2>(ws, g, d, n_wg, s);
+        case 4: return launch_step_nact<KS1, 4>(ws, g, d, n_wg, s);
+        case 6: return launch_step_nact<KS1, 6>(ws, g, d, n_wg, s);
+        default: return launch_step_nact<KS1, ACT_PAD>(ws, g, d, n_wg, s);
+    }
 }
 
 inline int step_grid(int64_t n_rows) {
