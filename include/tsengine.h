@@ -1526,6 +1526,116 @@ int ts_cql_loss(ts_workspace* ws, const float* q_data, const float* target, cons
                 const float* cql_log_alpha, int64_t B, int64_t R, int64_t act_dim, const double* cql_hp, float* d_data_out,
                 float* d_rep_out, float* loss_out9, ts_stream_t stream);
 
+/* ---- continuous BCQ (imitation/bcq.py:188-263, arXiv 1812.02900; VAE and Perturbation utils/net/continuous.py:378-490) ----
+ * Four networks.  `trunk` describes the perturbation net and the twin critics (all three on concat(obs, act)), `vae_trunk` the
+ * VAE's encoder and decoder (hidden width, depth, activation; max_action of both structs is ignored).  Flat layouts, with
+ * kc = pad32(obs_dim + act_dim), kd = pad32(obs_dim + L), lp = pad32(L), L = latent_dim in [1, 64], act_dim <= 32:
+ *   critic        ts_sac_layout's critic, unchanged: L1 [kc + 1, h] | L2.. [h + 1, h] | head [h + 1, 32] (Q in column 0)
+ *   perturbation  a TD3 actor layout on the input width kc: the same shape as a critic, the logits in head columns [0, act_dim)
+ *   vae           encoder | decoder in ONE vector:
+ *     encoder     L1 [kc + 1, hv] | L2.. [hv + 1, hv] | head [hv + 1, 2 lp]: `mean` in head columns [0, L), the raw
+ *                 `log_std` in [lp, lp + L) -- the two Linear heads behind the encoder's last ReLU are one GEMM
+ *     decoder     L1 [kd + 1, hv] | L2.. [hv + 1, hv] | head [hv + 1, 32]; input row = [obs | z | 0]
+ * ts_cbcq_layout: h_out12 = {kc, kd, lp, perturbation count, critic count, encoder count, decoder count, vae count,
+ * head offset of a critic / the perturbation net, encoder head offset, decoder offset in vae, decoder head offset in vae}. */
+int ts_cbcq_layout(int64_t obs_dim, int64_t act_dim, int64_t latent_dim, const ts_mlp_trunk* trunk, const ts_mlp_trunk* vae_trunk,
+                   int64_t* h_out12);
+
+/* state: a HOST array of TS_CBCQ_ST_COUNT device pointers (no struct) */
+#define TS_CBCQ_ST_PERT 0
+#define TS_CBCQ_ST_PERT_M 1
+#define TS_CBCQ_ST_PERT_V 2
+#define TS_CBCQ_ST_PERT_OLD 3          /* actor_perturbation_target: Polyak-updated, read by nothing (as in the reference) */
+#define TS_CBCQ_ST_CRITIC1 4
+#define TS_CBCQ_ST_CRITIC1_M 5
+#define TS_CBCQ_ST_CRITIC1_V 6
+#define TS_CBCQ_ST_CRITIC1_OLD 7
+#define TS_CBCQ_ST_CRITIC2 8
+#define TS_CBCQ_ST_CRITIC2_M 9
+#define TS_CBCQ_ST_CRITIC2_V 10
+#define TS_CBCQ_ST_CRITIC2_OLD 11
+#define TS_CBCQ_ST_VAE 12
+#define TS_CBCQ_ST_VAE_M 13
+#define TS_CBCQ_ST_VAE_V 14
+#define TS_CBCQ_ST_COUNT 15
+/* hp: a plain double array.  A negative learning rate skips that optimizer step; a max_grad_norm <= 0 means no clipping
+ * (clip_grad_norm_ over the optimizer's own module otherwise). */
+#define TS_CBCQ_HP_PERT_LR 0
+#define TS_CBCQ_HP_CRITIC1_LR 1
+#define TS_CBCQ_HP_CRITIC2_LR 2
+#define TS_CBCQ_HP_VAE_LR 3
+#define TS_CBCQ_HP_BETA1 4
+#define TS_CBCQ_HP_BETA2 5
+#define TS_CBCQ_HP_ADAM_EPS 6
+#define TS_CBCQ_HP_TAU 7
+#define TS_CBCQ_HP_GAMMA 8
+#define TS_CBCQ_HP_LMBDA 9
+#define TS_CBCQ_HP_PHI 10
+#define TS_CBCQ_HP_MAX_ACTION 11
+#define TS_CBCQ_HP_PERT_MAX_NORM 12
+#define TS_CBCQ_HP_CRITIC1_MAX_NORM 13
+#define TS_CBCQ_HP_CRITIC2_MAX_NORM 14
+#define TS_CBCQ_HP_VAE_MAX_NORM 15
+#define TS_CBCQ_HP_SPLIT_DECODE 16     /* nonzero: the decoder's target rows and actor-loss rows as two passes (comparison) */
+#define TS_CBCQ_HP_PERT_FIRST_ROW 17   /* nonzero: the perturbation of EVERY row comes from the logits of the batch's first row.
+                                          Perturbation.forward takes `[0]` of its preprocess net's output (continuous.py:409):
+                                          of a (logits, state) pair when the net is a `Net` (0 here), but the first row of the
+                                          logits when it is a plain `MLP`, as in examples/offline/d4rl_bcq.py (1 here) */
+#define TS_CBCQ_HP_COUNT 18
+
+/* BCQ._update_with_batch (bcq.py:188-263) in the reference's order:
+ *   1. VAE step: mean | log_std = enc([s, a]), log_std clamped to [-4, 15], z = mean + exp(log_std) eps1,
+ *      recon = max_action tanh(dec([s, z])), vae_loss = mse(act, recon) + KL / 2, Adam on the whole vae vector;
+ *   2. target with the UPDATED decoder, no gradient: a' = max_action tanh(dec([s'_rep, clamp(eps2, +-0.5)])) (s' repeated R
+ *      times, row b R + r; a' is NOT perturbed), tq = lmbda min(Q1_old, Q2_old) + (1 - lmbda) max(..), the max over the R rows
+ *      of a sample, target = rew + !done gamma tq (float32 throughout);
+ *   3. critic 1 / critic 2: mse(Q_k(s, a), target), each with its own rate and clip;
+ *   4. perturbation step on the updated critic 1 and VAE: sampled = decode(s, clamp(eps3, +-0.5)), perturbed =
+ *      clamp(sampled + phi max_action tanh(pert([s, sampled])), +-max_action), actor_loss = -mean Q1(s, perturbed);
+ *   5. Polyak on the three lagged networks.
+ * Both clamps pass the gradient AT the bound and block it beyond.  The decoder runs ONE pass over the B (R + 1) rows of steps 2
+ * and 4; the lagged critics one twin pass on B R rows, the live critics one twin pass on B rows.
+ * obs / obs_next float32[B, obs_dim], act [B, act_dim], rew / done (nonzero = done) [B]; the RAW standard-normal draws
+ * eps1 [B, L], eps2 [B R, L], eps3 [B, L] (the +-0.5 clamp is part of decode and happens here).  adam_step >= 1: the step
+ * number of all four optimizers.  stats_out4 = {actor_loss, critic1_loss, critic2_loss, vae_loss}; target_out (nullable)
+ * float32[B]; grads_out (nullable) = {vae, critic1, critic2, perturbation} flat gradients BEFORE clipping.
+ * TS_ERR_INVALID_ARG before any HIP call: R < 1, B (R + 1) beyond int, latent_dim outside [1, 64], max_action <= 0, phi < 0,
+ * lmbda outside [0, 1], a non-finite entry of hp, a NULL state pointer (BCQ needs the second critic). */
+int ts_cbcq_update(ts_workspace* ws, float* const* state, int64_t adam_step, const float* obs, const float* act, const float* rew,
+                   const float* done, const float* obs_next, const float* eps1, const float* eps2, const float* eps3, int64_t B,
+                   int64_t R, int64_t obs_dim, int64_t act_dim, int64_t latent_dim, const ts_mlp_trunk* trunk,
+                   const ts_mlp_trunk* vae_trunk, const double* hp, float* stats_out4, float* target_out, float* grads_out,
+                   ts_stream_t stream);
+
+/* BCQPolicy.forward (bcq.py:91-116) for N observations at once: T candidates each, candidate (n, t) =
+ * perturb(obs_n, decode(obs_n, clamp(noise[n, t], +-0.5))), noise the RAW draws float32[N, T, L]; act_out float32[N, act_dim] is
+ * the candidate with the largest Q1.  Ties go to the LOWEST index t.  pert_first_row: TS_CBCQ_HP_PERT_FIRST_ROW's switch, the
+ * batch being one observation's T candidates (the reference runs one observation at a time).  idx_out int64[N] / q_out float32[N] / cand_out
+ * float32[N, T, act_dim] (every candidate) are nullable. */
+int ts_cbcq_policy_forward(ts_workspace* ws, const float* pert, const float* critic1, const float* vae, const float* obs,
+                           const float* noise, int64_t N, int64_t T, int64_t obs_dim, int64_t act_dim, int64_t latent_dim,
+                           const ts_mlp_trunk* trunk, const ts_mlp_trunk* vae_trunk, double phi, double max_action,
+                           int32_t pert_first_row, float* act_out, int64_t* idx_out, float* q_out, float* cand_out,
+                           ts_stream_t stream);
+
+/* The per-sample kernels of ts_cbcq_update alone, on caller-supplied DENSE device arrays (no network inside).
+ * ts_cbcq_latent: raw mean / log_std / eps / upstream dz, all float32[B, L] -> z = mean + exp(clamp(log_std)) eps, kl_out (one
+ * float) = mean(-log std + (std^2 + mean^2 - 1) / 2), and d(recon loss + KL / 2) / d(mean, raw log_std): 0.5 / (B L) times
+ * {mean, std^2 - 1} plus the path through z {dz, dz eps std}; d_log_std is zero where the raw value lies outside [-4, 15].
+ * ts_cbcq_recon: decoder logits / act float32[B, act_dim] -> recon = max_action tanh(logits), mse_out (one float) =
+ * mse_loss(act, recon), d_logits = d mse / d logits.
+ * ts_cbcq_target: q1 / q2 float32[B R] of the lagged critics, rew / done [B] -> target [B] (step 2 above).
+ * ts_cbcq_perturb: perturbation logits / sampled / upstream dQ/da float32[B, act_dim] -> perturbed (step 4) and d_logits.
+ * All sums are taken in a fixed order (no float atomics): the same inputs give the same bits. */
+int ts_cbcq_latent(ts_workspace* ws, const float* mean, const float* log_std, const float* eps, const float* dz, int64_t B,
+                   int64_t L, float* z_out, float* kl_out, float* d_mean_out, float* d_log_std_out, ts_stream_t stream);
+int ts_cbcq_recon(ts_workspace* ws, const float* logits, const float* act, int64_t B, int64_t act_dim, double max_action,
+                  float* recon_out, float* mse_out, float* d_logits_out, ts_stream_t stream);
+int ts_cbcq_target(ts_workspace* ws, const float* q1, const float* q2, const float* rew, const float* done, int64_t B, int64_t R,
+                   double gamma, double lmbda, float* target_out, ts_stream_t stream);
+int ts_cbcq_perturb(ts_workspace* ws, const float* logits, const float* sampled, const float* dq_da, int64_t B, int64_t act_dim,
+                    double phi, double max_action, float* perturbed_out, float* d_logits_out, ts_stream_t stream);
+
 /* ---- data-parallel exchange ------------------------------------------------------------------
  * One process per GPU; the reference has no distributed path (its only multi-GPU mechanism is single-process
  * nn.DataParallel, tianshou/utils/net/common.py:473-515).  In-place sum all-reduce of a flat fp32 buffer over RCCL

@@ -2959,3 +2959,612 @@ int ts_cql_update(ts_workspace* ws, const ts_sac_state* st, float* cql_log_alpha
 }
 
 }  // extern "C"
+
+// ---- BCQ (continuous, imitation/bcq.py:188-263, arXiv 1812.02900; utils/net/continuous.py:378-490) -------------------
+// Four networks: the perturbation net and the twin critics on concat(obs, act) (one trunk), the conditional VAE (encoder with
+// the mean | log_std head block, decoder; a second trunk).  Order of an update: VAE step, target with the UPDATED decoder
+// (max over R decoded actions of lmbda min + (1 - lmbda) max of the lagged critics), the two critic steps, the perturbation
+// step on the updated critic 1 and VAE, Polyak.  After the VAE step the decoder's B R target rows and its B actor-loss rows
+// wait for nothing else and share the parameters: one pass over B (R + 1) rows.
+namespace {
+
+constexpr float CBCQ_LS_MIN = -4.f, CBCQ_LS_MAX = 15.f;     // continuous.py:466
+constexpr float CBCQ_Z_CLIP = 0.5f;                         // continuous.py:486
+
+// Row segments [rows, k] = [obs row (i / rep) | tail row i (clamped to +-clampv when clampv > 0; NULL: zeros) | 0]: every
+// network input of an update that does not depend on a network, in one launch.  Four columns per thread.
+constexpr int CBCQ_MAX_SEGS = 7;
+struct CbcqSeg { const float* obs; const float* tail; float* out; int64_t rows; int rep, tail_dim, k; float clampv; unsigned first; };
+struct CbcqPackArgs { CbcqSeg s[CBCQ_MAX_SEGS]; int n; int obs_dim; };
+__global__ __launch_bounds__(256) void cbcq_pack_kernel(CbcqPackArgs a) {
+    using f32x4 = __attribute__((ext_vector_type(4))) float;
+    int g = 0;
+    while (g + 1 < a.n && blockIdx.x >= a.s[g + 1].first) ++g;
+    const CbcqSeg& sg = a.s[g];
+    const int w4 = sg.k / 4;
+    const int64_t t = (int64_t)(blockIdx.x - sg.first) * 256 + threadIdx.x;
+    if (t >= sg.rows * w4) return;
+    const int64_t row = t / w4;
+    const int j = (int)(t - row * w4) * 4;
+    const int64_t b = sg.rep == 1 ? row : row / sg.rep;
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int col = j + e;
+        float x = 0.f;
+        if (col < a.obs_dim) x = sg.obs[b * a.obs_dim + col];
+        else if (sg.tail && col < a.obs_dim + sg.tail_dim) {
+            x = sg.tail[row * sg.tail_dim + col - a.obs_dim];
+            if (sg.clampv > 0.f) x = fminf(fmaxf(x, -sg.clampv), sg.clampv);
+        }
+        v[e] = x;
+    }
+    *reinterpret_cast<f32x4*>(sg.out + row * sg.k + j) = v;
+}
+
+// VAE latent (continuous.py:464-470): z = mean + exp(clamp(log_std, -4, 15)) eps, and the per-workgroup sums of the KL term
+// -log std + (std^2 + mean^2 - 1) / 2 (log std = the clamped log_std itself).  One thread per (b, l); mean / log_std rows are
+// `hs` apart, z rows `zs`.
+__global__ __launch_bounds__(256) void cbcq_latent_kernel(const float* __restrict__ mean, const float* __restrict__ log_std,
+                                                          const float* __restrict__ eps, int64_t B, int L, int hs, int zs,
+                                                          float* __restrict__ z, float* __restrict__ part) {
+    __shared__ float red[4];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    float kl = 0.f;
+    if (i < B * L) {
+        const int64_t b = i / L;
+        const int l = (int)(i - b * L);
+        const float mu = mean[b * hs + l];
+        const float ls = fminf(fmaxf(log_std[b * hs + l], CBCQ_LS_MIN), CBCQ_LS_MAX);
+        const float sd = expf(ls);
+        z[b * zs + l] = mu + sd * eps[i];
+        kl = -ls + (sd * sd + mu * mu - 1.f) / 2.f;
+    }
+    const float tot = block_sum_256(kl, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = tot;
+}
+
+// d(recon loss + KL / 2) / d(mean, raw log_std): the KL gradient 0.5 / (B L) {mean, std^2 - 1} plus the path through z,
+// {dz, dz eps std}; torch's clamp passes the gradient AT the bounds and blocks it beyond.  One thread per (b, l < Lt): the
+// columns [L, Lt) of both blocks are written as zeros (Lt = the padded block width inside an update, L on dense arrays).
+__global__ __launch_bounds__(256) void cbcq_latent_bwd_kernel(const float* __restrict__ mean, const float* __restrict__ log_std,
+                                                              const float* __restrict__ eps, const float* __restrict__ dz,
+                                                              int64_t B, int L, int Lt, int hs, int dzs,
+                                                              float* __restrict__ d_mean, float* __restrict__ d_log_std) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * Lt) return;
+    const int64_t b = i / Lt;
+    const int l = (int)(i - b * Lt);
+    if (l >= L) { d_mean[b * hs + l] = 0.f; d_log_std[b * hs + l] = 0.f; return; }
+    const float mu = mean[b * hs + l], raw = log_std[b * hs + l];
+    const float sd = expf(fminf(fmaxf(raw, CBCQ_LS_MIN), CBCQ_LS_MAX));
+    const float c = 0.5f / ((float)B * (float)L);
+    const float g = dz[b * dzs + l];
+    d_mean[b * hs + l] = c * mu + g;
+    d_log_std[b * hs + l] = (raw >= CBCQ_LS_MIN && raw <= CBCQ_LS_MAX) ? c * (sd * sd - 1.f) + g * eps[b * L + l] * sd : 0.f;
+}
+
+// recon = max_action tanh(logits) (continuous.py:490), the per-workgroup sums of (act - recon)^2 and
+// d mse_loss(act, recon) / d logits.  Thread (b, j < 32): with ds == 32 the whole 32-column gradient row is written.
+__global__ __launch_bounds__(256) void cbcq_recon_kernel(const float* __restrict__ logits, const float* __restrict__ act,
+                                                         int64_t B, int A, int ls, int ds, float max_action,
+                                                         float* __restrict__ recon, float* __restrict__ d_logits,
+                                                         float* __restrict__ part) {
+    __shared__ float red[4];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t b = i >> 5;
+    const int j = (int)(i & 31);
+    float sq = 0.f;
+    if (b < B) {
+        if (j < A) {
+            const float t = tanhf(logits[b * ls + j]);
+            const float r = max_action * t;
+            const float dlt = r - act[b * A + j];
+            if (recon) recon[b * A + j] = r;
+            sq = dlt * dlt;
+            d_logits[b * ds + j] = 2.f * dlt / ((float)B * (float)A) * max_action * (1.f - t * t);
+        } else if (ds == 32) d_logits[b * 32 + j] = 0.f;
+    }
+    const float tot = block_sum_256(sq, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = tot;
+}
+
+// One workgroup: partial sums in workgroup order -> mse (mean over B A), KL (mean over B L), vae_loss = mse + KL / 2
+// (bcq.py:203-206); every pointer nullable.
+__global__ __launch_bounds__(256) void cbcq_vae_finish_kernel(const float* __restrict__ part_mse, int n_mse, float inv_mse,
+                                                              const float* __restrict__ part_kl, int n_kl, float inv_kl,
+                                                              float* mse_out, float* kl_out, float* vae_out) {
+    __shared__ float red[4];
+    float s0 = 0.f, s1 = 0.f;
+    if (part_mse) for (int j = threadIdx.x; j < n_mse; j += 256) s0 += part_mse[j];
+    if (part_kl) for (int j = threadIdx.x; j < n_kl; j += 256) s1 += part_kl[j];
+    const float mse = block_sum_256(s0, red) * inv_mse;
+    __syncthreads();
+    const float kl = block_sum_256(s1, red) * inv_kl;
+    if (threadIdx.x != 0) return;
+    if (mse_out) *mse_out = mse;
+    if (kl_out) *kl_out = kl;
+    if (vae_out) *vae_out = mse + kl / 2.f;
+}
+
+// decode's output (continuous.py:490) into the action columns of the next network's input: rows [0, n0) -> x0, the rest -> x1
+__global__ __launch_bounds__(256) void cbcq_decode_out_kernel(const float* __restrict__ logits, int64_t N, int64_t n0, int A,
+                                                              float max_action, int obs_dim, int kc, float* __restrict__ x0,
+                                                              float* __restrict__ x1) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N * A) return;
+    const int64_t b = i / A;
+    const int j = (int)(i - b * A);
+    const float a = max_action * tanhf(logits[b * 32 + j]);
+    if (b < n0) x0[b * kc + obs_dim + j] = a;
+    else x1[(b - n0) * kc + obs_dim + j] = a;
+}
+
+// target (bcq.py:223-237): lmbda min(Q1, Q2) + (1 - lmbda) max(Q1, Q2) of the lagged critics, the max over the R rows of a
+// sample (the first of equal values), rew + !done gamma max; float32 throughout.  Q element i at q[i * qs].
+__global__ __launch_bounds__(256) void cbcq_target_kernel(const float* __restrict__ q1, const float* __restrict__ q2, int qs,
+                                                          const float* __restrict__ rew, const float* __restrict__ done,
+                                                          int64_t B, int R, float gamma, float lmbda, float one_minus_lmbda,
+                                                          float* __restrict__ out) {
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    float best = 0.f;
+    for (int r = 0; r < R; ++r) {
+        const float a = q1[(b * R + r) * qs], c = q2[(b * R + r) * qs];
+        const float v = lmbda * fminf(a, c) + one_minus_lmbda * fmaxf(a, c);
+        if (r == 0 || v > best) best = v;
+    }
+    out[b] = rew[b] + (done[b] != 0.f ? 0.f : gamma) * best;
+}
+
+// Perturbation.forward (continuous.py:407-412): clamp(sampled + phi max_action tanh(logits), +-max_action) into `out`, and
+// fac = d out / d logits = [|pre-clamp| <= max_action] phi max_action (1 - tanh^2) (the clamp passes the gradient at the bound).
+// grp > 0: continuous.py:409 takes `[0]` of its preprocess net's output -- of a (logits, state) pair when the net is a `Net`,
+// but the FIRST ROW of the logits when it is a plain `MLP` (the examples' choice); every row of a batch of `grp` rows is then
+// perturbed by the logits of the batch's first row.  grp == 0: each row by its own.
+__global__ __launch_bounds__(256) void cbcq_perturb_kernel(const float* __restrict__ logits, int ls,
+                                                           const float* __restrict__ sampled, int ss, int64_t B, int A,
+                                                           int64_t grp, float phi_max, float max_action,
+                                                           float* __restrict__ out, int os, float* __restrict__ fac) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * A) return;
+    const int64_t b = i / A;
+    const int j = (int)(i - b * A);
+    const int64_t lb = grp > 0 ? b / grp * grp : b;
+    const float t = tanhf(logits[lb * ls + j]);
+    const float pre = phi_max * t + sampled[b * ss + j];
+    out[b * os + j] = fminf(fmaxf(pre, -max_action), max_action);
+    if (fac) fac[i] = (pre >= -max_action && pre <= max_action) ? phi_max * (1.f - t * t) : 0.f;
+}
+
+// The first-row form's backward (one batch of B rows): d_logits row 0 = the column sums of dQ/da fac over the batch, in
+// block_sum_256's fixed order (workgroup 0); every other row is zero (workgroups 1..).  d_logits [B, 32].
+__global__ __launch_bounds__(256) void cbcq_perturb_bwd_row0_kernel(const float* __restrict__ dx, int xs,
+                                                                    const float* __restrict__ fac, int64_t B, int A,
+                                                                    float* __restrict__ d_logits) {
+    __shared__ float red[4];
+    if (blockIdx.x > 0) {
+        const int64_t i = (int64_t)(blockIdx.x - 1) * 256 + threadIdx.x + 32;
+        if (i < B * 32) d_logits[i] = 0.f;
+        return;
+    }
+    if (threadIdx.x >= A && threadIdx.x < 32) d_logits[threadIdx.x] = 0.f;
+    for (int j = 0; j < A; ++j) {
+        float sum = 0.f;
+        for (int64_t b = threadIdx.x; b < B; b += 256) sum += dx[b * xs + j] * fac[b * A + j];
+        const float tot = block_sum_256(sum, red);
+        if (threadIdx.x == 0) d_logits[j] = tot;
+        __syncthreads();
+    }
+}
+
+// d loss / d logits = dQ/da fac.  Thread (b, j < 32): with ds == 32 the whole 32-column row is written.
+__global__ __launch_bounds__(256) void cbcq_perturb_bwd_kernel(const float* __restrict__ dx, int xs, const float* __restrict__ fac,
+                                                               int64_t B, int A, int ds, float* __restrict__ d_logits) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t b = i >> 5;
+    const int j = (int)(i & 31);
+    if (b >= B) return;
+    if (j < A) d_logits[b * ds + j] = dx[b * xs + j] * fac[b * A + j];
+    else if (ds == 32) d_logits[b * 32 + j] = 0.f;
+}
+
+// BCQPolicy.forward's choice (bcq.py:111-114): per observation the first of the largest Q1 among its T candidates
+__global__ __launch_bounds__(256) void cbcq_argmax_kernel(const float* __restrict__ q, const float* __restrict__ x_q, int64_t N,
+                                                          int T, int A, int obs_dim, int kc, float* __restrict__ act_out,
+                                                          int64_t* __restrict__ idx_out, float* __restrict__ q_out) {
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    int best = 0;
+    float bq = q[n * T * 32];
+    for (int t = 1; t < T; ++t) {
+        const float v = q[(n * T + t) * 32];
+        if (v > bq) { bq = v; best = t; }
+    }
+    for (int j = 0; j < A; ++j) act_out[n * A + j] = x_q[(n * T + best) * kc + obs_dim + j];
+    if (idx_out) idx_out[n] = best;
+    if (q_out) q_out[n] = bq;
+}
+
+__global__ __launch_bounds__(256) void cbcq_cand_kernel(const float* __restrict__ x_q, int64_t rows, int A, int obs_dim, int kc,
+                                                        float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * A) return;
+    const int64_t b = i / A;
+    out[i] = x_q[b * kc + obs_dim + (int)(i - b * A)];
+}
+
+struct CbcqDims { Dims d, v; int L, lp, kd; };
+
+int cbcq_dims(const char* who, const ts_mlp_trunk* trunk, const ts_mlp_trunk* vae_trunk, int64_t obs_dim, int64_t act_dim,
+              int64_t latent_dim, CbcqDims* o) {
+    TS_REQUIRE(latent_dim >= 1 && latent_dim <= 64, TS_ERR_INVALID_ARG, "%s: latent_dim in [1, 64], got %lld", who, (long long)latent_dim);
+    if (int rc = make_dims(trunk, obs_dim, act_dim, &o->d)) return rc;
+    if (int rc = make_dims(vae_trunk, obs_dim, act_dim, &o->v)) return rc;
+    o->L = (int)latent_dim; o->lp = pad32(o->L); o->kd = pad32(o->d.obs + o->L);
+    return TS_OK;
+}
+
+int cbcq_pack(hipStream_t s, CbcqPackArgs& a) {
+    unsigned blocks = 0;
+    for (int g = 0; g < a.n; ++g) {
+        a.s[g].first = blocks;
+        blocks += (unsigned)ts::ceil_div(a.s[g].rows * (a.s[g].k / 4), 256);
+    }
+    hipLaunchKernelGGL(cbcq_pack_kernel, dim3(blocks), dim3(256), 0, s, a);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+inline Act act_rows(const Act& a, int64_t row0, int hid, int head_cols) {
+    Act r{};
+    for (int i = 0; i < MAXD; ++i) r.h[i] = a.h[i] ? a.h[i] + row0 * hid : nullptr;
+    r.out = a.out + row0 * head_cols;
+    return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ts_cbcq_layout(int64_t obs_dim, int64_t act_dim, int64_t latent_dim, const ts_mlp_trunk* trunk, const ts_mlp_trunk* vae_trunk,
+                   int64_t* h_out12) {
+    CbcqDims c;
+    if (int rc = cbcq_dims("ts_cbcq_layout", trunk, vae_trunk, obs_dim, act_dim, latent_dim, &c)) return rc;
+    TS_REQUIRE(h_out12, TS_ERR_INVALID_ARG, "ts_cbcq_layout: NULL output");
+    const Mlp mc = make_mlp(1, c.d.kc, 32, c.d.hid, c.d.depth, c.d.fn);
+    const Mlp me = make_mlp(1, c.d.kc, 2 * c.lp, c.v.hid, c.v.depth, c.v.fn), md = make_mlp(1, c.kd, 32, c.v.hid, c.v.depth, c.v.fn);
+    h_out12[0] = c.d.kc; h_out12[1] = c.kd; h_out12[2] = c.lp;
+    h_out12[3] = mc.total(); h_out12[4] = mc.total(); h_out12[5] = me.total(); h_out12[6] = md.total();
+    h_out12[7] = me.total() + md.total(); h_out12[8] = mc.off[mc.L - 1]; h_out12[9] = me.off[me.L - 1];
+    h_out12[10] = me.total(); h_out12[11] = me.total() + md.off[md.L - 1];
+    return TS_OK;
+}
+
+int ts_cbcq_latent(ts_workspace* ws, const float* mean, const float* log_std, const float* eps, const float* dz, int64_t B,
+                   int64_t L, float* z_out, float* kl_out, float* d_mean_out, float* d_log_std_out, ts_stream_t stream) {
+    TS_REQUIRE(B >= 1 && L >= 1 && L <= 64 && B <= 2147483647 / 64, TS_ERR_INVALID_ARG, "ts_cbcq_latent: B >= 1, L in [1, 64]");
+    TS_REQUIRE(mean && log_std && eps && dz && z_out && kl_out && d_mean_out && d_log_std_out, TS_ERR_INVALID_ARG,
+               "ts_cbcq_latent: NULL argument");
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_cbcq_latent: workspace is NULL");
+    hipStream_t s = ts::as_stream(stream);
+    const unsigned gb = (unsigned)ts::ceil_div(B * L, 256);
+    if (int rc = ts::ws_reserve(ws, al(4 * (size_t)gb) + 4096)) return rc;
+    float* part = static_cast<float*>(ws->base);
+    hipLaunchKernelGGL(cbcq_latent_kernel, dim3(gb), dim3(256), 0, s, mean, log_std, eps, B, (int)L, (int)L, (int)L, z_out, part);
+    hipLaunchKernelGGL(cbcq_latent_bwd_kernel, dim3(gb), dim3(256), 0, s, mean, log_std, eps, dz, B, (int)L, (int)L, (int)L, (int)L,
+                       d_mean_out, d_log_std_out);
+    hipLaunchKernelGGL(cbcq_vae_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)nullptr, 0, 0.f, (const float*)part, (int)gb,
+                       1.f / ((float)B * (float)L), (float*)nullptr, kl_out, (float*)nullptr);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+int ts_cbcq_recon(ts_workspace* ws, const float* logits, const float* act, int64_t B, int64_t act_dim, double max_action,
+                  float* recon_out, float* mse_out, float* d_logits_out, ts_stream_t stream) {
+    TS_REQUIRE(B >= 1 && B <= 2147483647 / 32 && act_dim >= 1 && act_dim <= 32, TS_ERR_INVALID_ARG, "ts_cbcq_recon: B >= 1, act_dim in [1, 32]");
+    TS_REQUIRE(std::isfinite(max_action) && max_action > 0.0, TS_ERR_INVALID_ARG, "ts_cbcq_recon: max_action must be > 0");
+    TS_REQUIRE(logits && act && recon_out && mse_out && d_logits_out, TS_ERR_INVALID_ARG, "ts_cbcq_recon: NULL argument");
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_cbcq_recon: workspace is NULL");
+    hipStream_t s = ts::as_stream(stream);
+    const unsigned gb = (unsigned)ts::ceil_div(B * 32, 256);
+    if (int rc = ts::ws_reserve(ws, al(4 * (size_t)gb) + 4096)) return rc;
+    float* part = static_cast<float*>(ws->base);
+    hipLaunchKernelGGL(cbcq_recon_kernel, dim3(gb), dim3(256), 0, s, logits, act, B, (int)act_dim, (int)act_dim, (int)act_dim,
+                       (float)max_action, recon_out, d_logits_out, part);
+    hipLaunchKernelGGL(cbcq_vae_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)part, (int)gb,
+                       1.f / ((float)B * (float)act_dim), (const float*)nullptr, 0, 0.f, mse_out, (float*)nullptr, (float*)nullptr);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+int ts_cbcq_target(ts_workspace* ws, const float* q1, const float* q2, const float* rew, const float* done, int64_t B, int64_t R,
+                   double gamma, double lmbda, float* target_out, ts_stream_t stream) {
+    TS_REQUIRE(B >= 1 && R >= 1 && R <= 2147483647 && B <= 2147483647 / R, TS_ERR_INVALID_ARG, "ts_cbcq_target: B, R >= 1 and B R within int");
+    TS_REQUIRE(std::isfinite(gamma) && std::isfinite(lmbda) && lmbda >= 0.0 && lmbda <= 1.0, TS_ERR_INVALID_ARG,
+               "ts_cbcq_target: gamma finite, lmbda in [0, 1]");
+    TS_REQUIRE(q1 && q2 && rew && done && target_out, TS_ERR_INVALID_ARG, "ts_cbcq_target: NULL argument");
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_cbcq_target: workspace is NULL");
+    hipLaunchKernelGGL(cbcq_target_kernel, dim3((unsigned)ts::ceil_div(B, 256)), dim3(256), 0, ts::as_stream(stream), q1, q2, 1, rew,
+                       done, B, (int)R, (float)gamma, (float)lmbda, (float)(1.0 - lmbda), target_out);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+int ts_cbcq_perturb(ts_workspace* ws, const float* logits, const float* sampled, const float* dq_da, int64_t B, int64_t act_dim,
+                    double phi, double max_action, float* perturbed_out, float* d_logits_out, ts_stream_t stream) {
+    TS_REQUIRE(B >= 1 && B <= 2147483647 / 32 && act_dim >= 1 && act_dim <= 32, TS_ERR_INVALID_ARG, "ts_cbcq_perturb: B >= 1, act_dim in [1, 32]");
+    TS_REQUIRE(std::isfinite(max_action) && max_action > 0.0 && std::isfinite(phi) && phi >= 0.0, TS_ERR_INVALID_ARG,
+               "ts_cbcq_perturb: max_action > 0, phi >= 0");
+    TS_REQUIRE(logits && sampled && dq_da && perturbed_out && d_logits_out, TS_ERR_INVALID_ARG, "ts_cbcq_perturb: NULL argument");
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_cbcq_perturb: workspace is NULL");
+    hipStream_t s = ts::as_stream(stream);
+    const int A = (int)act_dim;
+    if (int rc = ts::ws_reserve(ws, al(4 * (size_t)B * A) + 4096)) return rc;
+    float* fac = static_cast<float*>(ws->base);
+    hipLaunchKernelGGL(cbcq_perturb_kernel, dim3((unsigned)ts::ceil_div(B * A, 256)), dim3(256), 0, s, logits, A, sampled, A, B, A,
+                       (int64_t)0, (float)(phi * max_action), (float)max_action, perturbed_out, A, fac);
+    hipLaunchKernelGGL(cbcq_perturb_bwd_kernel, dim3((unsigned)ts::ceil_div(B * 32, 256)), dim3(256), 0, s, dq_da, A, (const float*)fac,
+                       B, A, A, d_logits_out);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+int ts_cbcq_policy_forward(ts_workspace* ws, const float* pert, const float* critic1, const float* vae, const float* obs,
+                           const float* noise, int64_t N, int64_t T, int64_t obs_dim, int64_t act_dim, int64_t latent_dim,
+                           const ts_mlp_trunk* trunk, const ts_mlp_trunk* vae_trunk, double phi, double max_action,
+                           int32_t pert_first_row, float* act_out, int64_t* idx_out, float* q_out, float* cand_out,
+                           ts_stream_t stream) {
+    TS_REQUIRE(N >= 1 && T >= 1 && T <= 2147483647 && N <= 2147483647 / T, TS_ERR_INVALID_ARG,
+               "ts_cbcq_policy_forward: N, T >= 1 and N T within int");
+    TS_REQUIRE(std::isfinite(max_action) && max_action > 0.0 && std::isfinite(phi) && phi >= 0.0, TS_ERR_INVALID_ARG,
+               "ts_cbcq_policy_forward: max_action > 0, phi >= 0");
+    TS_REQUIRE(pert && critic1 && vae && obs && noise && act_out, TS_ERR_INVALID_ARG, "ts_cbcq_policy_forward: NULL argument");
+    CbcqDims c;
+    if (int rc = cbcq_dims("ts_cbcq_policy_forward", trunk, vae_trunk, obs_dim, act_dim, latent_dim, &c)) return rc;
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_cbcq_policy_forward: workspace is NULL");
+    hipStream_t s = ts::as_stream(stream);
+    const Dims &d = c.d, &v = c.v;
+    const int64_t M = N * T;
+    const Mlp md = make_mlp((int)M, c.kd, 32, v.hid, v.depth, v.fn), mc = make_mlp((int)M, d.kc, 32, d.hid, d.depth, d.fn);
+    const Mlp me1 = make_mlp(1, d.kc, 2 * c.lp, v.hid, v.depth, v.fn);
+    const size_t spl = std::max(split_floats(md), split_floats(mc));
+    struct Bufs { float *x_d, *x_p, *x_q, *split; Act ad, ap, aq; } w;
+    auto carve = [&](char* base) {
+        Carve cv{base};
+        w.x_d = cv.take<float>(M * c.kd); w.x_p = cv.take<float>(M * d.kc); w.x_q = cv.take<float>(M * d.kc);
+        w.split = cv.take<float>(spl);
+        w.ad = take_act(cv, M, 32, v.hid, v.depth); w.ap = take_act(cv, M, 32, d.hid, d.depth); w.aq = take_act(cv, M, 32, d.hid, d.depth);
+        return (size_t)(cv.p - base);
+    };
+    if (int rc = ts::ws_reserve(ws, carve(nullptr) + 4096)) return rc;
+    carve(static_cast<char*>(ws->base));
+    CbcqPackArgs pk{};
+    pk.n = 3; pk.obs_dim = d.obs;
+    pk.s[0] = CbcqSeg{obs, noise, w.x_d, M, (int)T, c.L, c.kd, CBCQ_Z_CLIP, 0};
+    pk.s[1] = CbcqSeg{obs, nullptr, w.x_p, M, (int)T, 0, d.kc, 0.f, 0};
+    pk.s[2] = CbcqSeg{obs, nullptr, w.x_q, M, (int)T, 0, d.kc, 0.f, 0};
+    if (int rc = cbcq_pack(s, pk)) return rc;
+    if (int rc = mlp_forward(s, ws, md, vae + me1.total(), w.x_d, w.ad, w.split)) return rc;
+    hipLaunchKernelGGL(cbcq_decode_out_kernel, dim3((unsigned)ts::ceil_div(M * d.act, 256)), dim3(256), 0, s, w.ad.out, M, M, d.act,
+                       (float)max_action, d.obs, d.kc, w.x_p, w.x_p);
+    TS_LAUNCH_CHECK();
+    if (int rc = mlp_forward(s, ws, mc, pert, w.x_p, w.ap, w.split)) return rc;
+    hipLaunchKernelGGL(cbcq_perturb_kernel, dim3((unsigned)ts::ceil_div(M * d.act, 256)), dim3(256), 0, s, w.ap.out, 32,
+                       (const float*)(w.x_p + d.obs), d.kc, M, d.act, (int64_t)(pert_first_row ? T : 0), (float)(phi * max_action),
+                       (float)max_action, w.x_q + d.obs, d.kc, (float*)nullptr);
+    TS_LAUNCH_CHECK();
+    if (int rc = mlp_forward(s, ws, mc, critic1, w.x_q, w.aq, w.split)) return rc;
+    hipLaunchKernelGGL(cbcq_argmax_kernel, dim3((unsigned)ts::ceil_div(N, 256)), dim3(256), 0, s, w.aq.out, w.x_q, N, (int)T, d.act,
+                       d.obs, d.kc, act_out, idx_out, q_out);
+    if (cand_out)
+        hipLaunchKernelGGL(cbcq_cand_kernel, dim3((unsigned)ts::ceil_div(M * d.act, 256)), dim3(256), 0, s, w.x_q, M, d.act, d.obs, d.kc,
+                           cand_out);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+int ts_cbcq_update(ts_workspace* ws, float* const* state, int64_t adam_step, const float* obs, const float* act, const float* rew,
+                   const float* done, const float* obs_next, const float* eps1, const float* eps2, const float* eps3, int64_t B,
+                   int64_t R, int64_t obs_dim, int64_t act_dim, int64_t latent_dim, const ts_mlp_trunk* trunk,
+                   const ts_mlp_trunk* vae_trunk, const double* hp, float* stats_out4, float* target_out, float* grads_out,
+                   ts_stream_t stream) {
+    TS_REQUIRE(hp != nullptr, TS_ERR_INVALID_ARG, "ts_cbcq_update: hp is NULL");
+    for (int i = 0; i < TS_CBCQ_HP_COUNT; ++i)
+        TS_REQUIRE(std::isfinite(hp[i]), TS_ERR_INVALID_ARG, "ts_cbcq_update: hp[%d] is not finite", i);
+    TS_REQUIRE(B >= 1 && R >= 1, TS_ERR_INVALID_ARG, "ts_cbcq_update: B and R (num_sampled_action) must be >= 1");
+    TS_REQUIRE(R < 2147483647 && B <= 2147483647 / (R + 1), TS_ERR_INVALID_ARG, "ts_cbcq_update: B (R + 1) rows do not fit an int");
+    const double max_action = hp[TS_CBCQ_HP_MAX_ACTION], phi = hp[TS_CBCQ_HP_PHI], lmbda = hp[TS_CBCQ_HP_LMBDA];
+    TS_REQUIRE(max_action > 0.0, TS_ERR_INVALID_ARG, "ts_cbcq_update: max_action must be > 0");
+    TS_REQUIRE(phi >= 0.0, TS_ERR_INVALID_ARG, "ts_cbcq_update: phi must be >= 0");
+    TS_REQUIRE(lmbda >= 0.0 && lmbda <= 1.0, TS_ERR_INVALID_ARG, "ts_cbcq_update: lmbda in [0, 1]");
+    TS_REQUIRE(state && obs && act && rew && done && obs_next && eps1 && eps2 && eps3 && stats_out4 && adam_step >= 1,
+               TS_ERR_INVALID_ARG, "ts_cbcq_update: bad argument");
+    for (int i = TS_CBCQ_ST_CRITIC2; i <= TS_CBCQ_ST_CRITIC2_OLD; ++i)
+        TS_REQUIRE(state[i], TS_ERR_INVALID_ARG, "ts_cbcq_update: BCQ needs both critics (state[%d] of critic 2 is NULL)", i);
+    for (int i = 0; i < TS_CBCQ_ST_COUNT; ++i) TS_REQUIRE(state[i], TS_ERR_INVALID_ARG, "ts_cbcq_update: state[%d] is NULL", i);
+    CbcqDims c;
+    if (int rc = cbcq_dims("ts_cbcq_update", trunk, vae_trunk, obs_dim, act_dim, latent_dim, &c)) return rc;
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_cbcq_update: workspace is NULL");
+    hipStream_t s = ts::as_stream(stream);
+    const Dims &d = c.d, &v = c.v;
+    const int L = c.L, lp = c.lp, kd = c.kd, A = d.act;
+    const int64_t BR = B * R, ND = BR + B;
+    const bool split_decode = hp[TS_CBCQ_HP_SPLIT_DECODE] != 0.0, first_row = hp[TS_CBCQ_HP_PERT_FIRST_ROW] != 0.0;
+    const Mlp me = make_mlp((int)B, d.kc, 2 * lp, v.hid, v.depth, v.fn), md = make_mlp((int)B, kd, 32, v.hid, v.depth, v.fn);
+    const Mlp md2 = make_mlp((int)ND, kd, 32, v.hid, v.depth, v.fn), mdr = make_mlp((int)BR, kd, 32, v.hid, v.depth, v.fn);
+    const Mlp mc = make_mlp((int)B, d.kc, 32, d.hid, d.depth, d.fn), mt = make_mlp((int)BR, d.kc, 32, d.hid, d.depth, d.fn);
+    const size_t slab = std::max(std::max(slab_floats(me), slab_floats(md)), slab_floats(mc));
+    size_t spl = 4;
+    for (const Mlp* m : {&me, &md, &md2, &mdr, &mc, &mt}) spl = std::max(spl, split_floats(*m));
+    const int64_t pe = me.total(), pd = md.total(), pv = pe + pd, pc = mc.total();
+    const unsigned gb = (unsigned)ts::ceil_div(B, 256), g_kl = (unsigned)ts::ceil_div(B * L, 256), g_mse = (unsigned)ts::ceil_div(B * 32, 256);
+
+    // the workspace is carved twice with the same code: once from address 0 for its size, once for real
+    struct Bufs {
+        float *x_sa, *x_d, *x_d2, *x_t, *x_p, *x_q, *dx_d, *dx_q, *d_enc, *d_dec, *d_c[2], *d_q, *d_pol, *fac, *target, *td[2];
+        float *g_vae, *g_c[2], *g_p, *split[2], *norm_part, *part_kl, *part_mse, *part_c;
+        Act ae, ad, ad2, t1, t2, a1, a2, ap;
+        BwdScratch scv, sc[2];
+    } w;
+    auto carve = [&](char* base) {
+        Carve cv{base};
+        w.x_sa = cv.take<float>(B * d.kc); w.x_d = cv.take<float>(B * kd); w.x_d2 = cv.take<float>(ND * kd);
+        w.x_t = cv.take<float>(BR * d.kc); w.x_p = cv.take<float>(B * d.kc); w.x_q = cv.take<float>(B * d.kc);
+        w.dx_d = cv.take<float>(B * kd); w.dx_q = cv.take<float>(B * d.kc);
+        w.d_enc = cv.take<float>(B * 2 * lp); w.d_dec = cv.take<float>(B * 32);
+        w.d_c[0] = cv.take<float>(B * 32); w.d_c[1] = cv.take<float>(B * 32); w.d_q = cv.take<float>(B * 32); w.d_pol = cv.take<float>(B * 32);
+        w.fac = cv.take<float>(B * A); w.target = cv.take<float>(B); w.td[0] = cv.take<float>(B); w.td[1] = cv.take<float>(B);
+        w.g_vae = cv.take<float>(pv); w.g_c[0] = cv.take<float>(pc); w.g_c[1] = cv.take<float>(pc); w.g_p = cv.take<float>(pc);
+        w.split[0] = cv.take<float>(spl); w.split[1] = cv.take<float>(spl);
+        w.norm_part = cv.take<float>(1024); w.part_kl = cv.take<float>(g_kl); w.part_mse = cv.take<float>(g_mse);
+        w.part_c = cv.take<float>(2 * (size_t)gb);
+        w.ae = take_act(cv, B, 2 * lp, v.hid, v.depth); w.ad = take_act(cv, B, 32, v.hid, v.depth);
+        w.ad2 = take_act(cv, ND, 32, v.hid, v.depth);
+        w.t1 = take_act(cv, BR, 32, d.hid, d.depth); w.t2 = take_act(cv, BR, 32, d.hid, d.depth);
+        w.a1 = take_act(cv, B, 32, d.hid, d.depth); w.a2 = take_act(cv, B, 32, d.hid, d.depth); w.ap = take_act(cv, B, 32, d.hid, d.depth);
+        w.scv = take_scratch(cv, B, v.hid, v.depth, slab);
+        for (int k = 0; k < 2; ++k) w.sc[k] = take_scratch(cv, B, d.hid, d.depth, slab);
+        return (size_t)(cv.p - base);
+    };
+    const size_t bytes = carve(nullptr) + 4096;
+    if (int rc = ts::ws_reserve(ws, bytes)) return rc;
+    carve(static_cast<char*>(ws->base));
+
+    float* vae = state[TS_CBCQ_ST_VAE];
+    float* pert = state[TS_CBCQ_ST_PERT];
+    float* crit[2] = {state[TS_CBCQ_ST_CRITIC1], state[TS_CBCQ_ST_CRITIC2]};
+    float* crit_m[2] = {state[TS_CBCQ_ST_CRITIC1_M], state[TS_CBCQ_ST_CRITIC2_M]};
+    float* crit_v[2] = {state[TS_CBCQ_ST_CRITIC1_V], state[TS_CBCQ_ST_CRITIC2_V]};
+    float* crit_old[2] = {state[TS_CBCQ_ST_CRITIC1_OLD], state[TS_CBCQ_ST_CRITIC2_OLD]};
+    float* g_vae = grads_out ? grads_out : w.g_vae;
+    float* g_c[2] = {grads_out ? grads_out + pv : w.g_c[0], grads_out ? grads_out + pv + pc : w.g_c[1]};
+    float* g_p = grads_out ? grads_out + pv + 2 * pc : w.g_p;
+    const double b1 = hp[TS_CBCQ_HP_BETA1], b2 = hp[TS_CBCQ_HP_BETA2], aeps = hp[TS_CBCQ_HP_ADAM_EPS], tau = hp[TS_CBCQ_HP_TAU];
+    auto clip = [&](int i) { return hp[i] > 0.0 ? hp[i] : 0.0; };
+    const float fmax = (float)max_action;
+
+    // every network input that depends on no network, in one launch
+    {
+        CbcqPackArgs pk{};
+        pk.n = 7; pk.obs_dim = d.obs;
+        pk.s[0] = CbcqSeg{obs, act, w.x_sa, B, 1, A, d.kc, 0.f, 0};
+        pk.s[1] = CbcqSeg{obs, nullptr, w.x_d, B, 1, 0, kd, 0.f, 0};
+        pk.s[2] = CbcqSeg{obs_next, eps2, w.x_d2, BR, (int)R, L, kd, CBCQ_Z_CLIP, 0};
+        pk.s[3] = CbcqSeg{obs, eps3, w.x_d2 + BR * kd, B, 1, L, kd, CBCQ_Z_CLIP, 0};
+        pk.s[4] = CbcqSeg{obs_next, nullptr, w.x_t, BR, (int)R, 0, d.kc, 0.f, 0};
+        pk.s[5] = CbcqSeg{obs, nullptr, w.x_p, B, 1, 0, d.kc, 0.f, 0};
+        pk.s[6] = CbcqSeg{obs, nullptr, w.x_q, B, 1, 0, d.kc, 0.f, 0};
+        if (int rc = cbcq_pack(s, pk)) return rc;
+    }
+
+    // 1. VAE step (bcq.py:202-208)
+    if (int rc = mlp_forward(s, ws, me, vae, w.x_sa, w.ae, w.split[0])) return rc;
+    hipLaunchKernelGGL(cbcq_latent_kernel, dim3(g_kl), dim3(256), 0, s, (const float*)w.ae.out, (const float*)(w.ae.out + lp), eps1, B,
+                       L, 2 * lp, kd, w.x_d + d.obs, w.part_kl);
+    TS_LAUNCH_CHECK();
+    if (int rc = mlp_forward(s, ws, md, vae + pe, w.x_d, w.ad, w.split[0])) return rc;
+    hipLaunchKernelGGL(cbcq_recon_kernel, dim3(g_mse), dim3(256), 0, s, (const float*)w.ad.out, act, B, A, 32, 32, fmax, (float*)nullptr,
+                       w.d_dec, w.part_mse);
+    hipLaunchKernelGGL(cbcq_vae_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)w.part_mse, (int)g_mse,
+                       1.f / ((float)B * (float)A), (const float*)w.part_kl, (int)g_kl, 1.f / ((float)B * (float)L), (float*)nullptr,
+                       (float*)nullptr, stats_out4 + 3);
+    TS_LAUNCH_CHECK();
+    if (int rc = mlp_backward(s, ws, md, vae + pe, w.x_d, w.ad, w.d_dec, g_vae + pe, w.dx_d, d.obs, d.obs + L, w.scv)) return rc;
+    hipLaunchKernelGGL(cbcq_latent_bwd_kernel, dim3((unsigned)ts::ceil_div(B * lp, 256)), dim3(256), 0, s, (const float*)w.ae.out,
+                       (const float*)(w.ae.out + lp), eps1, (const float*)(w.dx_d + d.obs), B, L, lp, 2 * lp, kd, w.d_enc, w.d_enc + lp);
+    TS_LAUNCH_CHECK();
+    if (int rc = mlp_backward(s, ws, me, vae, w.x_sa, w.ae, w.d_enc, g_vae, nullptr, 0, 0, w.scv)) return rc;
+    if (hp[TS_CBCQ_HP_VAE_LR] >= 0.0)
+        if (int rc = ts::adam_step(s, vae, state[TS_CBCQ_ST_VAE_M], state[TS_CBCQ_ST_VAE_V], g_vae, pv, adam_step, hp[TS_CBCQ_HP_VAE_LR],
+                                   b1, b2, aeps, clip(TS_CBCQ_HP_VAE_MAX_NORM), w.norm_part))
+            return rc;
+
+    // 2. the updated decoder on [ (s'_rep, clamp(eps2)) | (s, clamp(eps3)) ]: a' of the target and the actor loss's sampled action
+    if (!split_decode) {
+        if (int rc = mlp_forward(s, ws, md2, vae + pe, w.x_d2, w.ad2, w.split[0])) return rc;
+    } else {
+        if (int rc = mlp_forward(s, ws, mdr, vae + pe, w.x_d2, w.ad2, w.split[0])) return rc;
+        if (int rc = mlp_forward(s, ws, md, vae + pe, w.x_d2 + BR * kd, act_rows(w.ad2, BR, v.hid, 32), w.split[0])) return rc;
+    }
+    hipLaunchKernelGGL(cbcq_decode_out_kernel, dim3((unsigned)ts::ceil_div(ND * A, 256)), dim3(256), 0, s, (const float*)w.ad2.out, ND, BR,
+                       A, fmax, d.obs, d.kc, w.x_t, w.x_p);
+    TS_LAUNCH_CHECK();
+    {
+        const Act t12[2] = {w.t1, w.t2};
+        if (int rc = mlp_forward_twin(s, ws, mt, crit_old, w.x_t, t12, w.split)) return rc;
+    }
+    float* target = target_out ? target_out : w.target;
+    hipLaunchKernelGGL(cbcq_target_kernel, dim3(gb), dim3(256), 0, s, (const float*)w.t1.out, (const float*)w.t2.out, 32, rew, done, B,
+                       (int)R, (float)hp[TS_CBCQ_HP_GAMMA], (float)lmbda, (float)(1.0 - lmbda), target);
+    TS_LAUNCH_CHECK();
+
+    // 3. the critic steps (bcq.py:239-245): one twin pass on (s, a), each critic's own rate and clip
+    const Act a12[2] = {w.a1, w.a2};
+    if (int rc = mlp_forward_twin(s, ws, mc, crit, w.x_sa, a12, w.split)) return rc;
+    {
+        CriticLossArgs la{};
+        for (int k = 0; k < 2; ++k) { la.q[k] = a12[k].out; la.td[k] = w.td[k]; la.d_out[k] = w.d_c[k]; la.part[k] = w.part_c + k * gb; }
+        la.ret = target; la.weight = nullptr; la.B = B;
+        hipLaunchKernelGGL(sac_critic_loss_mb_kernel, dim3(gb, 2), dim3(256), 0, s, la);
+        hipLaunchKernelGGL(sac_loss_finish_kernel, dim3(1), dim3(64), 0, s, (const float*)w.part_c, stats_out4 + 1,
+                           (const float*)(w.part_c + gb), stats_out4 + 2, (int)gb, B);
+        TS_LAUNCH_CHECK();
+    }
+    {
+        const float* dh2[2] = {w.d_c[0], w.d_c[1]};
+        if (fused_backward(mc, false, 0, 0)) {
+            const float* xs2[2] = {w.x_sa, w.x_sa};
+            if (int rc = mlp_backward_twin(s, ws, mc, crit, w.x_sa, a12, dh2, nullptr, 0, 0, w.sc)) return rc;
+            if (int rc = mlp_weight_grads(s, ws, 2, mc, xs2, a12, dh2, g_c, w.sc)) return rc;
+        } else {
+            for (int k = 0; k < 2; ++k)
+                if (int rc = mlp_backward(s, ws, mc, crit[k], w.x_sa, a12[k], dh2[k], g_c[k], nullptr, 0, 0, w.sc[k])) return rc;
+        }
+    }
+    for (int k = 0; k < 2; ++k) {
+        const double lr = hp[k == 0 ? TS_CBCQ_HP_CRITIC1_LR : TS_CBCQ_HP_CRITIC2_LR];
+        if (lr >= 0.0)
+            if (int rc = ts::adam_step(s, crit[k], crit_m[k], crit_v[k], g_c[k], pc, adam_step, lr, b1, b2, aeps,
+                                       clip(k == 0 ? TS_CBCQ_HP_CRITIC1_MAX_NORM : TS_CBCQ_HP_CRITIC2_MAX_NORM), w.norm_part))
+                return rc;
+    }
+
+    // 4. the perturbation step (bcq.py:247-253) on the updated critic 1; the gradients this backward would leave on the VAE and
+    // on critic 1 are never used and are not computed
+    if (int rc = mlp_forward(s, ws, mc, pert, w.x_p, w.ap, w.split[0])) return rc;
+    hipLaunchKernelGGL(cbcq_perturb_kernel, dim3((unsigned)ts::ceil_div(B * A, 256)), dim3(256), 0, s, (const float*)w.ap.out, 32,
+                       (const float*)(w.x_p + d.obs), d.kc, B, A, (int64_t)(first_row ? B : 0), (float)(phi * max_action), fmax,
+                       w.x_q + d.obs, d.kc, w.fac);
+    TS_LAUNCH_CHECK();
+    if (int rc = mlp_forward(s, ws, mc, crit[0], w.x_q, w.a1, w.split[0])) return rc;
+    hipLaunchKernelGGL(det_actor_loss_kernel, dim3(1 + (unsigned)ts::ceil_div(B, 1024)), dim3(1024), 0, s, (const float*)w.a1.out, B, w.d_q,
+                       stats_out4);
+    TS_LAUNCH_CHECK();
+    if (int rc = mlp_backward(s, ws, mc, crit[0], w.x_q, w.a1, w.d_q, nullptr, w.dx_q, d.obs, d.obs + A, w.sc[0])) return rc;
+    if (first_row)
+        hipLaunchKernelGGL(cbcq_perturb_bwd_row0_kernel, dim3(1 + (unsigned)ts::ceil_div((B - 1) * 32, 256)), dim3(256), 0, s,
+                           (const float*)(w.dx_q + d.obs), d.kc, (const float*)w.fac, B, A, w.d_pol);
+    else
+        hipLaunchKernelGGL(cbcq_perturb_bwd_kernel, dim3((unsigned)ts::ceil_div(B * 32, 256)), dim3(256), 0, s,
+                           (const float*)(w.dx_q + d.obs), d.kc, (const float*)w.fac, B, A, 32, w.d_pol);
+    TS_LAUNCH_CHECK();
+    if (int rc = mlp_backward(s, ws, mc, pert, w.x_p, w.ap, w.d_pol, g_p, nullptr, 0, 0, w.sc[0])) return rc;
+    if (hp[TS_CBCQ_HP_PERT_LR] >= 0.0)
+        if (int rc = ts::adam_step(s, pert, state[TS_CBCQ_ST_PERT_M], state[TS_CBCQ_ST_PERT_V], g_p, pc, adam_step, hp[TS_CBCQ_HP_PERT_LR],
+                                   b1, b2, aeps, clip(TS_CBCQ_HP_PERT_MAX_NORM), w.norm_part))
+            return rc;
+
+    // 5. Polyak on the three lagged networks (the lagged perturbation net is kept up to date and read by nothing)
+    if (tau > 0.0) {
+        const float ft = (float)tau, omt = (float)(1.0 - tau);
+        hipLaunchKernelGGL(polyak2_kernel, dim3((unsigned)ts::ceil_div(pc, 256)), dim3(256), 0, s, crit_old[0], (const float*)crit[0],
+                           crit_old[1], (const float*)crit[1], pc, ft, omt);
+        hipLaunchKernelGGL(polyak1_kernel, dim3((unsigned)ts::ceil_div(pc, 256)), dim3(256), 0, s, state[TS_CBCQ_ST_PERT_OLD],
+                           (const float*)pert, pc, ft, omt);
+    }
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+}  // extern "C"

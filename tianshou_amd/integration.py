@@ -3012,3 +3012,210 @@ def make_hip_cql(ref=None):
             return out
 
     return HipCQL
+
+
+# ---------------------------------------------------------------------------------------------------
+# continuous BCQ (imitation/bcq.py) on the nets of examples/offline/d4rl_bcq.py
+# ---------------------------------------------------------------------------------------------------
+def _mlp_linears(net, who: str, what: str, output: bool):
+    """The Linear layers of an `MLP` (`.model` is the nn.Sequential) or of a `Net` around one (`.model.model`): Linear, activation,
+    ... with nn.ReLU or nn.Tanh after every hidden Linear and, with `output`, one last Linear without.  -> (hidden Linears + the
+    output Linear, "relu" | "tanh")."""
+    seq = getattr(net, "model", None)
+    seq = getattr(seq, "model", seq)
+    ms = list(seq) if isinstance(seq, torch.nn.Sequential) else []
+    body = ms[:-1] if output else ms
+    ok = len(body) >= 2 and len(body) % 2 == 0 and (not output or type(ms[-1]) is torch.nn.Linear) and all(
+        type(body[i]) is torch.nn.Linear and type(body[i + 1]) in (torch.nn.ReLU, torch.nn.Tanh) for i in range(0, len(body), 2))
+    acts = {type(body[i]) for i in range(1, len(body), 2)} if ok else set()
+    if not ok or len(acts) != 1:
+        raise NotImplementedError(f"{who}: {what} must be an MLP / Net trunk of 1 .. 6 hidden Linear layers with one activation class "
+                                  f"(nn.ReLU or nn.Tanh) after each{' and a single Linear output layer' if output else ''} "
+                                  f"(got {[type(m).__name__ for m in ms]})")
+    return [m for m in ms if type(m) is torch.nn.Linear], "relu" if acts.pop() is torch.nn.ReLU else "tanh"
+
+
+def make_hip_bcq(ref=None):
+    """Returns HipBCQ(BCQ): `_update_with_batch` of imitation/bcq.py:188-263 on the engine (tianshou_amd/cbcq.py over
+    ts_cbcq_update).  Supported networks, those of examples/offline/d4rl_bcq.py: `Perturbation` over an `MLP` or a `Net` with an
+    action-sized output layer, two `ContinuousCritic(Net(concat=True))` with a single-Linear head, and a `VAE` whose encoder and
+    decoder are `MLP`s; every trunk 1 .. 6 hidden layers with nn.ReLU or nn.Tanh, one depth and activation for the perturbation
+    net and the critics, one for encoder and decoder; Adam with the same betas / eps on the four optimizers.
+    `Perturbation.forward` takes `[0]` of its preprocess net's output (continuous.py:409): of the (logits, state) pair of a `Net`,
+    but the first ROW of the logits of a plain `MLP` (the example's choice), so that every row of a batch is perturbed by the first
+    row's logits.  HipBCQ computes what the reference computes in either case (`cfg.pert_first_row`).
+    `_preprocess_batch` only takes the device mirror of the buffer and the indices; `_update_with_batch` gathers obs, act, rew,
+    `done` and obs_next on the device.  The three normal draws of an update come from torch's default generator in the reference's
+    order and shapes (`update_noise="torch"`: randn [B, L], [B R, L], [B, L]) or from the engine's Philox stream (`"device"`, the
+    default).  The learning rates, `lmbda`, `gamma`, `tau` and `phi` are read from the algorithm at every update; a changed
+    `num_sampled_action` or `latent_dim` raises (call `hip_invalidate()`).  Write-back and the `state_dict` round trip cover the
+    four networks, the three lagged copies (`actor_perturbation_target` is kept up to date although nothing reads it, as in the
+    reference) and the four Adam states.  The collector's `policy.forward` stays the reference's Python loop (HipPPO's
+    `policy_forward="hip"` hook is written for its Gaussian policies); `hip_policy_forward(obs)` is the engine's forward for all
+    observations at once.  `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    BCQ = _ref(ref, "tianshou.algorithm.imitation.bcq", "BCQ")
+    BCQTrainingStats = _ref(ref, "tianshou.algorithm.imitation.bcq", "BCQTrainingStats")
+
+    from . import cbcq as Q
+    from . import widths as WD
+
+    who = "HipBCQ"
+
+    class HipBCQ(_HipGlue, BCQ):
+        _HIP_LR = (("pert_lr", "actor_perturbation_optim"), ("critic1_lr", "critic_optim"), ("critic2_lr", "critic2_optim"),
+                   ("vae_lr", "vae_optim"))
+
+        def __init__(self, *args, device="cuda", update_noise="device", noise_seed=None, **kwargs):
+            super().__init__(*args, **kwargs)
+            if update_noise not in ("device", "torch"):
+                raise ValueError("update_noise must be 'device' or 'torch'")
+            self._hip_update_noise, self._hip_noise_calls = update_noise, 0
+            self._hip_noise_key = int(torch.initial_seed() % (2**31 - 1)) if noise_seed is None else int(noise_seed)
+            self._hip_device = torch.device(device)
+            pol = self.policy
+            pert, vae = pol.actor_perturbation, pol.vae
+            # an `MLP` (`.model` is the Sequential) returns the logits, a `Net` (`.model` is an MLP) a (logits, state) pair
+            self._hip_first_row = isinstance(getattr(pert.preprocess_net, "model", None), torch.nn.Sequential)
+            lp, act_p = _mlp_linears(pert.preprocess_net, who, "the perturbation net", True)
+            trunks = [(lp, act_p)]
+            for c in (pol.critic, self.critic2):
+                lc, act_c = _mlp_linears(getattr(c, "preprocess", None), who, "a critic's preprocess net", False)
+                head = list(getattr(getattr(c, "last", None), "model", []))
+                if len(head) != 1 or type(head[0]) is not torch.nn.Linear or head[0].out_features != 1:
+                    raise NotImplementedError(f"{who}: a critic's head must be a single Linear layer with one output")
+                trunks.append((lc + head, act_c))
+            le, act_e = _mlp_linears(vae.encoder, who, "the VAE's encoder", False)
+            ld, act_d = _mlp_linears(vae.decoder, who, "the VAE's decoder", True)
+            if type(vae.mean) is not torch.nn.Linear or type(vae.log_std) is not torch.nn.Linear:
+                raise NotImplementedError(f"{who}: the VAE's mean / log_std heads must be single Linear layers")
+            if len({len(t[0]) for t in trunks}) != 1 or len({t[1] for t in trunks}) != 1 or len(le) + 1 != len(ld) or act_e != act_d:
+                raise NotImplementedError(f"{who}: one depth and one activation for the perturbation net and the critics, and one "
+                                          "for the VAE's encoder and decoder")
+            self._hip_depth, self._hip_actfn, self._hip_vdepth, self._hip_vactfn = len(lp) - 1, act_p, len(le), act_e
+            if not 1 <= self._hip_depth <= WD.MAX_DEPTH or not 1 <= self._hip_vdepth <= WD.MAX_DEPTH:
+                raise NotImplementedError(f"{who}: 1 .. {WD.MAX_DEPTH} hidden layers per trunk")
+            self._hip_act_dim, self._hip_latent = int(lp[-1].out_features), int(vae.mean.out_features)
+            self._hip_obs_dim = int(lp[0].in_features) - self._hip_act_dim
+            if ld[0].in_features != self._hip_obs_dim + self._hip_latent or ld[-1].out_features != self._hip_act_dim \
+                    or not 1 <= self._hip_latent <= 64 or self._hip_act_dim > 32:
+                raise NotImplementedError(f"{who}: decoder on concat(obs, z) with act_dim <= 32 outputs, latent_dim in [1, 64]")
+            wd = lambda ls: tuple(int(m.out_features) for m in ls)  # noqa: E731
+            self._hip_sizes = {"pert": wd(lp[:-1]), "critic1": wd(trunks[1][0][:-1]), "critic2": wd(trunks[2][0][:-1]),
+                               "enc": wd(le), "dec": wd(ld[:-1])}
+            try:
+                self._hip_hidden = WD.engine_hidden([self._hip_sizes[n] for n in ("pert", "critic1", "critic2")])
+                self._hip_vhidden = WD.engine_hidden([self._hip_sizes["enc"], self._hip_sizes["dec"]])
+            except NotImplementedError as e:
+                raise NotImplementedError(f"{who}: hidden layers of widths up to 1024 per network ({e})") from None
+            groups = [_adam_of(o)[1] for o in (self.actor_perturbation_optim, self.critic_optim, self.critic2_optim, self.vae_optim)]
+            if len({(tuple(g["betas"]), g["eps"]) for g in groups}) != 1:
+                raise NotImplementedError(f"{who}: one (betas, eps) for the four Adam optimizers")
+            self._hip_keys = {"pert": list(pert.state_dict().keys()), "critic1": list(pol.critic.state_dict().keys()),
+                              "critic2": list(self.critic2.state_dict().keys()), "vae": list(vae.state_dict().keys())}
+            self._hip_engine = None
+            self._hip_glue_init()
+
+        def hip_extra_state(self) -> dict:
+            return {"update_noise_calls": int(self._hip_noise_calls)}
+
+        def load_hip_extra_state(self, state: dict) -> None:
+            if "update_noise_calls" in state:
+                self._hip_noise_calls = int(state["update_noise_calls"])
+
+        def _hip_cbcq_fields(self) -> dict:
+            pert = self.policy.actor_perturbation
+            norm = lambda o: 0.0 if o._max_grad_norm is None else float(o._max_grad_norm)  # noqa: E731
+            g = _adam_of(self.vae_optim)[1]
+            lr = lambda o: float(_adam_of(o)[1]["lr"])  # noqa: E731
+            return dict(gamma=float(self.gamma), tau=float(self.tau), lmbda=float(self.lmbda), phi=float(pert.phi),
+                        max_action=float(pert.max_action), num_sampled_action=int(self.num_sampled_action),
+                        forward_sampled_times=int(self.policy.forward_sampled_times), pert_lr=lr(self.actor_perturbation_optim),
+                        critic1_lr=lr(self.critic_optim), critic2_lr=lr(self.critic2_optim), vae_lr=lr(self.vae_optim),
+                        betas=tuple(g["betas"]), adam_eps=float(g["eps"]), pert_max_grad_norm=norm(self.actor_perturbation_optim),
+                        critic1_max_grad_norm=norm(self.critic_optim), critic2_max_grad_norm=norm(self.critic2_optim),
+                        vae_max_grad_norm=norm(self.vae_optim), pert_first_row=self._hip_first_row)
+
+        def _hip_parts(self):
+            o, a, ld, dev, sz = self._hip_obs_dim, self._hip_act_dim, self._hip_latent, self._hip_device, self._hip_sizes
+            h, d, hv, dv = self._hip_hidden, self._hip_depth, self._hip_vhidden, self._hip_vdepth
+            ne = 2 * dv + 4                                  # encoder trunk + mean + log_std tensors in the VAE's state_dict order
+            k = self._hip_keys
+
+            def vae_to(f):
+                enc, dec = Q.vae_flat_to_torch(f, o, a, ld, hv, dv, sz["enc"], sz["dec"])
+                return enc + dec
+
+            def critic(name, mod, old, optim):
+                return _ACPart(name, mod, old.module, optim, k[name], lambda t: Q.critic_flat_from_torch(t, o, a, dev, hidden=h),
+                               lambda f: Q.critic_flat_to_torch(f, o, a, h, sizes=sz[name]), "adam_step", True)
+
+            pol = self.policy
+            return (_ACPart("pert", pol.actor_perturbation, self.actor_perturbation_target.module, self.actor_perturbation_optim,
+                            k["pert"], lambda t: Q.pert_flat_from_torch(t, o, a, dev, hidden=h),
+                            lambda f: Q.pert_flat_to_torch(f, o, a, h, d, sz["pert"]), "adam_step", True),
+                    critic("critic1", pol.critic, self.critic_target, self.critic_optim),
+                    critic("critic2", self.critic2, self.critic2_target, self.critic2_optim),
+                    _ACPart("vae", pol.vae, None, self.vae_optim, k["vae"],
+                            lambda t: Q.vae_flat_from_torch(t[:ne], t[ne:], o, a, ld, dev, hidden=hv), vae_to, "adam_step", True))
+
+        def _engine(self):
+            if self._hip_engine is None:
+                flats = {p.name: p.flat() for p in self._hip_parts()}
+                eng = Q.CBCQEngine(self._hip_obs_dim, self._hip_act_dim, self._hip_latent, flats["pert"], flats["critic1"],
+                                   flats["critic2"], flats["vae"], Q.CBCQConfig(**self._hip_cbcq_fields()), hidden=self._hip_hidden,
+                                   depth=self._hip_depth, activation=self._hip_actfn, vae_hidden=self._hip_vhidden,
+                                   vae_depth=self._hip_vdepth, vae_activation=self._hip_vactfn)
+                self._hip_engine = _ac_load(self, eng)         # resume: lagged networks, Adam moments / steps of a loaded checkpoint
+            return self._hip_engine
+
+        def _preprocess_batch(self, batch, buffer, indices):
+            _ac_begin(self, who, buffer, indices)              # the mirror and the indices; the rows are gathered on the device
+            return batch
+
+        def _hip_noises(self, b: int, r: int, ld: int):
+            """The three normal draws of one update, raw, in the reference's order: randn_like(std), decode(obs_next_rep)'s randn,
+            decode(obs)'s randn."""
+            if self._hip_update_noise == "torch":
+                return torch.randn(b, ld), torch.randn(b * r, ld), torch.randn(b, ld)
+            from .buffer import normal_noise
+
+            key, c = self._hip_noise_key ^ 0xBC9, self._hip_noise_calls
+            self._hip_noise_calls += 3
+            return tuple(normal_noise(s, key, c + i, self._hip_device) for i, s in enumerate(((b, ld), (b * r, ld), (b, ld)), 1))
+
+        def _hip_refresh_fields(self, eng) -> None:
+            for k, v in self._hip_cbcq_fields().items():       # read at every update, as the learning rates
+                if k == "num_sampled_action" and getattr(eng.cfg, k) != v:
+                    raise NotImplementedError(f"{who}: `{k}` changed after the engine was built (call hip_invalidate())")
+                setattr(eng.cfg, k, v)
+            if int(self.policy.vae.latent_dim) != eng.latent_dim:
+                raise NotImplementedError(f"{who}: `latent_dim` changed after the engine was built (call hip_invalidate())")
+
+        def _update_with_batch(self, batch):
+            self._hip_refresh_lr()
+            from .buffer import gather_rows_multi
+
+            eng, m, idx = self._hip_engine, self._hip_mirror, self._hip_idx
+            self._hip_refresh_fields(eng)
+            obs, act, obs_next = gather_rows_multi([m.obs, m.act, m.obs_next], idx)
+            rew, done = m.rew[idx].to(torch.float32), m.done[idx].to(torch.float32)
+            stats = eng.update_with_batch(obs, act, rew, done, obs_next,
+                                          *self._hip_noises(int(idx.numel()), eng.cfg.num_sampled_action, eng.latent_dim))
+            s = stats.cpu().numpy()                                               # one D2H per update()
+            self._hip_after_update()
+            return BCQTrainingStats(actor_loss=float(s[0]), critic1_loss=float(s[1]), critic2_loss=float(s[2]), vae_loss=float(s[3]))
+
+        def hip_policy_forward(self, obs, noise=None):
+            """BCQPolicy.forward's actions for all observations in one engine call -> float32[N, act_dim] on the device.  `noise`:
+            the raw normal draws [N, forward_sampled_times, latent_dim] (default: torch.randn, the reference's generator)."""
+            _require_gpu(self._hip_device, who)
+            eng = self._engine()
+            self._hip_refresh_fields(eng)
+            obs = torch.as_tensor(np.asarray(obs, np.float32) if not torch.is_tensor(obs) else obs)
+            if noise is None:
+                noise = torch.randn(obs.shape[0], eng.cfg.forward_sampled_times, eng.latent_dim)
+            return eng.policy_forward(obs, noise)
+
+        _hip_write_back = _ac_write_back
+
+    return HipBCQ
