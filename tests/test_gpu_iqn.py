@@ -9,6 +9,7 @@ import torch
 
 from oracle import oracle_dqn as OD
 from tests import oracle_iqn as OI
+from tests.iqn_edge_cases import fractions_off_the_kink as _fractions_off_the_kink
 
 pytestmark = pytest.mark.gpu
 
@@ -28,25 +29,6 @@ def _engine(c, h, w, A, seed, **kw):
     p = OI.init_params(c, h, w, A, seed=seed)
     eng = I.IQNEngine(c, h, w, A, I.flat_from_torch([p[k] for k in OI.PARAM_ORDER], c, h, w, A), I.IQNConfig(**kw))
     return p, eng
-
-
-def _fractions_off_the_kink(p, rng, B, N, margin=2e-6):
-    """Fractions for a GRADIENT comparison.  d relu / d x jumps at 0, so an embedding pre-activation whose sign the
-    reference's own float32 rounding decides has no reference gradient: a 64-term float32 dot product of terms of size
-    <= 0.4 carries an error of up to 64 * 2^-24 * 0.4 = 1.5e-6, and both signs are legitimate results inside that band
-    (seen: float32 +4.5e-8 where float64 gives -1.8e-8; about 2 of 10^6 elements fall inside the band).  Rows whose
-    float64 pre-activations come closer to 0 than `margin` are redrawn; the rule looks at the reference only."""
-    K = p["emb.w"].shape[1]
-    i_pi = np.pi * torch.arange(1, K + 1, dtype=torch.float32)
-    tau = torch.as_tensor(rng.random((B, N), dtype=np.float32))
-    for _ in range(100):
-        cosv = torch.cos(tau.view(B * N, 1) * i_pi.view(1, K)).double()
-        pre = torch.nn.functional.linear(cosv, p["emb.w"].double(), p["emb.b"].double())
-        close = (pre.abs() < margin).any(dim=1).view(B, N)
-        if not close.any():
-            return tau
-        tau[close] = torch.as_tensor(rng.random(int(close.sum()), dtype=np.float32))
-    raise AssertionError("no fractions off the ReLU kink found")
 
 
 def test_layout_and_flat_round_trip():
