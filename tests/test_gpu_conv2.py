@@ -43,7 +43,7 @@ SHAPES = [  # name, B, IH, IW, IC, K, S, OC, uint8 input
     ("conv3", 96, 9, 9, 64, 3, 1, 64, False),            # 25 border classes, 144 KB weight block
     ("fc1", 300, 1, 1, 3136, 1, 1, 512, False),          # streamed weight slices; dgrad = forward over W^T (ragged 3136)
     ("head", 1000, 1, 1, 512, 1, 1, 32, False),
-    ("hidden", 700, 1, 1, 384, 1, 1, 256, False),        # two resident 128-column blocks
+    ("hidden", 700, 1, 1, 384, 1, 1, 256, False),        # four resident 64-column blocks (K = 384: 128 columns do not fit)
     ("ragged", 513, 1, 1, 64, 1, 1, 96, False),          # streamed, 96 of 128 columns; single reduction chunk pair
     ("uncovered", 19, 19, 19, 32, 4, 2, 32, False),      # input rows / columns no window reaches: dX = 0 there
     ("one_chunk", 5000, 1, 1, 32, 1, 1, 96, False),      # K = 32: one (odd) reduction chunk
