@@ -21,6 +21,10 @@ def _shim():            # every test here imports the reference: no test may dep
 
 @pytest.fixture(scope="module")
 def algo():
+    return _make_ppo_algo()
+
+
+def _make_ppo_algo():
     ref_shim.install()
     import gymnasium as gym
     from torch import nn
@@ -2035,6 +2039,200 @@ def test_ac_write_back_follows_key_order_not_definition_order(monkeypatch):
             assert torch.allclose(named[key].detach(), before[n][key] + (k + 1)), (n, key)
             st = nets[n][3]._optim.state[named[key]]
             assert bool((st["exp_avg"] == k + 1).all()) and bool((st["exp_avg_sq"] == k + 1).all()), (n, key)
+
+
+# ------------------------------------------------------------------------------------ the on-policy classes' one state path
+class _OnDouble:
+    """What the five on-policy class bodies (HipPPO / HipA2C, HipNPG / HipTRPO, HipReinforce, HipPPOCnn / HipA2CCnn,
+    HipPPODiscrete / HipA2CDiscrete) use of their engines, on the CPU.  `vectors` (set per body, see `_on_body`) are the engine's
+    parameter vectors in constructor order, `moments` the two optimizer-state vectors, which belong to the last of them.  Every
+    update adds 2 to the parameters, 0.125 / 0.25 to the two moments and 1 to the step count; preprocessing moves the return
+    statistics to `RMS`, as the engines' does.  `built` collects the engines in the order they were constructed."""
+    RMS = [0.5, 2.0, 7.0]
+    INC = (0.125, 0.25)
+
+    def __init__(self, *args, **kw):                         # dims (c, h, w first for the CNN), one flat per vector, cfg
+        flats = [a for a in args if isinstance(a, torch.Tensor)]
+        self.c, self.h, self.w = args[:3]
+        self.cfg = args[-1]
+        assert len(flats) == len(self.vectors)
+        for n, f in zip(self.vectors, flats):
+            setattr(self, n, f.clone())
+        for n in self.moments:
+            setattr(self, n, torch.zeros_like(flats[-1]))
+        self.adam_step, self.ret_rms = 0, [0.0, 1.0, 0.0]
+        self.built.append(self)
+
+    def preprocess(self, first, *a, **k):                    # `first`: observations, rewards or the device mirror
+        self.ret_rms = list(self.RMS)
+        z = torch.zeros(len(first))
+        return z if self.vectors == ("actor",) else {"obs": first, "act": z, "v_s": z, "returns": z, "adv": z, "logp_old": z}
+
+    def update(self, *a, **k):
+        self.adam_step += 1
+        for n in self.vectors:
+            getattr(self, n).add_(2.0)
+        for n, inc in zip(self.moments, self.INC):
+            getattr(self, n).add_(inc)
+        return torch.tensor([[4.0, 3.0, 2.0, 1.0]])[:, :1 if self.vectors == ("actor",) else 4], 1
+
+    def check(self):
+        pass
+
+
+_ON_BODIES = ["ppo", "npg", "trpo", "reinforce_ln_rmsprop", "ppo_cnn", "ppo_discrete"]
+
+
+def _cpu_sample_all(self, batch_size):
+    """DeviceReplayBuffer.sample_indices(0) without its kernel."""
+    return torch.as_tensor(np.concatenate([
+        self.h_offset[e] + (np.arange(self.h_lengths[e]) if self.h_lengths[e] < (self.h_offset[e + 1] - self.h_offset[e])
+                            else (self.h_insertion[e] + np.arange(self.h_lengths[e])) % self.h_lengths[e])
+        for e in range(self.buffer_num)]).astype(np.int64))
+
+
+def _cpu_cuts(m, idx):
+    """returns.cut_positions without its kernel."""
+    unf = [int(m.h_last_index[e]) for e in range(m.buffer_num) if m.h_lengths[e] > 0 and not bool(m.done[m.h_last_index[e]])]
+    pos = np.nonzero(np.isin(idx.numpy(), unf))[0]
+    return torch.as_tensor(pos), torch.tensor([len(pos)])
+
+
+def _reinforce_ln_rmsprop_algo():
+    """HipReinforce on the per-layer engine: a LayerNorm trunk of unequal widths under RMSprop with momentum (its first state
+    vector is the momentum buffer)."""
+    import gymnasium as gym
+    from tianshou.algorithm.modelfree.reinforce import ProbabilisticActorPolicy
+    from tianshou.algorithm.optim import RMSpropOptimizerFactory
+    from tianshou.utils.net.common import Net
+    from tianshou.utils.net.continuous import ContinuousActorProbabilistic
+    from tianshou_amd import integration as I
+
+    net = Net(state_shape=(17,), hidden_sizes=[48, 40], activation=torch.nn.ReLU, norm_layer=torch.nn.LayerNorm)
+    a = ContinuousActorProbabilistic(preprocess_net=net, action_shape=(6,), unbounded=True)
+    pol = ProbabilisticActorPolicy(actor=a, dist_fn=_normal_dist, action_space=gym.spaces.Box(-1, 1, (6,)))
+    return I.make_hip_reinforce()(policy=pol, optim=RMSpropOptimizerFactory(lr=1e-3, eps=1e-5, momentum=0.9), gamma=0.97, device="cpu")
+
+
+def _on_body(which, monkeypatch):
+    """-> (the algorithm of one class body with an `_OnDouble` in place of its engine, a buffer, the doubles built so far, the
+    names of the optimizer's two state tensors, per engine vector: (flat vector -> tensors in torch layout by the engine module's
+    own converter, the torch parameters it maps to, whether the optimizer holds them)); `rebuild(algo)` builds the engine again."""
+    from tianshou.data import VectorReplayBuffer
+    import tianshou_amd.buffer as B
+    import tianshou_amd.integration as I
+    import tianshou_amd.npg as NG
+    import tianshou_amd.ppo_cnn as PC
+    import tianshou_amd.ppo_discrete as PD
+    import tianshou_amd.ppo_wide as PW
+    import tianshou_amd.reinforce as RF
+    import tianshou_amd.returns as R
+    from tianshou_amd.checkpoint import params_by_keys
+
+    lay = lambda o, h, a: {"k0": 32, "head": 32, "actor_count": 33 * h + (h + 1) * h + (h + 1) * 32 + 32,       # noqa: E731
+                           "critic_count": 33 * h + (h + 1) * h + (h + 1) * 32, "count": 33 * h + (h + 1) * h + (h + 1) * 32}
+    _patch_for_cpu(monkeypatch)
+    monkeypatch.setattr(NG, "layout", lay)
+    monkeypatch.setattr(PD, "layout", lay)
+    monkeypatch.setattr(B.DeviceReplayBuffer, "sample_indices", _cpu_sample_all)
+    monkeypatch.setattr(R, "cut_positions", _cpu_cuts)
+    obs, act, dtype, state = (17,), np.zeros((2, 6), np.float32), np.float32, ("exp_avg", "exp_avg_sq")
+    if which == "ppo":
+        algo, mod, engine = _make_ppo_algo(), I, "PPOEngine"
+        sizes = [p.numel() for p in algo._hip_params()]                           # (the fused layout is the tensors end to end)
+        nets = {"params": (lambda f: torch.split(f, sizes), algo._hip_params(), True)}
+    elif which in ("npg", "trpo"):
+        algo, mod, engine = _natural_algo(which), NG, "NPGEngine"
+        nets = {"actor": (lambda f: NG.actor_flat_to_torch(f, 17, 64, 6), params_by_keys(algo.policy.actor, algo._hip_akeys), False),
+                "critic": (lambda f: NG.critic_flat_to_torch(f, 17, 64), params_by_keys(algo.critic, algo._hip_ckeys), True)}
+    elif which == "reinforce_ln_rmsprop":
+        algo, mod, engine, state = _reinforce_ln_rmsprop_algo(), RF, "NetReinforceEngine", ("momentum_buffer", "square_avg")
+        nets = {"actor": (lambda f: PW.net_flat_to_tensors(f, 17, [48, 40], 6, True, layer_norm=True),
+                          params_by_keys(algo.policy.actor, algo._hip_keys), True)}
+    elif which == "ppo_cnn":
+        algo, mod, engine, obs, act, dtype = _ppo_cnn_algo(), PC, "CnnPPOEngine", (4, 84, 84), np.zeros(2, np.int64), np.uint8
+        nets = {"params": (lambda f: PC.flat_to_torch(f, 4, 84, 84, 6), algo._hip_params(), True)}
+    else:
+        algo, mod, engine, obs, act = _ppo_discrete_algo(), PD, "DiscretePPOEngine", (4,), np.zeros(2, np.int64)
+        nets = {"params": (lambda f: PD.flat_to_torch(f, 4, 64, 2), algo._hip_params(), True)}
+    double = type("Double", (_OnDouble,), {"built": [], "vectors": tuple(nets),
+                                           "moments": ("critic_m", "critic_v") if "critic" in nets else ("adam_m", "adam_v")})
+    monkeypatch.setattr(mod, engine, double)
+    buf = VectorReplayBuffer(32, 2)
+    _fill(buf, 12, obs, act, dtype)
+    return algo, buf, double.built, state, nets, (lambda a: a._engine(4, 84, 84) if which == "ppo_cnn" else a._engine())
+
+
+def _on_update(algo, buf):
+    from tianshou.utils.torch_utils import policy_within_training_step
+
+    with policy_within_training_step(algo.policy):
+        return algo.update(buffer=buf, batch_size=8, repeat=2)
+
+
+@pytest.mark.parametrize("which", _ON_BODIES)
+def test_on_policy_engine_rebuilt_from_torch_receives_what_the_last_one_wrote_back(which, monkeypatch):
+    """Load and write-back are inverses: after one update and a `state_dict()` (HipPPO's optimizer state moves there), the engine
+    is dropped and built again from the torch modules and torch.optim; it starts from the parameters, optimizer moments, step
+    count and return statistics the first one ended with.  The NPG / TRPO actor has no optimizer: its part carries no moments,
+    the critic's does.  (Compared in torch layout: the padding of a flat vector is not state.)"""
+    algo, buf, built, _, nets, rebuild = _on_body(which, monkeypatch)
+    _on_update(algo, buf)
+    algo.state_dict()
+    first = built[0]
+    algo._hip_invalidate()
+    second = rebuild(algo)
+    assert built == [first, second] and second is not first
+    assert second.adam_step == first.adam_step == 1 and second.ret_rms == first.ret_rms == _OnDouble.RMS
+    for name, (to_torch, params, _) in nets.items():
+        a, b = to_torch(getattr(first, name)), to_torch(getattr(second, name))
+        assert len(a) == len(b) > 0 and all(torch.equal(x, y) for x, y in zip(a, b)), name
+        assert len(params) == len(b) and all(torch.equal(p.detach().reshape(-1), y.reshape(-1)) for p, y in zip(params, b)), name
+    to_torch = list(nets.values())[-1][0]                                     # the vector the optimizer holds
+    for name, inc in zip(first.moments, _OnDouble.INC):
+        a, b = to_torch(getattr(first, name)), to_torch(getattr(second, name))
+        assert all(torch.equal(x, y) for x, y in zip(a, b)), name
+        assert all(bool((y == inc).all()) for y in b), name                   # ... and it is what the update left, not zeros
+    parts = algo._hip_parts(second)
+    assert [p.name for p in parts] == list(nets) and [p.moments for p in parts if p.moments] == [first.moments]
+    assert [p.moments is not None for p in parts] == [held for _, _, held in nets.values()]
+
+
+@pytest.mark.parametrize("which", _ON_BODIES)
+def test_on_policy_write_back_leaves_a_foreign_write_alone(which, monkeypatch):
+    """`_hip_write_back` of every on-policy class goes through `_hip_put`: a parameter somebody else has written since the engine
+    snapshotted it (`_hip_skip_ids`, set by the `_hip_engine` property) keeps its value, all others, of every module, are written."""
+    algo, buf, built, _, nets, _ = _on_body(which, monkeypatch)
+    _on_update(algo, buf)
+    params = [p for _, ps, _ in nets.values() for p in ps]
+    before = [p.detach().clone() for p in params]
+    for name in nets:
+        getattr(built[0], name).add_(1.0)
+    algo.__dict__["_hip_skip_ids"] = {id(params[1])}
+    try:
+        algo._hip_write_back()
+    finally:
+        algo.__dict__["_hip_skip_ids"] = None
+    assert torch.equal(params[1].detach(), before[1])
+    assert all(torch.allclose(p.detach(), b + 1.0) for i, (p, b) in enumerate(zip(params, before)) if i != 1)
+
+
+@pytest.mark.parametrize("which", _ON_BODIES)
+def test_on_policy_optimizer_state_arrives_with_the_update_except_for_hip_ppo(which, monkeypatch):
+    """After an update and before any reader the four eager bodies hold the optimizer's state of step 1 in torch.optim; HipPPO's
+    torch.optim is still what it was (empty) and receives the same state at `state_dict()` (`_hip_flush`)."""
+    algo, buf, built, (k_m, k_v), nets, _ = _on_body(which, monkeypatch)
+    opt = algo.optim._optim
+    held = [p for _, ps, h in nets.values() if h for p in ps]
+    assert held and not opt.state
+    _on_update(algo, buf)
+    if which == "ppo":
+        assert not opt.state and all(p not in opt.state for p in held)
+        algo.state_dict()
+    assert set(opt.state) == set(held)
+    for p in held:
+        st = opt.state[p]
+        assert float(st["step"]) == 1.0 and bool((st[k_m] == 0.125).all()) and bool((st[k_v] == 0.25).all())
 
 
 def test_device_permutation_key_follows_numpy_seed_and_travels_in_the_checkpoint():

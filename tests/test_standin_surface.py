@@ -169,7 +169,7 @@ def test_real_subclass_and_standin_subclass_are_the_same_hook_code():
     from tianshou_amd.integration import make_hip_ppo
 
     A, B = make_hip_ppo("ppo"), make_hip_ppo("ppo", ref=SI)
-    for name in ("update", "_preprocess_batch", "_update_with_batch", "_engine", "_sync_back", "_hip_flush"):
+    for name in ("update", "_preprocess_batch", "_update_with_batch", "_engine", "_hip_write_back", "_hip_flush"):
         fa, fb = getattr(A, name), getattr(B, name)
         assert fa.__code__.co_code == fb.__code__.co_code and fa.__code__.co_firstlineno == fb.__code__.co_firstlineno, name
 

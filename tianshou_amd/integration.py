@@ -9,7 +9,8 @@ keeping the Policy / Algorithm API, the Batch fields (`v_s`, `returns`, `adv`, `
 the stats dataclasses and `state_dict()` (parameters and Adam moments are copied back into the
 torch modules / optimizer after every update(), or, under `write_back="lazy"`, when somebody reads them; for the
 Q-learning classes, HipDQN to HipRainbow, that copy is `_q_write_back`; for the off-policy actor-critic classes, HipSAC, HipREDQ,
-HipDiscreteSAC and HipTD3 / HipDDPG / HipTD3BC, it is `_ac_write_back`).  Supported net: the MuJoCo actor-critic of
+HipDiscreteSAC and HipTD3 / HipDDPG / HipTD3BC, it is `_ac_write_back`; for the on-policy classes, HipPPO to HipPPODiscrete and their A2C
+variants, it is `_on_write_back`, and HipPPO's Adam moments alone wait for a reader).  Supported net: the MuJoCo actor-critic of
 examples/mujoco/mujoco_ppo.py (Net[64,64] tanh, ContinuousActorProbabilistic(unbounded=True) with a
 state-independent sigma, ContinuousCritic); anything else raises at construction.
 """
@@ -591,6 +592,8 @@ def make_hip_ppo(algo: str = "ppo", ref=None):
     Batch = _ref(ref, "tianshou.data", "Batch")
     PPO = _on_policy_base(algo, ref)
 
+    from . import ppo_wide as PW
+
     class HipPPO(_HipGlue, PPO):
         def __init__(self, *args, device="cuda", permutations="device", perm_seed=None, data_parallel=False, group=None,
                      allreduce=None, shard_buffer=True, policy_forward="hip", sampling="device", noise_seed=None, **kwargs):
@@ -668,64 +671,43 @@ def make_hip_ppo(algo: str = "ppo", ref=None):
             return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
         # -- engine life cycle ------------------------------------------------------------------
-        def _hip_flat(self, tensors) -> torch.Tensor:
-            """13 tensors in `_hip_params()` order (parameters or Adam moments) -> the engine's flat vector."""
+        def _hip_params(self):
+            ka, kc = _net_keys(self.policy.actor, self.critic)      # == TIANSHOU_ACTOR_KEYS / _CRITIC_KEYS for Net[h, h]
+            return params_by_keys(self.policy.actor, ka) + params_by_keys(self.critic, kc)
+
+        def _hip_parts(self, eng=None):
+            """One vector: the actor's tensors, then the critic's, in `_hip_params()` order (13 for Net[h, h])."""
             obs_dim, act_dim, hidden, kind = self._hip_dims
+            params, dev = self._hip_params(), self._hip_device
             if kind == "fused":
-                return torch.cat([t.detach().reshape(-1).float() for t in tensors]).to(self._hip_device).contiguous()
-            if kind == "net":
-                from .ppo_wide import net_flat_from_tensors
-
-                cs, ln = "conditioned_sigma" in hidden[3:], _ln_eps_of(hidden) is not None
-                na = (4 if ln else 2) * len(hidden[0]) + 2 + (2 if cs else 1)
-                return torch.cat([net_flat_from_tensors(list(tensors[:na]), obs_dim, list(hidden[0]), act_dim, self._hip_device,
-                                                        conditioned_sigma=cs, layer_norm=ln),
-                                  net_flat_from_tensors(list(tensors[na:]), obs_dim, list(hidden[1]), None, self._hip_device,
-                                                        layer_norm=ln)]).contiguous()
-            from .ppo_wide import flat_from_tensors
-
-            return flat_from_tensors(list(tensors[:7]), list(tensors[7:]), obs_dim, hidden, act_dim, self._hip_device)
-
-        def _hip_unflat(self, flat: torch.Tensor) -> list[torch.Tensor]:
-            """The engine's flat vector -> 13 tensors in `_hip_params()` order (shapes as flattened / nn.Linear layout)."""
-            obs_dim, act_dim, hidden, kind = self._hip_dims
-            if kind == "fused":
-                return list(torch.split(flat, [p.numel() for p in self._hip_params()]))
-            if kind == "net":
-                a, c = self._engine().flat_to_tensors(flat)
-                return a + c
-            from .ppo_wide import flat_to_tensors
-
-            a, c = flat_to_tensors(flat, obs_dim, hidden, act_dim)
-            return a + c
+                conv = (lambda t: torch.cat([x.detach().reshape(-1).float() for x in t]).to(dev).contiguous(),
+                        lambda f: torch.split(f, [p.numel() for p in params]))
+            elif kind == "net":
+                ha, hc, kw = list(hidden[0]), list(hidden[1]), dict(layer_norm=_ln_eps_of(hidden) is not None)
+                cs = "conditioned_sigma" in hidden[3:]
+                na = (4 if kw["layer_norm"] else 2) * len(ha) + 2 + (2 if cs else 1)
+                conv = (lambda t: torch.cat([PW.net_flat_from_tensors(list(t[:na]), obs_dim, ha, act_dim, dev, conditioned_sigma=cs, **kw),
+                                             PW.net_flat_from_tensors(list(t[na:]), obs_dim, hc, None, dev, **kw)]).contiguous(),
+                        lambda f: sum(eng.flat_to_tensors(f), []))
+            else:
+                conv = (lambda t: PW.flat_from_tensors(list(t[:7]), list(t[7:]), obs_dim, hidden, act_dim, dev),
+                        lambda f: sum(PW.flat_to_tensors(f, obs_dim, hidden, act_dim), []))
+            return [_OnPart("params", ("adam_m", "adam_v"), self.optim, params, *conv)]
 
         def _engine(self):
             if self._hip_engine is None:
                 obs_dim, act_dim, hidden, kind = self._hip_dims
-                flat = self._hip_flat([p.detach() for p in self._hip_params()])
+                flat, cfg = self._hip_parts()[0].flat(), ppo_config_from(self)
                 if kind == "fused":
-                    eng = PPOEngine(obs_dim, act_dim, flat, ppo_config_from(self))
+                    eng = PPOEngine(obs_dim, act_dim, flat, cfg)
                 elif kind == "net":
-                    from .ppo_wide import NetPPOEngine
-
                     ln_eps = _ln_eps_of(hidden)
-                    eng = NetPPOEngine(obs_dim, act_dim, hidden[0], hidden[1], hidden[2], flat, ppo_config_from(self),
-                                       conditioned_sigma="conditioned_sigma" in hidden[3:], layer_norm=ln_eps is not None,
-                                       ln_eps=ln_eps or 1e-5)
+                    eng = PW.NetPPOEngine(obs_dim, act_dim, hidden[0], hidden[1], hidden[2], flat, cfg, layer_norm=ln_eps is not None,
+                                          ln_eps=ln_eps or 1e-5, conditioned_sigma="conditioned_sigma" in hidden[3:])
                 else:
-                    from .ppo_wide import WidePPOEngine
-
-                    eng = WidePPOEngine(obs_dim, act_dim, hidden, flat, ppo_config_from(self))
-                self._hip_engine = eng
-                eng.ret_rms = [float(self.ret_rms.mean), float(self.ret_rms.var), float(self.ret_rms.count)]
-                # resume: Adam moments / step of a loaded checkpoint (algorithm_base.py:523-543)
-                ms, vs, step = adam_state(self.optim._optim, self._hip_params())
-                eng.adam_m, eng.adam_v, eng.adam_step = self._hip_flat(ms), self._hip_flat(vs), step
+                    eng = PW.WidePPOEngine(obs_dim, act_dim, hidden, flat, cfg)
+                self._hip_engine = _on_load(self, eng)
             return self._hip_engine
-
-        def _hip_params(self):
-            ka, kc = _net_keys(self.policy.actor, self.critic)      # == TIANSHOU_ACTOR_KEYS / _CRITIC_KEYS for Net[h, h]
-            return params_by_keys(self.policy.actor, ka) + params_by_keys(self.critic, kc)
 
         def _hip_runner(self, eng):
             if not self._hip_dp_on:
@@ -734,25 +716,16 @@ def make_hip_ppo(algo: str = "ppo", ref=None):
 
             return self._hip_dp(DataParallelPPO if self._hip_dims[3] == "fused" else DataParallelWidePPO, eng)
 
-        def _sync_back(self) -> None:
-            """After every update(): engine parameters -> nn.Parameters (the collector acts with the torch modules;
-            device-to-device when they live on the GPU, no host synchronisation) and the three ret_rms scalars.
-            The Adam moments are only needed by `state_dict()` (algorithm_base.py:523-543) and move there
-            (`_hip_flush`)."""
-            eng = self._hip_engine
-            with torch.no_grad():
-                for p, t in zip(self._hip_params(), self._hip_unflat(eng.params)):
-                    p.copy_(t.reshape(p.shape).to(p.device))
-            self.ret_rms.mean, self.ret_rms.var, self.ret_rms.count = eng.ret_rms
+        def _hip_write_back(self) -> None:
+            """After every update(): parameters (the collector acts with the torch modules) and ret_rms.  The Adam moments are
+            only needed by `state_dict()` (algorithm_base.py:523-543) and move there (`_hip_flush`)."""
+            _on_write_back(self, optimizer=False)
             self._hip_adam_dirty = True
 
         def _hip_flush(self) -> None:
-            eng = self._hip_engine
-            if eng is None or not getattr(self, "_hip_adam_dirty", False):
-                return
-            store_adam_state(self.optim._optim, self._hip_params(), self._hip_unflat(eng.adam_m), self._hip_unflat(eng.adam_v),
-                             eng.adam_step)
-            self._hip_adam_dirty = False
+            if getattr(self, "_hip_adam_dirty", False):
+                _on_write_back(self, params=False)
+                self._hip_adam_dirty = False
 
         # -- Algorithm.update ---------------------------------------------------------------------------
         def update(self, buffer, batch_size, repeat):
@@ -837,16 +810,10 @@ def make_hip_ppo(algo: str = "ppo", ref=None):
                 key = ((self._hip_perm_seed * 0x9E3779B97F4A7C15) ^ (self._hip_updates << 20) ^ (rank << 52)) & (2**64 - 1)
                 perms = [random_permutation(n, key + r, self._hip_device) for r in range(repeat)]
             losses, steps = self._hip_runner(eng).update(self._hip_batch, batch_size, repeat, perms)
-            arr = losses.cpu().numpy().astype(np.float64)              # one D2H per update()
+            stats = _a2c_stats(A2CTrainingStats, SequenceSummaryStats.from_sequence, losses, steps)
             eng.check()                                                # surfaces a stuck GAE hand-off (never observed)
-            self._sync_back()
-            return A2CTrainingStats(
-                loss=SequenceSummaryStats.from_sequence(arr[:, 0]),
-                actor_loss=SequenceSummaryStats.from_sequence(arr[:, 1]),
-                vf_loss=SequenceSummaryStats.from_sequence(arr[:, 2]),
-                ent_loss=SequenceSummaryStats.from_sequence(arr[:, 3]),
-                gradient_steps=steps,
-            )
+            self._hip_write_back()
+            return stats
 
     if algo == "a2c":
         HipPPO.__name__ = HipPPO.__qualname__ = "HipA2C"
@@ -907,12 +874,33 @@ def _make_hip_natural(algo: str, ref=None):
             self._hip_engine = None
             self._hip_glue_init()
 
+        def _hip_parts(self, eng=None):
+            """The actor (no optimizer: natural-gradient steps) and the critic; the per-layer engine brings its own converters."""
+            dev = self._hip_device
+            aparams = params_by_keys(self.policy.actor, self._hip_akeys)
+            cparams = params_by_keys(self.critic, self._hip_ckeys)
+            obs_dim, act_dim = aparams[0].shape[1], aparams[-3].shape[0]          # (the actor ends in mu.weight, mu.bias, sigma_param)
+            if self._hip_two:
+                hidden, sizes = self._hip_hidden, self._hip_sizes     # (two widths per network, embedded: tianshou_amd.widths)
+                conv = (lambda t: NG.actor_flat_from_torch(t, obs_dim, hidden, act_dim, dev),
+                        lambda f: NG.actor_flat_to_torch(f, obs_dim, hidden, act_dim, sizes=sizes["actor"]),
+                        lambda t: NG.critic_flat_from_torch(t, obs_dim, hidden, dev),
+                        lambda f: NG.critic_flat_to_torch(f, obs_dim, hidden, sizes=sizes["critic"]))
+            elif eng is not None:
+                conv = (eng.actor_from_tensors, eng.actor_to_tensors, eng.critic_from_tensors, eng.critic_to_tensors)
+            else:
+                from .ppo_wide import net_flat_from_tensors as nf
+
+                ha, hc, _ = self._hip_trunks
+                conv = (lambda t: nf(t, obs_dim, ha, act_dim, dev), None, lambda t: nf(t, obs_dim, hc, None, dev), None)
+            return [_OnPart("actor", None, None, aparams, conv[0], conv[1]),
+                    _OnPart("critic", ("critic_m", "critic_v"), self.optim, cparams, conv[2], conv[3])]
+
         def _engine(self):
             if self._hip_engine is None:
-                sa, sc = self.policy.actor.state_dict(), self.critic.state_dict()
-                ka, kc = self._hip_akeys, self._hip_ckeys
-                obs_dim, act_dim = sa[ka[0]].shape[1], sa["mu.model.0.weight"].shape[0]
-                opt, g = _adam_of(self.optim)
+                actor, critic = self._hip_parts()
+                obs_dim, act_dim = actor.params[0].shape[1], actor.params[-3].shape[0]
+                _, g = _adam_of(self.optim)
                 cfg = NG.NPGConfig(algo=algo, gamma=self.gamma, gae_lambda=self.gae_lambda,
                                    optim_critic_iters=self.optim_critic_iters,
                                    trust_region_size=float(getattr(self, "trust_region_size", 0.5)),
@@ -921,37 +909,17 @@ def _make_hip_natural(algo: str, ref=None):
                                    backtrack_coeff=float(getattr(self, "backtrack_coeff", 0.8)),
                                    max_backtracks=int(getattr(self, "max_backtracks", 10)), lr=g["lr"], betas=tuple(g["betas"]),
                                    adam_eps=g["eps"], max_grad_norm=self.optim._max_grad_norm)
-                dev = self._hip_device
-                ms, vs, step = adam_state(opt, params_by_keys(self.critic, kc))     # resume
-                if self._hip_two:
-                    hidden = self._hip_hidden
-                    eng = self._hip_engine = NG.NPGEngine(
-                        obs_dim, act_dim, hidden, NG.actor_flat_from_torch([sa[k] for k in ka], obs_dim, hidden, act_dim, dev),
-                        NG.critic_flat_from_torch([sc[k] for k in kc], obs_dim, hidden, dev), cfg)
-                    eng.critic_m = NG.critic_flat_from_torch(ms, obs_dim, hidden, dev)
-                    eng.critic_v = NG.critic_flat_from_torch(vs, obs_dim, hidden, dev)
-                else:
-                    from .ppo_wide import net_flat_from_tensors as nf
-
-                    ha, hc, act_name = self._hip_trunks
-                    eng = self._hip_engine = NG.NetNPGEngine(
-                        obs_dim, act_dim, ha, hc, act_name, nf([sa[k] for k in ka], obs_dim, ha, act_dim, dev),
-                        nf([sc[k] for k in kc], obs_dim, hc, None, dev), cfg)
-                    eng.critic_m, eng.critic_v = eng.critic_from_tensors(ms), eng.critic_from_tensors(vs)
-                eng.ret_rms = [float(self.ret_rms.mean), float(self.ret_rms.var), float(self.ret_rms.count)]
-                eng.adam_step = step
+                Engine, net = (NG.NPGEngine, (self._hip_hidden,)) if self._hip_two else (NG.NetNPGEngine, self._hip_trunks)
+                self._hip_engine = _on_load(self, Engine(obs_dim, act_dim, *net, actor.flat(), critic.flat(), cfg))
             return self._hip_engine
 
+        _hip_write_back = _on_write_back
+
         def _preprocess_batch(self, batch, buffer, indices):
-            _require_gpu(self._hip_device, who)
-            eng = self._engine()
-            dev = self._hip_device
-            t = lambda x, dt=None: torch.as_tensor(np.ascontiguousarray(x), device=dev) if dt is None \
-                else torch.as_tensor(np.ascontiguousarray(x), device=dev).to(dt)  # noqa: E731
-            cut = np.nonzero(np.isin(indices, buffer.unfinished_index()))[0]      # algorithm_base.py:715
+            eng, t, cut = _on_host_batch(self, who, buffer, indices)
             b = self._hip_pre = eng.preprocess(t(batch.obs, torch.float32), t(batch.obs_next, torch.float32),
                                                t(batch.act, torch.float32), t(batch.rew, torch.float64), t(batch.terminated),
-                                               t(batch.truncated), t(cut))
+                                               t(batch.truncated), cut)
             batch.v_s, batch.returns, batch.adv, batch.logp_old, batch.act = b["v_s"], b["returns"], b["adv"], b["logp_old"], b["act"]
             return batch
 
@@ -961,22 +929,7 @@ def _make_hip_natural(algo: str, ref=None):
             perms = [np.random.permutation(len(batch)) for _ in range(repeat)]     # Batch.split, batch.py:1209
             stats, _ = eng.update(self._hip_pre, batch_size, repeat, perms)
             arr = stats.cpu().numpy().astype(np.float64)                          # one D2H per update()
-            if self._hip_two:
-                dims, szc = (eng.obs_dim, eng.hidden), self._hip_sizes["critic"]
-                actor_t = NG.actor_flat_to_torch(eng.actor, eng.obs_dim, eng.hidden, eng.act_dim, sizes=self._hip_sizes["actor"])
-                critic_t, m_t, v_t = (NG.critic_flat_to_torch(x, *dims, sizes=szc) for x in (eng.critic, eng.critic_m, eng.critic_v))
-            else:
-                actor_t = eng.actor_to_tensors(eng.actor)
-                critic_t, m_t, v_t = (eng.critic_to_tensors(x) for x in (eng.critic, eng.critic_m, eng.critic_v))
-            cparams = params_by_keys(self.critic, self._hip_ckeys)
-            with torch.no_grad():
-                for p, t in zip(params_by_keys(self.policy.actor, self._hip_akeys), actor_t):
-                    p.copy_(t.reshape(p.shape))
-                for p, t in zip(cparams, critic_t):
-                    p.copy_(t.reshape(p.shape))
-            store_adam_state(self.optim._optim, cparams, [t.reshape(p.shape) for p, t in zip(cparams, m_t)],
-                             [t.reshape(p.shape) for p, t in zip(cparams, v_t)], eng.adam_step)
-            self.ret_rms.mean, self.ret_rms.var, self.ret_rms.count = eng.ret_rms
+            self._hip_write_back()
             seq = SequenceSummaryStats.from_sequence
             kw = dict(actor_loss=seq(arr[:, 0]), vf_loss=seq(arr[:, 1]), kl=seq(arr[:, 2]))
             if algo == "trpo":
@@ -1008,6 +961,7 @@ def make_hip_reinforce(ref=None):
     SequenceSummaryStats = _ref(ref, "tianshou.data", "SequenceSummaryStats")
 
     from . import npg as NG
+    from . import ppo_wide as PW
     from . import reinforce as RF
 
     who = "HipReinforce"
@@ -1051,57 +1005,43 @@ def make_hip_reinforce(ref=None):
             hidden, obs_dim = sa[self._hip_keys[0]].shape
             return obs_dim, hidden, sa["mu.model.0.weight"].shape[0]
 
-        def _to_flat(self, tensors):
-            obs_dim, hidden, act_dim = self._dims()
+        def _hip_parts(self, eng=None):
+            params = params_by_keys(self.policy.actor, self._hip_keys)
+            (hidden, obs_dim), act_dim = params[0].shape, params[-3].shape[0]     # (`_dims()` without its walk; the keys end in mu, sigma_param)
+            dev, sizes, ln = self._hip_device, list(self._hip_net[0]), self._hip_ln is not None
             if self._hip_kind == "legacy":
-                return NG.actor_flat_from_torch(tensors, obs_dim, hidden, act_dim, self._hip_device)
-            from .ppo_wide import net_flat_from_tensors
-
-            return net_flat_from_tensors(list(tensors), obs_dim, list(self._hip_net[0]), act_dim, self._hip_device,
-                                         layer_norm=self._hip_ln is not None)
-
-        def _from_flat(self, flat):
-            obs_dim, hidden, act_dim = self._dims()
-            if self._hip_kind == "legacy":
-                return NG.actor_flat_to_torch(flat, obs_dim, hidden, act_dim)
-            from .ppo_wide import net_flat_to_tensors
-
-            return net_flat_to_tensors(flat, obs_dim, list(self._hip_net[0]), act_dim, True, layer_norm=self._hip_ln is not None)
+                conv = (lambda t: NG.actor_flat_from_torch(t, obs_dim, hidden, act_dim, dev),
+                        lambda f: NG.actor_flat_to_torch(f, obs_dim, hidden, act_dim))
+            else:
+                conv = (lambda t: PW.net_flat_from_tensors(list(t), obs_dim, sizes, act_dim, dev, layer_norm=ln),
+                        lambda f: PW.net_flat_to_tensors(f, obs_dim, sizes, act_dim, True, layer_norm=ln))
+            return [_OnPart("actor", ("adam_m", "adam_v"), self.optim, params, *conv)]
 
         def _engine(self):
             if self._hip_engine is None:
-                sa = self.policy.actor.state_dict()
-                dims = self._dims()
-                opt = self.optim._optim
+                part, = self._hip_parts()
+                obs_dim, hidden, act_dim = self._dims()
                 of = self._hip_net[3]
                 drc = self.discounted_return_computation
                 cfg = RF.ReinforceConfig(gamma=drc.gamma, return_standardization=drc.return_standardization, lr=of["lr"],
                                          betas=tuple(of.get("betas", (0.9, 0.999))), adam_eps=of["adam_eps"],
                                          max_grad_norm=self.optim._max_grad_norm)
-                flat = self._to_flat([sa[k] for k in self._hip_keys])
                 if self._hip_kind == "legacy":
-                    eng = self._hip_engine = RF.ReinforceEngine(dims[0], dims[2], dims[1], flat, cfg)
+                    eng = RF.ReinforceEngine(obs_dim, act_dim, hidden, part.flat(), cfg)
                 else:
                     hidden_sizes, act_name, max_action, _ = self._hip_net
-                    eng = self._hip_engine = RF.NetReinforceEngine(dims[0], dims[2], hidden_sizes, act_name, flat, cfg,
-                                                                   max_action=max_action, optimizer=of,
-                                                                   layer_norm=self._hip_ln is not None, ln_eps=self._hip_ln or 1e-5)
-                eng.ret_rms = [float(drc.ret_rms.mean), float(drc.ret_rms.var), float(drc.ret_rms.count)]
-                ms, vs, step = adam_state(opt, params_by_keys(self.policy.actor, self._hip_keys))     # resume
-                eng.adam_m, eng.adam_v = self._to_flat(ms), self._to_flat(vs)
-                eng.adam_step = step
+                    eng = RF.NetReinforceEngine(obs_dim, act_dim, hidden_sizes, act_name, part.flat(), cfg, max_action=max_action,
+                                                optimizer=of, layer_norm=self._hip_ln is not None, ln_eps=self._hip_ln or 1e-5)
+                self._hip_engine = _on_load(self, eng)
             return self._hip_engine
 
+        _hip_write_back = _on_write_back
+
         def _preprocess_batch(self, batch, buffer, indices):
-            _require_gpu(self._hip_device, who)
-            eng = self._engine()
-            dev = self._hip_device
-            t = lambda x: torch.as_tensor(np.ascontiguousarray(x), device=dev)  # noqa: E731
-            cut = np.nonzero(np.isin(indices, buffer.unfinished_index()))[0]      # algorithm_base.py:715
-            batch.returns = eng.preprocess(t(batch.rew).to(torch.float64), t(batch.terminated), t(batch.truncated), t(cut))
-            self._hip_obs, self._hip_act = t(batch.obs).to(torch.float32), t(batch.act).to(torch.float32)
-            drc = self.discounted_return_computation
-            drc.ret_rms.mean, drc.ret_rms.var, drc.ret_rms.count = eng.ret_rms
+            eng, t, cut = _on_host_batch(self, who, buffer, indices)
+            batch.returns = eng.preprocess(t(batch.rew, torch.float64), t(batch.terminated), t(batch.truncated), cut)
+            self._hip_obs, self._hip_act = t(batch.obs, torch.float32), t(batch.act, torch.float32)
+            _on_ret_rms(self, eng)                       # (the return statistics move here already, not only after the update)
             return batch
 
         def _update_with_batch(self, batch, batch_size, repeat):
@@ -1110,11 +1050,7 @@ def make_hip_reinforce(ref=None):
             perms = [np.random.permutation(len(batch)) for _ in range(repeat)]     # Batch.split, batch.py:1209
             losses, _ = eng.update(self._hip_obs, self._hip_act, batch.returns, batch_size, repeat, perms)
             arr = losses.cpu().numpy().astype(np.float64).reshape(-1)              # one D2H per update()
-            aparams = params_by_keys(self.policy.actor, self._hip_keys)
-            with torch.no_grad():
-                for p, t in zip(aparams, self._from_flat(eng.actor)):
-                    p.copy_(t.reshape(p.shape).to(p.device))
-            store_adam_state(self.optim._optim, aparams, self._from_flat(eng.adam_m), self._from_flat(eng.adam_v), eng.adam_step)
+            self._hip_write_back()
             return LossSequenceTrainingStats(loss=SequenceSummaryStats.from_sequence(arr))
 
     return HipReinforce
@@ -1375,6 +1311,84 @@ def _ac_write_back(algo) -> None:
             step = getattr(eng, parts[0].step)
             if step:
                 store_adam_state(algo.alpha._optim, [algo.alpha._log_alpha], [eng.log_alpha_m[0]], [eng.log_alpha_v[0]], step)
+
+
+# -- what the on-policy classes (HipPPO / HipA2C, HipNPG / HipTRPO, HipReinforce, HipPPOCnn / HipA2CCnn, HipPPODiscrete / HipA2CDiscrete)
+# share: the same two paths over one `_OnPart` per flat engine vector (`_on_load`, `_on_write_back`), the statistics, the host preamble --
+class _OnPart(NamedTuple):
+    """How one flat engine vector `eng.<name>` and its two optimizer-state vectors map to torch parameters.  Every class body
+    builds its parts in `_hip_parts(eng)`, per call (the converters are looked up in their engine module when they are used) and
+    closes them over its dims; `eng` is None before the engine exists, when only `flat()` is asked for."""
+    name: str             # the engine attribute that holds the parameters: "params", "actor" or "critic"
+    moments: tuple | None  # the engine attributes of the two moment vectors; None: no optimizer (the NPG / TRPO actor)
+    optim: object         # the Algorithm.Optimizer wrapper of `params` (None with `moments`)
+    params: list          # the torch parameters in converter order; one part may span modules (PPO: the actor's, then the critic's)
+    from_torch: Callable  # tensors in `params` order (parameters or moments) -> flat
+    to_torch: Callable    # flat -> tensors in `params` order
+
+    def flat(self) -> torch.Tensor:
+        """The parameters as the flat vector an engine is constructed from."""
+        return self.from_torch([p.detach() for p in self.params])
+
+
+def _on_ret_rms(algo, eng=None):
+    """The running return statistics' holder: the algorithm's own (a2c.py, npg.py) or REINFORCE's return computation
+    (reinforce.py:249-271); with `eng`, the engine's three scalars are first stored there."""
+    rms = getattr(algo, "discounted_return_computation", algo).ret_rms
+    if eng is not None:
+        rms.mean, rms.var, rms.count = eng.ret_rms
+    return rms
+
+
+def _on_load(algo, eng):
+    """Torch state -> a fresh engine (built from every part's `flat()`): optimizer moments and step count (resume from a
+    checkpoint, algorithm_base.py:523-543), return statistics.  The inverse of `_on_write_back`.  -> eng"""
+    for part in algo._hip_parts(eng):
+        if part.moments is not None:
+            ms, vs, eng.adam_step = adam_state(part.optim._optim, part.params)
+            setattr(eng, part.moments[0], part.from_torch(ms))
+            setattr(eng, part.moments[1], part.from_torch(vs))
+    rms = _on_ret_rms(algo)
+    eng.ret_rms = [float(rms.mean), float(rms.var), float(rms.count)]
+    return eng
+
+
+def _on_write_back(algo, params: bool = True, optimizer: bool = True) -> None:
+    """`_hip_write_back` of the on-policy classes.  `params`: engine parameters -> the torch modules, every parameter through
+    `_hip_put` (which leaves out what somebody else has written; device-to-device when the modules live on the GPU), and the three
+    return statistics.  `optimizer`: moments and step count -> torch.optim (HipPPO defers them to `_hip_flush`)."""
+    eng = algo.__dict__.get("_hip_engine_obj")
+    if eng is None:
+        return
+    with torch.no_grad():
+        for part in algo._hip_parts(eng):
+            if params:
+                for p, t in zip(part.params, part.to_torch(getattr(eng, part.name))):
+                    algo._hip_put(p, t)
+            if optimizer and part.moments is not None:
+                m, v = (part.to_torch(getattr(eng, name)) for name in part.moments)
+                store_adam_state(part.optim._optim, part.params, m, v, eng.adam_step)
+    if params:
+        _on_ret_rms(algo, eng)
+
+
+def _a2c_stats(Stats, seq, losses, steps):
+    """[steps, 4+] per-step (loss, actor loss, value loss, entropy loss) on the device -> A2CTrainingStats; one D2H per update()."""
+    arr = losses.cpu().numpy().astype(np.float64)
+    return Stats(loss=seq(arr[:, 0]), actor_loss=seq(arr[:, 1]), vf_loss=seq(arr[:, 2]), ent_loss=seq(arr[:, 3]), gradient_steps=steps)
+
+
+def _on_host_batch(algo, who: str, buffer, indices):
+    """`_preprocess_batch` of the classes that read the host batch (HipNPG / HipTRPO, HipReinforce): -> (engine, host array ->
+    device tensor[, cast], the positions in `indices` of the unfinished slots (algorithm_base.py:715) on the device)."""
+    _require_gpu(algo._hip_device, who)
+    eng, dev = algo._engine(), algo._hip_device
+
+    def t(x, dt=None):
+        x = torch.as_tensor(np.ascontiguousarray(x), device=dev)
+        return x if dt is None else x.to(dt)
+
+    return eng, t, t(np.nonzero(np.isin(indices, buffer.unfinished_index()))[0])
 
 
 def _dqn_config(algo):
@@ -2574,18 +2588,21 @@ def make_hip_ppo_cnn(algo: str = "ppo", ref=None):
                 raise NotImplementedError("HipPPOCnn: observations must be [c, h, w]")
             return obs.shape[1], obs.shape[2], obs.shape[3], 1
 
+        def _hip_parts(self, eng=None, frame=None):
+            """`frame`: (c, h, w) of the buffer's observations, before the engine exists."""
+            params, dev = self._hip_params(), self._hip_device
+            dims = (*(frame or (eng.c, eng.h, eng.w)), params[8].shape[0])
+            return [_OnPart("params", ("adam_m", "adam_v"), self.optim, params,
+                            lambda t: PC.flat_from_torch(t, *dims, dev), lambda f: PC.flat_to_torch(f, *dims))]
+
         def _engine(self, c, h, w):
             if self._hip_engine is None:
-                params = self._hip_params()
-                n_act = params[8].shape[0]
-                dev = self._hip_device
-                eng = self._hip_engine = PC.CnnPPOEngine(c, h, w, n_act, PC.flat_from_torch(params, c, h, w, n_act, dev),
-                                                         ppo_config_from(self))
-                eng.ret_rms = [float(self.ret_rms.mean), float(self.ret_rms.var), float(self.ret_rms.count)]
-                ms, vs, step = adam_state(self.optim._optim, params)
-                eng.adam_m, eng.adam_v = PC.flat_from_torch(ms, c, h, w, n_act, dev), PC.flat_from_torch(vs, c, h, w, n_act, dev)
-                eng.adam_step = step
+                part, = self._hip_parts(frame=(c, h, w))
+                eng = PC.CnnPPOEngine(c, h, w, part.params[8].shape[0], part.flat(), ppo_config_from(self))
+                self._hip_engine = _on_load(self, eng)
             return self._hip_engine
+
+        _hip_write_back = _on_write_back
 
         def _preprocess_batch(self, batch, buffer, indices):
             _require_gpu(self._hip_device, "HipPPOCnn")
@@ -2602,19 +2619,8 @@ def make_hip_ppo_cnn(algo: str = "ppo", ref=None):
             eng, m = self._hip_engine, self._hip_mirror
             perms = [np.random.permutation(len(batch)) for _ in range(repeat)]     # Batch.split, batch.py:1209
             losses, steps = eng.update(m, m.obs, self._hip_pre, self._hip_stack, batch_size, repeat, perms)
-            arr = losses.cpu().numpy().astype(np.float64)
-            params = self._hip_params()
-            dims = (eng.c, eng.h, eng.w, eng.n_act)
-            with torch.no_grad():
-                for p, t in zip(params, PC.flat_to_torch(eng.params, *dims)):
-                    p.copy_(t)
-            store_adam_state(self.optim._optim, params, PC.flat_to_torch(eng.adam_m, *dims),
-                             PC.flat_to_torch(eng.adam_v, *dims), eng.adam_step)
-            self.ret_rms.mean, self.ret_rms.var, self.ret_rms.count = eng.ret_rms
-            return A2CTrainingStats(
-                loss=SequenceSummaryStats.from_sequence(arr[:, 0]), actor_loss=SequenceSummaryStats.from_sequence(arr[:, 1]),
-                vf_loss=SequenceSummaryStats.from_sequence(arr[:, 2]), ent_loss=SequenceSummaryStats.from_sequence(arr[:, 3]),
-                gradient_steps=steps)
+            self._hip_write_back()
+            return _a2c_stats(A2CTrainingStats, SequenceSummaryStats.from_sequence, losses, steps)
 
     if algo == "a2c":
         HipPPOCnn.__name__ = HipPPOCnn.__qualname__ = "HipA2CCnn"
@@ -2665,18 +2671,21 @@ def make_hip_ppo_discrete(algo: str = "ppo", ref=None):
         def _hip_params(self):
             return params_by_keys(self.policy.actor, PD.TRUNK_KEYS + PD.HEAD_KEYS) + params_by_keys(self.critic, PD.HEAD_KEYS)
 
+        def _hip_parts(self, eng=None):
+            params, dev = self._hip_params(), self._hip_device
+            hidden, obs_dim = params[0].shape
+            dims = (obs_dim, hidden, params[4].shape[0])
+            return [_OnPart("params", ("adam_m", "adam_v"), self.optim, params,
+                            lambda t: PD.flat_from_torch(t, *dims, dev), lambda f: PD.flat_to_torch(f, *dims))]
+
         def _engine(self):
             if self._hip_engine is None:
-                params = self._hip_params()
-                hidden, obs_dim = params[0].shape
-                dims, dev = (obs_dim, hidden, params[4].shape[0]), self._hip_device
-                eng = self._hip_engine = PD.DiscretePPOEngine(*dims, PD.flat_from_torch(params, *dims, dev),
-                                                              ppo_config_from(self))
-                eng.ret_rms = [float(self.ret_rms.mean), float(self.ret_rms.var), float(self.ret_rms.count)]
-                ms, vs, step = adam_state(self.optim._optim, params)
-                eng.adam_m, eng.adam_v = PD.flat_from_torch(ms, *dims, dev), PD.flat_from_torch(vs, *dims, dev)
-                eng.adam_step = step
+                part, = self._hip_parts()
+                (hidden, obs_dim), n_act = part.params[0].shape, part.params[4].shape[0]
+                self._hip_engine = _on_load(self, PD.DiscretePPOEngine(obs_dim, hidden, n_act, part.flat(), ppo_config_from(self)))
             return self._hip_engine
+
+        _hip_write_back = _on_write_back
 
         def _preprocess_batch(self, batch, buffer, indices):
             _require_gpu(self._hip_device, "HipPPODiscrete")
@@ -2691,19 +2700,8 @@ def make_hip_ppo_discrete(algo: str = "ppo", ref=None):
             eng, m = self._hip_engine, self._hip_mirror
             perms = [np.random.permutation(len(batch)) for _ in range(repeat)]     # Batch.split, batch.py:1209
             losses, steps = eng.update(m, self._hip_pre, batch_size, repeat, perms)
-            arr = losses.cpu().numpy().astype(np.float64)
-            params = self._hip_params()
-            dims = (eng.obs_dim, eng.hidden, eng.n_act)
-            with torch.no_grad():
-                for p, t in zip(params, PD.flat_to_torch(eng.params, *dims)):
-                    p.copy_(t)
-            store_adam_state(self.optim._optim, params, PD.flat_to_torch(eng.adam_m, *dims),
-                             PD.flat_to_torch(eng.adam_v, *dims), eng.adam_step)
-            self.ret_rms.mean, self.ret_rms.var, self.ret_rms.count = eng.ret_rms
-            return A2CTrainingStats(
-                loss=SequenceSummaryStats.from_sequence(arr[:, 0]), actor_loss=SequenceSummaryStats.from_sequence(arr[:, 1]),
-                vf_loss=SequenceSummaryStats.from_sequence(arr[:, 2]), ent_loss=SequenceSummaryStats.from_sequence(arr[:, 3]),
-                gradient_steps=steps)
+            self._hip_write_back()
+            return _a2c_stats(A2CTrainingStats, SequenceSummaryStats.from_sequence, losses, steps)
 
     if algo == "a2c":
         HipPPODiscrete.__name__ = HipPPODiscrete.__qualname__ = "HipA2CDiscrete"
