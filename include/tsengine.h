@@ -1413,6 +1413,39 @@ int ts_npg_net_critic_steps(ts_workspace* ws, float* critic, float* adam_m, floa
                             const float* obs, const float* returns, int64_t B, int64_t iters, double lr, double beta1, double beta2,
                             double adam_eps, double max_grad_norm, float* loss_out, float* grad_out, ts_stream_t stream);
 
+/* ---- GAIL (imitation/gail.py:188-250, arXiv 1606.03476): the discriminator half of an update; the PPO half is ts_ppo_* -------
+ * The discriminator is described by a ts_net_desc whose obs_dim is obs_dim + act_dim (the network sees concat(obs, act),
+ * gail.py:205, 227-228), flat critic layout of ts_net_layout (its first h_out3[2] entries); head column 0 is the logit l.
+ * Layer-norm trunks: TS_ERR_UNSUPPORTED.  All arithmetic float32; softplus(z) = max(z, 0) + log1p(exp(-|z|)).
+ * `route`: 0 = automatic, 1 = layer by layer on the GEMM kernels, 2 = the one-launch kernel of the NPG critic with the logistic
+ * loss (Net[64, 64] tanh on obs_dim + act_dim <= 32 inputs; anywhere else route 2 is TS_ERR_UNSUPPORTED and route 0 takes 1).
+ *
+ * ts_gail_loss: the loss kernel alone.  logits float32[n_pi + n_exp], policy rows first.  d_logit_out[b] = sigmoid(l) / n_pi
+ * (policy) resp. -sigmoid(-l) / n_exp (expert); stats_out3 = {mean softplus(l_pi) + mean softplus(-l_exp), mean(l_pi < 0),
+ * mean(l_exp > 0)} (gail.py:229-235; the inequalities are strict, so a logit of +0 or -0 counts for neither accuracy). */
+int ts_gail_loss(ts_workspace* ws, const float* logits, int64_t n_pi, int64_t n_exp, float* d_logit_out, float* stats_out3,
+                 ts_stream_t stream);
+/* rew_out[b] = -logsigmoid(-D(obs_b, act_b)) = softplus(l_b) (gail.py:203-206), obs float32[B, net->obs_dim - act_dim], act
+ * float32[B, act_dim]; logits_out (nullable) float32[B]. */
+int ts_gail_reward(ts_workspace* ws, const float* disc, const ts_net_desc* net, int64_t act_dim, const float* obs, const float* act,
+                   int64_t B, float* rew_out, float* logits_out, int32_t route, ts_stream_t stream);
+/* All discriminator steps of one update (gail.py:207-244) without a host synchronisation, copy or allocation:
+ * steps = N / bsz; step k < steps - 1 takes the policy rows perm[k bsz : (k + 1) bsz] of obs / act ([N, .]), the last step
+ * perm[k bsz : N] (Batch.split(bsz, merge_last=True), batch.py:1199-1215); every step takes the bsz expert rows
+ * exp_index[k bsz : (k + 1) bsz] of obs_exp / act_exp ([n_exp_rows, .]).  perm int64[N], exp_index int64[steps bsz]; entries
+ * outside their arrays are clamped into them.  Step k is optimizer step optim_step0 + k (1-based) of `optim_kind` with the
+ * hyper-parameters of ts_optim_step, after clip_grad_norm_(max_grad_norm) (<= 0: none).  stats_out float32[steps, 3] =
+ * ts_gail_loss's statistics per step (before that step's update).  grad_out (nullable) receives the last step's gradient,
+ * padding entries zero; lr < 0: gradients and statistics only.
+ * TS_ERR_INVALID_ARG before any launch: a NULL pointer (grad_out excepted), bsz < 1, N < bsz, n_exp_rows < 1,
+ * optim_step0 < 1, act_dim outside [1, net->obs_dim), route outside 0 .. 2. */
+int ts_gail_disc_steps(ts_workspace* ws, float* disc, float* state_m, float* state_v, int64_t optim_step0, const ts_net_desc* net,
+                       int64_t act_dim, const float* obs, const float* act, const int64_t* perm, int64_t N, const float* obs_exp,
+                       const float* act_exp, int64_t n_exp_rows, const int64_t* exp_index, int64_t bsz, int32_t optim_kind, double lr,
+                       double beta1, double beta2, double eps, double weight_decay, double rms_alpha, double rms_momentum,
+                       int32_t rms_centered, double max_grad_norm, int32_t route, float* stats_out, float* grad_out,
+                       ts_stream_t stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * TD3 / DDPG: ContinuousActorDeterministic (utils/net/continuous.py:26-85) + the SAC critics,

@@ -44,6 +44,10 @@ int npg_infer_fused(hipStream_t s, ts_workspace* ws, const float* theta, const f
                     int act, int64_t B, float* head_out, int head_stride, float* logp_out);
 int npg_critic_grad_fused(hipStream_t s, ts_workspace* ws, const float* critic, const float* x, const float* returns, int obs,
                           int k0, int64_t B, float* slabs, float* grad, float* loss_out);
+// ts_ppo.hip / ts_npg_q.h, GAIL pass: one discriminator step's gradient and statistics in one launch + two small sums
+size_t gail_fused_slab_floats(int64_t in_dim, int64_t rows);
+int gail_grad_fused(hipStream_t s, ts_workspace* ws, const float* disc, const float* x, int in_dim, int k0, int64_t n_pi,
+                    int64_t n_exp, float* slabs, float* grad, float* loss_scratch, float* stats3);
 int npg_eval_fused(hipStream_t s, ts_workspace* ws, const float* theta_old, const float* cands, int64_t cand_stride, int n_cand,
                    const float* x, const float* actions, const float* adv, const float* logp_old, const float* mu, int obs, int k0,
                    int act, int64_t B, float* partial, float* res, float* apply_theta = nullptr, float* apply_stats3 = nullptr);
@@ -1584,6 +1588,244 @@ int ts_npg_net_critic_steps(ts_workspace* ws, float* critic, float* adam_m, floa
         if (int rc = backward_l(s, ws, n, critic, x, a, d_head, grad, dha, dhb, slabs, B)) return rc;
         if (lr < 0.0) continue;
         if (int rc = ts::adam_step(s, critic, adam_m, adam_v, grad, P, adam_step + it, lr, beta1, beta2, adam_eps, max_grad_norm, norm_part))
+            return rc;
+    }
+    return TS_OK;
+}
+
+}  // extern "C"
+
+// ---- GAIL (imitation/gail.py:188-250): the discriminator half of an update on the critic's network code ---------------------
+// The discriminator is a critic on [obs | act] whose head column 0 is the logit l.  Per step (gail.py:208-235): pack the policy
+// and the expert rows into one input matrix, forward, the logistic loss -logsigmoid(-l_pi).mean() - logsigmoid(l_exp).mean()
+// with its per-row gradient, reverse pass, clip + optimizer step.  softplus(z) = max(z, 0) + log1p(exp(-|z|)) (torch's stable
+// form); its derivative as log_sigmoid_backward forms it: q = e / (1 + e), e = exp(-|z|); z > 0: 1 - q, else q.
+namespace {
+
+// x[r, :] = [obs | act] of row perm[r] (perm == NULL: row r) for r < n_pi, of expert row eidx[r - n_pi] behind them, zero-padded
+// to k0 columns.  Row numbers outside their arrays are clamped into them (an index list is the caller's; no read leaves the arrays).
+__global__ __launch_bounds__(256) void gail_pack_kernel(const float* __restrict__ obs, const float* __restrict__ act,
+                                                        const int64_t* __restrict__ perm, int64_t n_rows_pi, int64_t n_pi,
+                                                        const float* __restrict__ obs_e, const float* __restrict__ act_e,
+                                                        const int64_t* __restrict__ eidx, int64_t n_rows_e, int64_t n_exp, int od,
+                                                        int ad, int k0, float* __restrict__ x) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (n_pi + n_exp) * k0) return;
+    const int64_t r = i / k0;
+    const int j = (int)(i - r * k0);
+    const bool pol = r < n_pi;
+    int64_t src = pol ? (perm ? perm[r] : r) : eidx[r - n_pi];
+    const int64_t lim = pol ? n_rows_pi : n_rows_e;
+    src = src < 0 ? 0 : (src >= lim ? lim - 1 : src);
+    const float* o = pol ? obs : obs_e;
+    const float* a = pol ? act : act_e;
+    x[i] = j < od ? o[src * od + j] : (j < od + ad ? a[src * ad + (j - od)] : 0.f);
+}
+
+// rows [0, n_pi) policy, [n_pi, n_pi + n_exp) expert; logit of row b at logits[b * ls].  d[b * ds] = sigmoid(l) / n_pi resp.
+// -sigmoid(-l) / n_exp (ds == HEAD: the rest of the head row is zeroed); partial[block] = {sum softplus(l_pi), sum softplus(-l_exp),
+// #(l_pi < 0), #(l_exp > 0)} of the workgroup's rows.
+__global__ __launch_bounds__(256) void gail_loss_kernel(const float* __restrict__ logits, int ls, int64_t n_pi, int64_t n_exp,
+                                                        float* __restrict__ d, int ds, float* __restrict__ partial) {
+    using f32x4 = __attribute__((ext_vector_type(4))) float;
+    __shared__ float red4[4];
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool pol = b < n_pi;
+    float lp = 0.f, le = 0.f, cp = 0.f, ce = 0.f;
+    if (b < n_pi + n_exp) {
+        const float l = logits[b * ls];
+        const float z = pol ? l : -l;
+        const float e = expf(-fabsf(z)), q = e / (1.f + e);
+        const float sg = z > 0.f ? 1.f - q : q;
+        const float sp = fmaxf(z, 0.f) + log1pf(e);
+        const float u = pol ? sg * (1.f / (float)n_pi) : -sg * (1.f / (float)n_exp);
+        if (pol) { lp = sp; cp = l < 0.f ? 1.f : 0.f; }
+        else { le = sp; ce = l > 0.f ? 1.f : 0.f; }
+        if (ds == HEAD) {
+            f32x4* row = reinterpret_cast<f32x4*>(d + b * HEAD);
+            row[0] = f32x4{u, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 1; j < HEAD / 4; ++j) row[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        } else {
+            d[b * ds] = u;
+        }
+    }
+    const float t0 = block_sum256(lp, red4);
+    __syncthreads();
+    const float t1 = block_sum256(le, red4);
+    __syncthreads();
+    const float t2 = block_sum256(cp, red4);
+    __syncthreads();
+    const float t3 = block_sum256(ce, red4);
+    if (threadIdx.x == 0) {
+        partial[4 * blockIdx.x] = t0; partial[4 * blockIdx.x + 1] = t1;
+        partial[4 * blockIdx.x + 2] = t2; partial[4 * blockIdx.x + 3] = t3;
+    }
+}
+
+// stats3 = {mean softplus(l_pi) + mean softplus(-l_exp), mean(l_pi < 0), mean(l_exp > 0)} (gail.py:229-235), fixed order
+__global__ __launch_bounds__(256) void gail_loss_finish_kernel(const float* __restrict__ partial, int n_blocks, float n_pi,
+                                                               float n_exp, float* __restrict__ stats3) {
+    __shared__ float red4[4];
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int i = threadIdx.x; i < n_blocks; i += 256) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] += partial[4 * i + k];
+    }
+    float t[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        t[k] = block_sum256(v[k], red4);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        stats3[0] = t[0] / n_pi + t[1] / n_exp;
+        stats3[1] = t[2] / n_pi;
+        stats3[2] = t[3] / n_exp;
+    }
+}
+
+// rew = -logsigmoid(-D(s, a)) = softplus(logit) (gail.py:205), float32
+__global__ __launch_bounds__(256) void gail_reward_kernel(const float* __restrict__ logits, int ls, int64_t B, float* __restrict__ rew,
+                                                          float* __restrict__ logits_out) {
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const float l = logits[b * ls];
+    rew[b] = fmaxf(l, 0.f) + log1pf(expf(-fabsf(l)));
+    if (logits_out) logits_out[b] = l;
+}
+
+// the one-launch kernel's shape: Net[64, 64] tanh on at most 32 inputs (ts_npg_q.h)
+bool gail_fused_shape(const ts_net_desc* d) {
+    return d->n_hidden == 2 && d->hidden[0] == 64 && d->hidden[1] == 64 && d->activation == TS_NET_ACT_TANH && d->obs_dim >= 1 &&
+           d->obs_dim <= 32 && !(d->flags & TS_NET_LAYERNORM);
+}
+
+// Which route the automatic choice takes at the one-launch kernel's shape (measured: profiles/gail_bench.json)
+constexpr int GAIL_AUTO_ROUTE = 2;
+
+}  // namespace
+
+extern "C" {
+
+int ts_gail_loss(ts_workspace* ws, const float* logits, int64_t n_pi, int64_t n_exp, float* d_logit_out, float* stats_out3,
+                 ts_stream_t stream) {
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_gail_loss: workspace is NULL");
+    TS_REQUIRE(logits && d_logit_out && stats_out3 && n_pi >= 1 && n_exp >= 1 && n_pi + n_exp <= (int64_t)1 << 30, TS_ERR_INVALID_ARG,
+               "ts_gail_loss: bad argument");
+    const int64_t rows = n_pi + n_exp;
+    const int n_blocks = (int)ts::ceil_div(rows, 256);
+    if (int rc = ts::ws_reserve(ws, al(16 * (size_t)n_blocks) + 4096)) return rc;
+    float* partial = static_cast<float*>(ws->base);
+    hipStream_t s = ts::as_stream(stream);
+    hipLaunchKernelGGL(gail_loss_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, logits, 1, n_pi, n_exp, d_logit_out, 1, partial);
+    hipLaunchKernelGGL(gail_loss_finish_kernel, dim3(1), dim3(256), 0, s, partial, n_blocks, (float)n_pi, (float)n_exp, stats_out3);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+int ts_gail_reward(ts_workspace* ws, const float* disc, const ts_net_desc* net, int64_t act_dim, const float* obs, const float* act,
+                   int64_t B, float* rew_out, float* logits_out, int32_t route, ts_stream_t stream) {
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_gail_reward: workspace is NULL");
+    TS_REQUIRE(disc && net && obs && act && rew_out && B >= 1 && B <= (int64_t)1 << 30 && act_dim >= 1 && act_dim < net->obs_dim &&
+                   route >= 0 && route <= 2, TS_ERR_INVALID_ARG, "ts_gail_reward: bad argument");
+    TS_REQUIRE(!(net->flags & TS_NET_LAYERNORM), TS_ERR_UNSUPPORTED, "ts_gail_reward: layer-norm discriminators are not supported");
+    NetL n;
+    if (int rc = make_netl((int)B, net, &n)) return rc;
+    const bool fits = gail_fused_shape(net);
+    TS_REQUIRE(route != 2 || fits, TS_ERR_UNSUPPORTED, "ts_gail_reward: route 2 needs a [64, 64] tanh trunk on at most 32 inputs");
+    const bool fused = fits && (route == 2 || (route == 0 && GAIL_AUTO_ROUTE == 2));
+    hipStream_t s = ts::as_stream(stream);
+    const int od = (int)(net->obs_dim - act_dim), ad = (int)act_dim;
+    const size_t bytes = al(4 * B * n.k0) + al(4 * B) + (fused ? 0 : actl_bytes(n, B) + al(4 * split_floats(n))) + 4096;
+    if (int rc = ts::ws_reserve(ws, bytes)) return rc;
+    Carve c{static_cast<char*>(ws->base)};
+    float* x = c.f(B * n.k0);
+    float* lg = c.f(B);
+    hipLaunchKernelGGL(gail_pack_kernel, dim3((unsigned)ts::ceil_div(B * n.k0, 256)), dim3(256), 0, s, obs, act, (const int64_t*)nullptr,
+                       B, B, (const float*)nullptr, (const float*)nullptr, (const int64_t*)nullptr, (int64_t)0, (int64_t)0, od, ad, n.k0, x);
+    TS_LAUNCH_CHECK();
+    const unsigned gb = (unsigned)ts::ceil_div(B, 256);
+    if (fused) {
+        if (int rc = ts::npg_infer_fused(s, ws, disc, x, nullptr, n.obs, n.k0, 1, B, lg, 1, nullptr)) return rc;
+        hipLaunchKernelGGL(gail_reward_kernel, dim3(gb), dim3(256), 0, s, lg, 1, B, rew_out, logits_out);
+    } else {
+        const ActL a = take_actl(c, n, B);
+        float* split = c.f(split_floats(n));
+        if (int rc = forward_l(s, ws, n, disc, x, a, split, B)) return rc;
+        hipLaunchKernelGGL(gail_reward_kernel, dim3(gb), dim3(256), 0, s, a.h[n.L - 1], HEAD, B, rew_out, logits_out);
+    }
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+int ts_gail_disc_steps(ts_workspace* ws, float* disc, float* state_m, float* state_v, int64_t optim_step0, const ts_net_desc* net,
+                       int64_t act_dim, const float* obs, const float* act, const int64_t* perm, int64_t N, const float* obs_exp,
+                       const float* act_exp, int64_t n_exp_rows, const int64_t* exp_index, int64_t bsz, int32_t optim_kind, double lr,
+                       double beta1, double beta2, double eps, double weight_decay, double rms_alpha, double rms_momentum,
+                       int32_t rms_centered, double max_grad_norm, int32_t route, float* stats_out, float* grad_out,
+                       ts_stream_t stream) {
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_gail_disc_steps: workspace is NULL");
+    TS_REQUIRE(disc && state_m && state_v && net && obs && act && perm && obs_exp && act_exp && exp_index && stats_out,
+               TS_ERR_INVALID_ARG, "ts_gail_disc_steps: NULL argument");
+    TS_REQUIRE(bsz >= 1 && N >= bsz && N <= (int64_t)1 << 30 && n_exp_rows >= 1 && optim_step0 >= 1 && act_dim >= 1 &&
+                   act_dim < net->obs_dim && route >= 0 && route <= 2, TS_ERR_INVALID_ARG,
+               "ts_gail_disc_steps: bsz >= 1, N >= bsz, n_exp_rows >= 1, optim_step0 >= 1, 1 <= act_dim < net->obs_dim, route in 0 .. 2");
+    TS_REQUIRE(!(net->flags & TS_NET_LAYERNORM), TS_ERR_UNSUPPORTED, "ts_gail_disc_steps: layer-norm discriminators are not supported");
+    const int64_t steps = N / bsz;                       // Batch.split(bsz, merge_last=True): the last chunk takes the remainder
+    const int64_t max_rows = (N - (steps - 1) * bsz) + bsz;
+    NetL n, n_even;                                      // (the layer geometry carries the row count: the last step's and the others')
+    if (int rc = make_netl((int)max_rows, net, &n)) return rc;
+    if (int rc = make_netl((int)(2 * bsz), net, &n_even)) return rc;
+    const bool fits = gail_fused_shape(net);
+    TS_REQUIRE(route != 2 || fits, TS_ERR_UNSUPPORTED, "ts_gail_disc_steps: route 2 needs a [64, 64] tanh trunk on at most 32 inputs");
+    const bool fused = fits && (route == 2 || (route == 0 && GAIL_AUTO_ROUTE == 2));
+    hipStream_t s = ts::as_stream(stream);
+    const int64_t P = n.off[n.L];
+    const int od = (int)(net->obs_dim - act_dim), ad = (int)act_dim;
+    const int max_blocks = (int)ts::ceil_div(max_rows, 256);
+    const size_t slab_fl = fused ? ts::gail_fused_slab_floats(n.obs, max_rows) : std::max(slab_floats(n), slab_floats(n_even));
+    const size_t sp = fused ? 4 : std::max(split_floats(n), split_floats(n_even));
+    const size_t bytes = al(4 * max_rows * n.k0) + al(4 * slab_fl) + al(4 * P) + al(4 * 1024) + al(16 * (size_t)max_blocks) + 8192 +
+                         (fused ? 0 : actl_bytes(n, max_rows) + al(4 * max_rows * HEAD) + 2 * al(4 * max_rows * n.wmax) + al(4 * sp));
+    if (int rc = ts::ws_reserve(ws, bytes)) return rc;
+    Carve c{static_cast<char*>(ws->base)};
+    float* x = c.f(max_rows * n.k0);
+    float* slabs = c.f(slab_fl);
+    float* grad = c.f(P);
+    float* norm_part = c.f(1024);
+    float* lpart = c.f(4 * (size_t)max_blocks);
+    ActL a{};
+    float *d_head = nullptr, *dha = nullptr, *dhb = nullptr, *split = nullptr;
+    if (!fused) {
+        a = take_actl(c, n, max_rows);
+        d_head = c.f(max_rows * HEAD);
+        dha = c.f(max_rows * n.wmax); dhb = c.f(max_rows * n.wmax);
+        split = c.f(sp);
+    }
+    if (grad_out) grad = grad_out;
+    ts::OptimDesc o;
+    o.kind = optim_kind; o.centered = rms_centered; o.weight_decay = weight_decay; o.alpha = rms_alpha; o.momentum = rms_momentum;
+    for (int64_t k = 0; k < steps; ++k) {
+        const int64_t n_pi = k + 1 < steps ? bsz : N - k * bsz, rows = n_pi + bsz;
+        hipLaunchKernelGGL(gail_pack_kernel, dim3((unsigned)ts::ceil_div(rows * n.k0, 256)), dim3(256), 0, s, obs, act, perm + k * bsz, N,
+                           n_pi, obs_exp, act_exp, exp_index + k * bsz, n_exp_rows, bsz, od, ad, n.k0, x);
+        TS_LAUNCH_CHECK();
+        if (fused) {
+            if (int rc = ts::gail_grad_fused(s, ws, disc, x, n.obs, n.k0, n_pi, bsz, slabs, grad, lpart, stats_out + 3 * k)) return rc;
+        } else {
+            const NetL& nk = k + 1 < steps ? n_even : n;
+            const int n_blocks = (int)ts::ceil_div(rows, 256);
+            if (int rc = forward_l(s, ws, nk, disc, x, a, split, rows)) return rc;
+            hipLaunchKernelGGL(gail_loss_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, a.h[nk.L - 1], HEAD, n_pi, bsz, d_head, HEAD,
+                               lpart);
+            hipLaunchKernelGGL(gail_loss_finish_kernel, dim3(1), dim3(256), 0, s, lpart, n_blocks, (float)n_pi, (float)bsz,
+                               stats_out + 3 * k);
+            TS_LAUNCH_CHECK();
+            if (int rc = backward_l(s, ws, nk, disc, x, a, d_head, grad, dha, dhb, slabs, rows)) return rc;
+        }
+        if (lr < 0.0) continue;
+        if (int rc = ts::optim_step(s, o, disc, state_m, state_v, grad, P, optim_step0 + k, lr, beta1, beta2, eps, max_grad_norm, norm_part))
             return rc;
     }
     return TS_OK;

@@ -13,6 +13,9 @@
 //           u = dmu / sigma^2 / B;   reverse pass with u as the head gradient                  (J^T u)
 //   CRITIC one critic iteration's gradient (npg.py:179-183: mse_loss(returns, V)): GRAD on the critic's vector, whose head
 //         has one column.
+//   GAIL  one discriminator step's gradient (imitation/gail.py:229-235): CRITIC's pass with the logistic loss
+//         mean softplus(l) over the policy rows [0, n_pi) + mean softplus(-l) over the expert rows behind them; the head's
+//         column 0 is the logit l.  Also leaves the loss and the two accuracy counts (l_pi < 0, l_exp > 0) in the slabs.
 //   INFER forward only: the head's outputs (an actor's mu, a critic's V -- the same 64-64 trunk with one head column) and
 //         log pi(a | s) per sample: the network passes of NPG._preprocess_batch (npg.py:123-138).
 //   EVAL  kl(old || candidate) and the surrogate at up to 32 candidate parameter vectors (npg.py:170-177's kl,
@@ -29,7 +32,7 @@
 
 namespace q4 {
 
-enum { NPG_FVP = 0, NPG_GRAD = 1, NPG_EVAL = 2, NPG_INFER = 3, NPG_CRITIC = 4 };
+enum { NPG_FVP = 0, NPG_GRAD = 1, NPG_EVAL = 2, NPG_INFER = 3, NPG_CRITIC = 4, NPG_GAIL = 5 };
 
 struct ActorArgs {
     const float* theta;       // parameters (EVAL: candidate c at theta + c * cand_stride)
@@ -48,6 +51,8 @@ struct ActorArgs {
     int64_t cand_stride;
     float* logp_out;          // INFER: [n_rows] log pi(actions) or NULL; mu (or NULL) receives the head's first `act` outputs
     int mu_stride;            //        per row at this stride (a critic: act = 1, stride 1 -> V)
+    int64_t n_pi;             // GAIL: rows [0, n_pi) are policy rows (weight inv_batch = 1 / n_pi), the others expert rows
+    float inv_exp;            //       (weight inv_exp = 1 / n_exp)
 };
 
 template <int MODE>
@@ -91,6 +96,7 @@ __device__ __forceinline__ void actor_run(const ActorArgs& g, float* lds) {
     using L = LdsA<MODE>;
     constexpr bool FVP = MODE == NPG_FVP, GRAD = MODE == NPG_GRAD, EVAL = MODE == NPG_EVAL, INFER = MODE == NPG_INFER;
     constexpr bool CRITIC = MODE == NPG_CRITIC;            // GRAD with the critic's loss: mse_loss(returns, V), one head column
+    constexpr bool GAIL = MODE == NPG_GAIL;                // CRITIC with the discriminator's logistic loss
     constexpr bool FWD = EVAL || INFER;                    // forward only: no reverse pass, no gradient tiles
     constexpr int NB1 = (4 * K1S + 15) / 16;
     constexpr int RW = 4 * K1S;                            // floats per observation record in LDS
@@ -176,7 +182,7 @@ __device__ __forceinline__ void actor_run(const ActorArgs& g, float* lds) {
         if (tid < 8) {
             const int a = tid;
             const bool live = a < n_act;
-            const float ls = (live && !CRITIC && (!INFER || g.actions)) ? th[o_sig + a] : 0.f;    // (a critic's vector has no log_sigma block)
+            const float ls = (live && !CRITIC && !GAIL && (!INFER || g.actions)) ? th[o_sig + a] : 0.f;    // (a critic's vector has no log_sigma block)
             const float sigma = expf(ls), var = sigma * sigma;
             if constexpr (FVP) {
                 SM[a] = live ? dv[o_bmu + a] : 0.f;                    // vbmu
@@ -232,7 +238,8 @@ __device__ __forceinline__ void actor_run(const ActorArgs& g, float* lds) {
                     int64_t row = t * 32 + 16 * b + n;
                     row = row < g.n_rows ? row : g.n_rows - 1;
                     const int a0 = gq < n_act ? gq : 0, a1 = 4 + gq < n_act ? 4 + gq : 0;
-                    if constexpr (CRITIC) {
+                    if constexpr (GAIL) {                                // (the loss needs the row number alone)
+                    } else if constexpr (CRITIC) {
                         in.adv[b] = g.adv[row];                          // the return of the sample
                     } else if constexpr (INFER) {
                         in.act0[b] = g.actions ? g.actions[row * n_act + a0] : 0.f;
@@ -369,6 +376,21 @@ __device__ __forceinline__ void actor_run(const ActorArgs& g, float* lds) {
                     u1[b] = m1 * iv1 * wgt;
                     sD0 += u0[b];
                     sD1 += u1[b];
+                } else if constexpr (GAIL) {
+                    // gail.py:229-235: -logsigmoid(-l_pi).mean() - logsigmoid(l_exp).mean() -- lane (sample, action 0) holds l.
+                    // softplus(z) = max(z, 0) + log1p(exp(-|z|)), its derivative as torch's log_sigmoid_backward forms it
+                    const bool pol = t * 32 + s < g.n_pi;
+                    const float z = pol ? m0 : -m0;
+                    const float e = expf(-fabsf(z)), q = e / (1.f + e);
+                    const float sg = z > 0.f ? 1.f - q : q;
+                    const float wr = pol ? wgt : (valid ? g.inv_exp : 0.f);
+                    const bool own = valid && gq == 0;
+                    u0[b] = a0 == 0 ? (pol ? sg : -sg) * wr : 0.f;
+                    u1[b] = 0.f;
+                    sD0 += u0[b];
+                    sL += own ? (fmaxf(z, 0.f) + log1pf(e)) * wr : 0.f;
+                    sS0 += (own && pol && m0 < 0.f) ? 1.f : 0.f;         // strict: a logit of +-0 counts for neither accuracy
+                    sS1 += (own && !pol && m0 > 0.f) ? 1.f : 0.f;
                 } else if constexpr (CRITIC) {
                     // npg.py:180: mse_loss(returns, V) -- lane (sample, action 0) holds V
                     const float td = m0 - in.adv[b];
@@ -555,7 +577,7 @@ __device__ __forceinline__ void actor_run(const ActorArgs& g, float* lds) {
             slab_st(slab + SL.hb[0] + gq, sD0);
             slab_st(slab + SL.hb[0] + 4 + gq, sD1);
         }
-        if constexpr (GRAD || CRITIC) {
+        if constexpr (GRAD || CRITIC || GAIL) {
             // every wave sees every sample: the log_sigma and loss sums come from wave 0 alone
             sS0 = row16_sum(sS0);
             sS1 = row16_sum(sS1);
@@ -586,6 +608,12 @@ template <int K1S>
 __global__ __launch_bounds__(QT, 3) void npg_critic_kernel(ActorArgs g) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     actor_run<K1S, NPG_CRITIC>(g, lds);
+}
+
+template <int K1S>
+__global__ __launch_bounds__(QT, 3) void npg_gail_kernel(ActorArgs g) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    actor_run<K1S, NPG_GAIL>(g, lds);
 }
 
 template <int K1S>
@@ -651,6 +679,20 @@ __global__ __launch_bounds__(1024) void npg_actor_reduce_kernel(const float* __r
             else if (i == P) loss_out[0] = loss_sign * (t / n_rows);
         }
     }
+}
+
+// GAIL: stats3 = {loss, mean(l_pi < 0), mean(l_exp > 0)} from the slabs' loss / count columns (fixed order: slab k on thread
+// k % 64, then the wave's lanes in a tree).  One wave per statistic.
+__global__ __launch_bounds__(192) void npg_gail_finish_kernel(const float* __restrict__ slabs, int n_slabs, int slab_w, int k1,
+                                                              float n_pi, float n_exp, float* __restrict__ stats3) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const Slab3 SL = slab3_layout(k1);
+    const int col = SL.sig + (wave == 0 ? 8 : (wave == 1 ? 0 : 4));
+    float s = 0.f;
+    for (int k = lane; k < n_slabs; k += 64) s += slabs[(int64_t)k * slab_w + col];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if (lane == 0) stats3[wave] = wave == 0 ? s : (wave == 1 ? s / n_pi : s / n_exp);
 }
 
 // res[2 c + {0, 1}] = {mean kl, -mean(ratio adv)} of candidate c from the EVAL partial sums [n_cand][n_wg][2]

@@ -1834,6 +1834,31 @@ int npg_critic_grad_fused(hipStream_t s, ts_workspace* ws, const float* critic, 
     return TS_OK;
 }
 
+// grad = d (mean softplus(l_pi) + mean softplus(-l_exp)) / d disc over x's rows [0, n_pi) (policy) and [n_pi, n_pi + n_exp)
+// (expert) -- the critic's block layout; stats3 = {loss, mean(l_pi < 0), mean(l_exp > 0)}.  loss_scratch: one float.
+size_t gail_fused_slab_floats(int64_t in_dim, int64_t rows) {
+    return (size_t)npg_grid(rows, 2, "TS_NPG_CRITIC_WGS") * (size_t)q4::actor_slab_width(q4::k1s_for((int)in_dim));
+}
+int gail_grad_fused(hipStream_t s, ts_workspace* ws, const float* disc, const float* x, int in_dim, int k0, int64_t n_pi,
+                    int64_t n_exp, float* slabs, float* grad, float* loss_scratch, float* stats3) {
+    const int k1s = q4::k1s_for(in_dim);
+    TS_REQUIRE(k1s > 0 && n_pi >= 1 && n_exp >= 1, TS_ERR_UNSUPPORTED, "gail_grad_fused: unsupported shape");
+    q4::ActorArgs g{};
+    g.theta = disc; g.x = x; g.n_rows = n_pi + n_exp; g.inv_batch = 1.f / (float)n_pi;
+    g.n_pi = n_pi; g.inv_exp = 1.f / (float)n_exp;
+    g.slabs = slabs; g.slab_w = q4::actor_slab_width(k1s);
+    g.obs = in_dim; g.act = 1; g.k0 = k0;
+    const int grid = npg_grid(g.n_rows, 2, "TS_NPG_CRITIC_WGS");
+    TS_NPG_DISPATCH(npg_gail_kernel, q4::NPG_GAIL, dim3(grid))
+    const int P = npg_param_count(k0) - 32;
+    hipLaunchKernelGGL(q4::npg_actor_reduce_kernel, dim3((unsigned)((P + 1 + 63) / 64)), dim3(1024), 0, s, slabs, grid, g.slab_w,
+                       in_dim, 1, k0, 4 * k1s, (const float*)nullptr, grad, P, 0.f, loss_scratch, 1.f, 1.f);
+    hipLaunchKernelGGL(q4::npg_gail_finish_kernel, dim3(1), dim3(192), 0, s, slabs, grid, g.slab_w, 4 * k1s, (float)n_pi,
+                       (float)n_exp, stats3);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
 // res[2 c + {0, 1}] = {mean kl(old || candidate c), -mean(ratio adv) at candidate c (logp_old != NULL)}; candidates at
 // cands + c * cand_stride; mu = the old mean per sample (npg_grad_fused).  apply_theta (NPG, n_cand == 1): the finish kernel
 // also copies the candidate over theta and writes stats3[1] = kl, stats3[2] = 0

@@ -584,13 +584,14 @@ def _attach_gauss_policy(algorithm, policy_forward: str, sampling: str, noise_se
                   ln_eps=ln_eps, **kw)
 
 
-def make_hip_ppo(algo: str = "ppo", ref=None):
+def make_hip_ppo(algo: str = "ppo", ref=None, base=None):
     """Returns the HipPPO class (imports tianshou lazily); algo="a2c": HipA2C(A2C), same networks.
-    `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    `ref`: optional namespace replacing the tianshou imports (see `_ref`).  `base`: a subclass of the reference's PPO to build
+    the same body over (make_hip_gail: GAIL)."""
     A2CTrainingStats = _ref(ref, "tianshou.algorithm.modelfree.a2c", "A2CTrainingStats")
     SequenceSummaryStats = _ref(ref, "tianshou.data", "SequenceSummaryStats")
     Batch = _ref(ref, "tianshou.data", "Batch")
-    PPO = _on_policy_base(algo, ref)
+    PPO = _on_policy_base(algo, ref) if base is None else base
 
     from . import ppo_wide as PW
 
@@ -694,20 +695,26 @@ def make_hip_ppo(algo: str = "ppo", ref=None):
                         lambda f: sum(PW.flat_to_tensors(f, obs_dim, hidden, act_dim), []))
             return [_OnPart("params", ("adam_m", "adam_v"), self.optim, params, *conv)]
 
+        def _hip_build_engine(self):
+            """A fresh engine from the torch parameters (`_engine` loads the optimizer state into it)."""
+            obs_dim, act_dim, hidden, kind = self._hip_dims
+            flat, cfg = self._hip_parts()[0].flat(), ppo_config_from(self)
+            if kind == "fused":
+                return PPOEngine(obs_dim, act_dim, flat, cfg)
+            if kind == "net":
+                ln_eps = _ln_eps_of(hidden)
+                return PW.NetPPOEngine(obs_dim, act_dim, hidden[0], hidden[1], hidden[2], flat, cfg, layer_norm=ln_eps is not None,
+                                       ln_eps=ln_eps or 1e-5, conditioned_sigma="conditioned_sigma" in hidden[3:])
+            return PW.WidePPOEngine(obs_dim, act_dim, hidden, flat, cfg)
+
         def _engine(self):
             if self._hip_engine is None:
-                obs_dim, act_dim, hidden, kind = self._hip_dims
-                flat, cfg = self._hip_parts()[0].flat(), ppo_config_from(self)
-                if kind == "fused":
-                    eng = PPOEngine(obs_dim, act_dim, flat, cfg)
-                elif kind == "net":
-                    ln_eps = _ln_eps_of(hidden)
-                    eng = PW.NetPPOEngine(obs_dim, act_dim, hidden[0], hidden[1], hidden[2], flat, cfg, layer_norm=ln_eps is not None,
-                                          ln_eps=ln_eps or 1e-5, conditioned_sigma="conditioned_sigma" in hidden[3:])
-                else:
-                    eng = PW.WidePPOEngine(obs_dim, act_dim, hidden, flat, cfg)
-                self._hip_engine = _on_load(self, eng)
+                self._hip_engine = _on_load(self, self._hip_build_engine())
             return self._hip_engine
+
+        def _hip_rewards(self, eng, obs, act, rew):
+            """The rewards the returns are computed from: the buffer's (HipGAIL: the discriminator's)."""
+            return rew
 
         def _hip_runner(self, eng):
             if not self._hip_dp_on:
@@ -779,8 +786,9 @@ def make_hip_ppo(algo: str = "ppo", ref=None):
             obs_next = take(m.obs_next) if m.obs_next is not None else m.gather_tensor(m.obs, m.next(idx))
             cut, d_n = cut_positions(m, idx)                                   # algorithm_base.py:715
             runner = self._hip_runner(eng)                                     # the engine, or its data-parallel wrapper
-            b = runner.preprocess(take(m.obs), obs_next, take(m.act), take(m.rew), take(m.terminated), take(m.truncated),
-                                  cut, d_n)
+            obs, act = take(m.obs), take(m.act)
+            b = runner.preprocess(obs, obs_next, act, self._hip_rewards(eng, obs, act, take(m.rew)), take(m.terminated),
+                                  take(m.truncated), cut, d_n)
             self._hip_batch = b
             batch.v_s, batch.returns, batch.adv = b["v_s"], b["returns"], b["adv"]
             batch.act = b["act"]
@@ -818,6 +826,146 @@ def make_hip_ppo(algo: str = "ppo", ref=None):
     if algo == "a2c":
         HipPPO.__name__ = HipPPO.__qualname__ = "HipA2C"
     return HipPPO
+
+
+# ---------------------------------------------------------------------------------------------------
+# GAIL (imitation/gail.py): HipPPO over the reference's GAIL, plus the discriminator engine (tianshou_amd/gail.py)
+# ---------------------------------------------------------------------------------------------------
+_GAIL_KEY = 0xA5A5A5A55A5A5A5A          # sub-key of (perm_seed, update counter) for the discriminator's draws
+
+
+def make_hip_gail(ref=None):
+    """Returns HipGAIL(GAIL): HipPPO's body over the reference's GAIL (gail.py:30-248) -- every keyword, engine kind and the
+    device buffer mirror are HipPPO's -- with the discriminator on the engine: `_preprocess_batch` replaces the rewards by
+    -logsigmoid(-D(obs, act)) (ts_gail_reward on the mirror's rows, float32, before the discriminator is updated);
+    `_update_with_batch` first runs all discriminator steps in one call (ts_gail_disc_steps), then HipPPO's update, and returns
+    GailTrainingStats from one read of the per-step statistics.
+    Discriminator: ContinuousCritic(preprocess_net=Net(..., concat=True)) or any Linear / tanh / ReLU chain with one output
+    (no normalisation layers), Adam or RMSprop.  The expert buffer's obs / act are copied to the device when the engine is built
+    (`hip_invalidate()` after changing the expert buffer).
+    Randomness follows `permutations=`: "host" makes the reference's draws in its order -- np.random.permutation(N) for the split,
+    `expert_buffer.sample_indices(bsz)` once per step, then the PPO permutations; "device" uses the keyed device generators with
+    sub-keys of (perm_seed, update counter) and touches neither NumPy's nor the expert buffer's generator.
+    `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    GAIL = _ref(ref, "tianshou.algorithm.imitation.gail", "GAIL")
+    GailTrainingStats = _ref(ref, "tianshou.algorithm.imitation.gail", "GailTrainingStats")
+    SequenceSummaryStats = _ref(ref, "tianshou.data", "SequenceSummaryStats")
+    HipPPO = make_hip_ppo("ppo", ref, base=GAIL)
+
+    from . import gail as GA
+    from .ppo_wide import net_flat_to_tensors
+
+    class HipGAIL(HipPPO):
+        def __init__(self, *args, data_parallel=False, disc_route="auto", **kwargs):
+            if data_parallel:
+                raise NotImplementedError("HipGAIL: data_parallel=True is not supported (the discriminator steps are not all-reduced)")
+            policy = kwargs.get("policy", args[0] if args else None)
+            space = getattr(policy, "action_space", None)
+            if space is not None and (hasattr(space, "n") or hasattr(space, "nvec")):
+                raise NotImplementedError(f"HipGAIL: continuous actions only (found a {type(space).__name__} action space; the "
+                                          "reference's cat([obs, act], dim=1) needs action vectors)")
+            super().__init__(*args, **kwargs)
+            obs_dim, act_dim = self._hip_dims[0], self._hip_dims[1]
+            # raises NotImplementedError naming what was found (layer norm, another layer class, an output size != 1)
+            self._hip_disc = GA.describe_module(self.disc_net, obs_dim + act_dim)[:2]
+            if disc_route not in GA.ROUTES:
+                raise ValueError(f"disc_route must be one of {sorted(GA.ROUTES)}")
+            self._hip_disc_route = disc_route
+            optimizer_fields(self.disc_optim._optim)                       # (raises on an optimizer the engine does not implement)
+            self._hip_gail_rew = None
+
+        # -- engine life cycle: the discriminator is a second part, owned by `eng.gail` ------------------------------------------
+        def _hip_disc_config(self):
+            of = optimizer_fields(self.disc_optim._optim)
+            return GA.GAILConfig(disc_update_num=int(self.disc_update_num), optimizer=of["optimizer"], lr=of["lr"],
+                                 betas=tuple(of.get("betas", (0.9, 0.999))), eps=of["adam_eps"], weight_decay=of["weight_decay"],
+                                 rms_alpha=of.get("rms_alpha", 0.99), rms_momentum=of.get("rms_momentum", 0.0),
+                                 rms_centered=of.get("rms_centered", False), max_grad_norm=self.disc_optim._max_grad_norm,
+                                 route=self._hip_disc_route)
+
+        def _hip_parts(self, eng=None):
+            obs_dim, act_dim = self._hip_dims[0], self._hip_dims[1]
+            hidden, _ = self._hip_disc
+            params, dev = GA.describe_module(self.disc_net, obs_dim + act_dim)[2], self._hip_device
+            return super()._hip_parts(eng) + [
+                _OnPart("disc", ("state_m", "state_v"), self.disc_optim, params,
+                        lambda t: GA.GAILDiscriminator.flat_from_tensors(t, obs_dim, act_dim, hidden, dev),
+                        lambda f: net_flat_to_tensors(f, obs_dim + act_dim, hidden, 1, False), holder="gail", step="optim_step")]
+
+        def _hip_build_engine(self):
+            eng = super()._hip_build_engine()
+            obs_dim, act_dim = self._hip_dims[0], self._hip_dims[1]
+            hidden, activation = self._hip_disc
+            eb = self.expert_buffer
+            eng.gail = GA.GAILDiscriminator(obs_dim, act_dim, hidden, activation, self._hip_parts()[-1].flat(),
+                                            np.asarray(eb.obs, dtype=np.float32), np.asarray(eb.act, dtype=np.float32),
+                                            self._hip_disc_config())
+            return eng
+
+        def _hip_refresh_lr(self) -> None:
+            super()._hip_refresh_lr()
+            eng = self._hip_engine
+            if eng is not None:
+                opt = self.disc_optim._optim
+                lr = float(opt.param_groups[0]["lr"])
+                if any(float(g["lr"]) != lr for g in opt.param_groups):
+                    raise NotImplementedError("the HIP engines take one learning rate per optimizer")
+                eng.gail.cfg.lr = lr
+                eng.gail.cfg.disc_update_num = int(self.disc_update_num)
+                opt._opt_called = True
+
+        def _hip_expert_layout(self, dev):
+            """(offset, lengths) of the expert buffer's sub-buffers on the device, for the seeded index sampler."""
+            eb = self.expert_buffer
+            if hasattr(eb, "_lengths"):
+                off, ln = np.asarray(eb._offset, np.int64), np.asarray(eb._lengths, np.int64)
+            else:
+                off, ln = np.zeros(1, np.int64), np.asarray([len(eb)], np.int64)
+            return torch.as_tensor(off, device=dev), torch.as_tensor(ln, device=dev)
+
+        # -- hooks ----------------------------------------------------------------------------------------------------------------
+        def _hip_rewards(self, eng, obs, act, rew):
+            """gail.py:203-206, with the parameters the discriminator has BEFORE this update's steps."""
+            self._hip_gail_rew = eng.gail.reward(obs, act)
+            return self._hip_gail_rew
+
+        def _preprocess_batch(self, batch, buffer, indices):
+            batch = super()._preprocess_batch(batch, buffer, indices)
+            batch.rew = self._hip_gail_rew
+            return batch
+
+        def _update_with_batch(self, batch, batch_size, repeat):
+            self._hip_refresh_lr()
+            eng = self._engine()
+            b, dev = self._hip_batch, self._hip_device
+            n = int(b["obs"].shape[0])
+            bsz, steps = GA.chunking(n, self.disc_update_num)        # ValueError before anything is launched (gail.py:224: bsz 0)
+            if self._hip_perms == "host":
+                perm = np.random.permutation(n)                       # Batch.split, batch.py:1209
+                ei = np.concatenate([np.asarray(self.expert_buffer.sample_indices(bsz), np.int64) for _ in range(steps)])
+            else:
+                import ctypes as C
+
+                from . import _lib
+                from .buffer import random_permutation
+
+                u = self._hip_updates + 1                             # the update counter HipPPO's permutations take below
+                key = ((self._hip_perm_seed * 0x9E3779B97F4A7C15) ^ (u << 20) ^ _GAIL_KEY) & (2**64 - 1)
+                perm = random_permutation(n, key, dev)
+                off, ln = self._hip_expert_layout(dev)
+                ei = torch.empty(steps * bsz, dtype=torch.int64, device=dev)
+                err = torch.zeros(1, dtype=torch.int32, device=dev)
+                for k in range(steps):                                # (the sampler's output is grouped by sub-buffer: one draw per step)
+                    _lib.check(_lib.load().ts_sample_indices_seeded(
+                        _lib.ptr(off), _lib.i64(off.numel()), _lib.ptr(ln), C.c_uint64(key), C.c_uint64(k), _lib.i64(bsz),
+                        C.c_void_p(ei.data_ptr() + 8 * k * bsz), _lib.ptr(err), _lib.current_stream(dev)))
+            dstats = eng.gail.disc_update(b["obs"], b["act"], perm, ei)
+            stat = super()._update_with_batch(batch, batch_size, repeat)
+            arr = dstats.cpu().numpy().astype(np.float64)             # the one read of the discriminator's statistics
+            seq = SequenceSummaryStats.from_sequence
+            return GailTrainingStats(**stat.__dict__, disc_loss=seq(arr[:, 0]), acc_pi=seq(arr[:, 1]), acc_exp=seq(arr[:, 2]))
+
+    return HipGAIL
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1325,6 +1473,11 @@ class _OnPart(NamedTuple):
     params: list          # the torch parameters in converter order; one part may span modules (PPO: the actor's, then the critic's)
     from_torch: Callable  # tensors in `params` order (parameters or moments) -> flat
     to_torch: Callable    # flat -> tensors in `params` order
+    holder: str | None = None   # the engine attribute of the sub-engine that owns the vectors (HipGAIL's discriminator); None: the engine
+    step: str = "adam_step"     # the owner's attribute with the optimizer's step count
+
+    def own(self, eng):
+        return eng if self.holder is None else getattr(eng, self.holder)
 
     def flat(self) -> torch.Tensor:
         """The parameters as the flat vector an engine is constructed from."""
@@ -1345,9 +1498,11 @@ def _on_load(algo, eng):
     checkpoint, algorithm_base.py:523-543), return statistics.  The inverse of `_on_write_back`.  -> eng"""
     for part in algo._hip_parts(eng):
         if part.moments is not None:
-            ms, vs, eng.adam_step = adam_state(part.optim._optim, part.params)
-            setattr(eng, part.moments[0], part.from_torch(ms))
-            setattr(eng, part.moments[1], part.from_torch(vs))
+            own = part.own(eng)
+            ms, vs, step = adam_state(part.optim._optim, part.params)
+            setattr(own, part.step, step)
+            setattr(own, part.moments[0], part.from_torch(ms))
+            setattr(own, part.moments[1], part.from_torch(vs))
     rms = _on_ret_rms(algo)
     eng.ret_rms = [float(rms.mean), float(rms.var), float(rms.count)]
     return eng
@@ -1362,12 +1517,13 @@ def _on_write_back(algo, params: bool = True, optimizer: bool = True) -> None:
         return
     with torch.no_grad():
         for part in algo._hip_parts(eng):
+            own = part.own(eng)
             if params:
-                for p, t in zip(part.params, part.to_torch(getattr(eng, part.name))):
+                for p, t in zip(part.params, part.to_torch(getattr(own, part.name))):
                     algo._hip_put(p, t)
             if optimizer and part.moments is not None:
-                m, v = (part.to_torch(getattr(eng, name)) for name in part.moments)
-                store_adam_state(part.optim._optim, part.params, m, v, eng.adam_step)
+                m, v = (part.to_torch(getattr(own, name)) for name in part.moments)
+                store_adam_state(part.optim._optim, part.params, m, v, getattr(own, part.step))
     if params:
         _on_ret_rms(algo, eng)
 
