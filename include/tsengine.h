@@ -1562,6 +1562,48 @@ int ts_td3bc_update(ts_workspace* ws, const ts_td3_state* st, int64_t critic_ste
                     const ts_mlp_trunk* trunk, const ts_td3_hparams* hp, double bc_alpha, float* stats_out4, float* weight_out,
                     float* grads_out, ts_stream_t stream);
 
+/* ---- behaviour cloning (imitation/imitation_base.py:108-127): ImitationLearningAlgorithmMixin._imitation_update ----------
+ * The loss alone on an actor network: softmax cross-entropy on a discrete actor's logits, MSE on a deterministic continuous
+ * actor's action.  Every reduction below runs in a fixed order without floating-point atomics: the same inputs give the same
+ * bits.  No new struct: the trunks travel as ts_mlp_trunk, DQNet's hyper-parameters as ts_dqn_hparams. */
+#define TS_BC_DISCRETE 0   /* ts_bc_mlp_update mode: head = n_out logits, act = int64[B] */
+#define TS_BC_CONTINUOUS 1 /* head = TD3's actor head, a = max_action * tanh(head), act = float32[B, n_out] */
+
+/* loss[0] = F.nll_loss(F.log_softmax(logits, -1), act) (mean over B) and dlogits = (softmax(logits) - onehot(act)) / B on raw
+ * arrays: logits / dlogits float32[B, ld] (row pitch ld >= A), act int64[B], 1 <= A <= 64 (TS_ERR_INVALID_ARG beyond).  The row
+ * maximum is subtracted before exp.  Padding columns [A, ld) of dlogits are written as exact zeros.  An act[b] outside [0, A)
+ * is never used as an index: that row's dlogits and the loss are NaN (torch raises there). */
+int ts_bc_ce_loss(const float* logits, int64_t ld, const int64_t* act, int64_t B, int64_t A, float* loss, float* dlogits,
+                  ts_stream_t stream);
+
+/* loss[0] = F.mse_loss(a, act_data) (mean over B * act_dim) with a = max_action * tanh(head), and
+ * dhead = 2 (a - act_data) / (B act_dim) * max_action * (1 - tanh^2): head / dhead float32[B, 32] (the actor head's pitch;
+ * columns [act_dim, 32) of dhead are written as zeros), act_data float32[B, act_dim].  a is one float32 product, as
+ * ts_td3_policy_forward rounds it.  act_dim > 32 (the MLP actor head's limit): TS_ERR_UNSUPPORTED. */
+int ts_bc_mse_loss(const float* head, const float* act_data, int64_t B, int64_t act_dim, double max_action, float* loss,
+                   float* dhead, ts_stream_t stream);
+
+/* One _imitation_update on DQNet(c, h, w, n_act) in ts_dqn_update's flat layout: forward, cross-entropy of the logits
+ * against act int64[B], backward (the dense head gradient and the head layer's backward pass share the loss kernel's launch),
+ * hp->max_grad_norm clip, Adam.  Observations u8 or f32 NHWC as ts_dqn_update; hp->huber_delta is ignored; hp->lr < 0:
+ * gradient only.  grad_out (nullable): the unclipped flat gradient, every element written.  loss_out float32[1]. */
+int ts_bc_dqnet_update(ts_workspace* ws, float* params, float* adam_m, float* adam_v, int64_t adam_step, int64_t c, int64_t h,
+                       int64_t w, int64_t n_act, const void* obs_nhwc, int obs_u8, const int64_t* act, int64_t B,
+                       const ts_dqn_hparams* hp, float* loss_out, float* grad_out, ts_stream_t stream);
+
+/* Net(obs_dim, n_out, hidden_sizes) as a discrete actor, in ts_mlp_layout(obs_dim, hidden, depth, pad32(n_out))'s layout
+ * (2 <= n_out <= 64): logits_out (nullable) float32[B, n_out], act_out (nullable) int64[B] = the first maximum. */
+int ts_bc_mlp_forward(ts_workspace* ws, const float* params, const float* obs, int64_t B, int64_t obs_dim, int64_t n_out,
+                      const ts_mlp_trunk* trunk, float* logits_out, int64_t* act_out, ts_stream_t stream);
+
+/* One _imitation_update on an MLP actor.  mode TS_BC_DISCRETE: the network of ts_bc_mlp_forward, act int64[B], loss
+ * ts_bc_ce_loss.  TS_BC_CONTINUOUS: TD3's actor (ts_td3_policy_forward's layout and max_action), act float32[B, n_out], loss
+ * ts_bc_mse_loss; n_out > 32: TS_ERR_UNSUPPORTED.  max_grad_norm 0: no clip; lr < 0: gradient only; grad_out as above. */
+int ts_bc_mlp_update(ts_workspace* ws, float* params, float* adam_m, float* adam_v, int64_t adam_step, const float* obs,
+                     const void* act, int64_t B, int64_t obs_dim, int64_t n_out, const ts_mlp_trunk* trunk, int mode,
+                     double max_action, double lr, double beta1, double beta2, double adam_eps, double max_grad_norm,
+                     float* loss_out, float* grad_out, ts_stream_t stream);
+
 /* ---- continuous CQL (imitation/cql.py:203-400, arXiv 2006.04779, with the Cal-QL option) on SAC's networks and state ----
  * cql_hp: a plain double array indexed by TS_CQL_HP_* (no struct: the SAC structs carry everything else). */
 #define TS_CQL_HP_GAMMA 0

@@ -11,6 +11,7 @@
 #include <cstring>
 #include "ts_common.h"
 #include "ts_conv.h"
+#include "ts_bc.h"
 
 namespace ts {
 int adam_step(hipStream_t s, float* params, float* m, float* v, const float* grad, int64_t n, int64_t step,
@@ -179,6 +180,109 @@ __global__ __launch_bounds__(256) void head_backward_kernel(const float* __restr
     const int k = (int)(i - b * HIDDEN);
     const float g = td_terms(q, act, ret, weight, b, A, huber_delta, inv_b, &t, &l);
     dh4[i] = h4[i] > 0.f ? g * wb[(int64_t)k * A + act[b]] : 0.f;
+}
+
+// ---- behaviour cloning (imitation/imitation_base.py:119-122): softmax cross-entropy over ALL actions, its DENSE head
+// gradient g[b, a] = (softmax(Q[b])_a - 1{a = act_b}) / B and the head layer's backward pass in ONE launch, as above: every
+// workgroup recomputes the part of g it needs from Q instead of reading it from a launch before it.  A row's softmax is two
+// numbers (ts::bc_row_stats, one thread per row); g is then one exp and one division per element.
+//   workgroup 0:              loss = mean_b nll_b (ts::bc_block_mean_nll)
+//   workgroups 1 .. BC_KB:    dWb5[k, a] = sum_b H4[b, k] g[b, a] for BC_KPER rows k (row HIDDEN: bias, H = 1), thread t on the
+//                             batch rows t (mod 256) as in head_backward_kernel
+//   the rest, BC_ROWS rows b: dH4[b, k] = (H4[b, k] > 0) sum_a g[b, a] W5[k, a]: g of the rows in LDS, thread t on k = t and
+//                             t + 256 with one accumulator per row, a = 0 .. A - 1 in order (W5 is read once per workgroup)
+// No atomics, every order fixed by (B, A).  An act[b] outside [0, A) makes row b's g NaN (and with it the loss, dWb5 and row b
+// of dH4 where H4 > 0); it is compared and range-checked, never used as an index.
+constexpr int BC_KPER = 4;
+constexpr int BC_KB = (HIDDEN + 1 + BC_KPER - 1) / BC_KPER;
+constexpr int BC_ROWS = 16;
+__global__ __launch_bounds__(256) void bc_head_backward_kernel(const float* __restrict__ q, const int64_t* __restrict__ act,
+                                                               const float* __restrict__ h4, const float* __restrict__ wb,
+                                                               int64_t B, int A, float* __restrict__ loss,
+                                                               float* __restrict__ dwb, float* __restrict__ dh4) {
+    __shared__ float red[BC_KPER][4][MAX_ACT];        // (also: the loss's four wave sums; g of BC_ROWS rows)
+    __shared__ ts::BcRow stats[256];
+    __shared__ int64_t acts[256];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float fb = (float)B;
+    if (blockIdx.x == 0) {
+        const float mean = ts::bc_block_mean_nll(q, A, act, B, A, &red[0][0][0]);
+        if (threadIdx.x == 0) *loss = mean;
+        return;
+    }
+    if (blockIdx.x <= BC_KB) {
+        // head_backward_kernel's thread map: thread t owns the rows b = t (mod 256) in batch order, 8 actions per pass keep
+        // the accumulators in registers (the row's statistics are taken again in every pass), per (k, action) a wave shuffle
+        // tree, then the 4 wave sums in order
+        const int k0 = (blockIdx.x - 1) * BC_KPER;
+        for (int a0 = 0; a0 < A; a0 += 8) {
+            float acc[BC_KPER][8];
+#pragma unroll
+            for (int i = 0; i < BC_KPER; ++i)
+#pragma unroll
+                for (int a = 0; a < 8; ++a) acc[i][a] = 0.f;
+            for (int64_t b = threadIdx.x; b < B; b += 256) {
+                const float* row = q + b * A;
+                const ts::BcRow st = ts::bc_row_stats(row, A);
+                const int64_t ab = act[b];
+                float hv[BC_KPER];
+#pragma unroll
+                for (int i = 0; i < BC_KPER; ++i) hv[i] = k0 + i < HIDDEN ? h4[b * HIDDEN + k0 + i] : (k0 + i == HIDDEN ? 1.f : 0.f);
+#pragma unroll
+                for (int a = 0; a < 8; ++a) {
+                    if (a0 + a >= A) break;
+                    const float g = ts::bc_elem_grad(row[a0 + a], a0 + a, A, ab, st) / fb;
+#pragma unroll
+                    for (int i = 0; i < BC_KPER; ++i) acc[i][a] += hv[i] * g;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < BC_KPER; ++i)
+#pragma unroll
+                for (int a = 0; a < 8; ++a) {
+                    float v = acc[i][a];
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+                    if (lane == 0) red[i][wave][a0 + a] = v;
+                }
+        }
+        __syncthreads();
+        if (lane < A) {            // wave i writes row k0 + i
+            const int k = k0 + wave;
+            if (k <= HIDDEN) dwb[k * A + lane] = (red[wave][0][lane] + red[wave][1][lane]) + (red[wave][2][lane] + red[wave][3][lane]);
+        }
+        return;
+    }
+    float* gs = &red[0][0][0];                            // [BC_ROWS][MAX_ACT]
+    static_assert(BC_ROWS * MAX_ACT <= BC_KPER * 4 * MAX_ACT, "g of a row group fits the reduction buffer");
+    const int64_t b0 = (int64_t)(blockIdx.x - BC_KB - 1) * BC_ROWS;
+    const int rows = (int)(B - b0 < BC_ROWS ? B - b0 : BC_ROWS);
+    if ((int)threadIdx.x < rows) {
+        stats[threadIdx.x] = ts::bc_row_stats(q + (b0 + threadIdx.x) * A, A);
+        acts[threadIdx.x] = act[b0 + threadIdx.x];
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < BC_ROWS * MAX_ACT; e += 256) {
+        const int r = e / MAX_ACT, a = e - r * MAX_ACT;
+        gs[e] = r < rows && a < A ? ts::bc_elem_grad(q[(b0 + r) * A + a], a, A, acts[r], stats[r]) / fb : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < HIDDEN / 256; ++j) {
+        const int k = threadIdx.x + 256 * j;
+        float s[BC_ROWS];
+#pragma unroll
+        for (int r = 0; r < BC_ROWS; ++r) s[r] = 0.f;
+#pragma unroll 4
+        for (int a = 0; a < A; ++a) {                 // (unrolled: W5's loads go out together)
+            const float w5 = wb[(int64_t)k * A + a];
+#pragma unroll
+            for (int r = 0; r < BC_ROWS; ++r) s[r] += gs[r * MAX_ACT + a] * w5;
+        }
+#pragma unroll
+        for (int r = 0; r < BC_ROWS; ++r)
+            if (r < rows) dh4[(b0 + r) * HIDDEN + k] = h4[(b0 + r) * HIDDEN + k] > 0.f ? s[r] : 0.f;
+    }
 }
 
 struct Scratch {           // carve of the workspace for one network pass over B samples
@@ -432,6 +536,56 @@ int ts_dqn_update_cached(ts_workspace* ws, float* params, float* adam_m, float* 
     TS_REQUIRE(cache != nullptr, TS_ERR_INVALID_ARG, "ts_dqn_update_cached: cache is NULL");
     return dqn_update_impl(ws, params, adam_m, adam_v, adam_step, c, h, w, n_act, obs_nhwc, obs_u8, act, returns, weight, B, hp,
                            td_out, loss_out, grad_out, stream, cache, "ts_dqn_update_cached");
+}
+
+// ---- behaviour cloning on DQNet: ImitationLearningAlgorithmMixin._imitation_update, discrete branch -------------------------
+int ts_bc_dqnet_update(ts_workspace* ws, float* params, float* adam_m, float* adam_v, int64_t adam_step, int64_t c, int64_t h,
+                       int64_t w, int64_t n_act, const void* obs_nhwc, int obs_u8, const int64_t* act, int64_t B,
+                       const ts_dqn_hparams* hp, float* loss_out, float* grad_out, ts_stream_t stream) {
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_bc_dqnet_update: workspace is NULL");
+    TS_REQUIRE(B >= 1 && adam_step >= 1, TS_ERR_INVALID_ARG, "ts_bc_dqnet_update: bad batch size / step");
+    TS_REQUIRE(params && adam_m && adam_v && obs_nhwc && act && hp && loss_out, TS_ERR_INVALID_ARG,
+               "ts_bc_dqnet_update: NULL argument");
+    Net n;
+    if (int rc = make_net((int)B, (int)c, (int)h, (int)w, (int)n_act, &n)) return rc;
+    hipStream_t s = ts::as_stream(stream);
+    // workspace: forward scratch | dY of every layer | wgrad slabs | flat gradient | norm partials (ts_dqn_update's carve)
+    size_t bytes = fwd_scratch_bytes(n, B);
+    for (int i = 0; i < 4; ++i) bytes += align_up(sizeof(float) * n.l[i].out_elems());
+    size_t slab[4];
+    for (int i = 0; i < 4; ++i) {
+        slab[i] = align_up(sizeof(float) * (size_t)ts::conv_wgrad_splits(n.l[i]) * n.l[i].param_elems());
+        bytes += slab[i];
+    }
+    bytes += align_up(sizeof(float) * n.total) + 4096;
+    if (int rc = ts::ws_reserve(ws, bytes)) return rc;
+    Scratch sc;
+    char* p = carve_fwd(n, B, static_cast<char*>(ws->base), &sc);
+    float* dy[4];
+    for (int i = 0; i < 4; ++i) { dy[i] = reinterpret_cast<float*>(p); p += align_up(sizeof(float) * n.l[i].out_elems()); }
+    float* slabs[4];
+    for (int i = 0; i < 4; ++i) { slabs[i] = reinterpret_cast<float*>(p); p += slab[i]; }
+    float* grad = reinterpret_cast<float*>(p); p += align_up(sizeof(float) * n.total);
+    float* norm_part = reinterpret_cast<float*>(p);
+    if (grad_out) grad = grad_out;
+
+    if (int rc = net_forward(s, ws, n, params, obs_nhwc, obs_u8 != 0, B, sc, sc.q, nullptr)) return rc;
+    // cross-entropy, its dense head gradient and the head layer's backward pass: one launch
+    hipLaunchKernelGGL(bc_head_backward_kernel, dim3((unsigned)(1 + BC_KB + ts::ceil_div(B, BC_ROWS))), dim3(256), 0, s, sc.q, act,
+                       sc.h[3], params + n.off[4], B, n.n_act, loss_out, grad + n.off[4], dy[3]);
+    TS_LAUNCH_CHECK();
+    {
+        const float* x[4]; const float* wb[4]; float* g[4];
+        for (int i = 0; i < 4; ++i) {
+            x[i] = i == 0 ? static_cast<const float*>(obs_nhwc) : sc.h[i - 1];
+            wb[i] = params + n.off[i];
+            g[i] = grad + n.off[i];
+        }
+        if (int rc = ts::chain_backward(s, ws, 4, n.l, x, dy, wb, slabs, g, obs_u8 != 0)) return rc;
+    }
+    if (hp->lr < 0.0) return TS_OK;      // gradient-only mode
+    return ts::adam_step(s, params, adam_m, adam_v, grad, n.total, adam_step, hp->lr, hp->beta1, hp->beta2, hp->adam_eps,
+                         hp->max_grad_norm, norm_part);
 }
 
 // ---- one call per update on a device-resident frame replay (uniform or prioritized) -----------------------------------------

@@ -19,6 +19,7 @@
 #include "ts_common.h"
 #include "ts_conv.h"
 #include "ts_mlp.h"
+#include "ts_bc.h"
 
 #pragma clang fp contract(off)   // the elementwise formulas follow torch's operation order
 
@@ -3565,6 +3566,203 @@ int ts_cbcq_update(ts_workspace* ws, float* const* state, int64_t adam_step, con
     }
     TS_LAUNCH_CHECK();
     return TS_OK;
+}
+
+}  // extern "C"
+
+// ---- behaviour cloning (imitation/imitation_base.py:108-127): the loss alone, on a Net actor ----------------------------------
+namespace {
+
+// F.nll_loss(F.log_softmax(logits, -1), act) and d loss / d logits = (softmax - onehot) / B on rows of pitch ld >= A, A <= 64.
+// Workgroup 0: the loss (ts::bc_block_mean_nll); the others: 256 rows each -- thread t takes row t's softmax statistics
+// (ts::bc_row_stats) into LDS, then the 256 threads sweep the rows' ld columns, neighbouring threads on neighbouring floats;
+// padding columns [A, ld) are written as zeros.
+__global__ __launch_bounds__(256) void bc_ce_kernel(const float* __restrict__ logits, int64_t ld, const int64_t* __restrict__ act,
+                                                    int64_t B, int A, float* __restrict__ loss, float* __restrict__ dlogits) {
+    __shared__ float red[4];
+    __shared__ ts::BcRow stats[256];
+    __shared__ int64_t acts[256];
+    if (blockIdx.x == 0) {
+        const float mean = ts::bc_block_mean_nll(logits, ld, act, B, A, red);
+        if (threadIdx.x == 0) *loss = mean;
+        return;
+    }
+    const int64_t b0 = (int64_t)(blockIdx.x - 1) * 256;
+    const int rows = (int)(B - b0 < 256 ? B - b0 : 256);
+    if ((int)threadIdx.x < rows) {
+        stats[threadIdx.x] = ts::bc_row_stats(logits + (b0 + threadIdx.x) * ld, A);
+        acts[threadIdx.x] = act[b0 + threadIdx.x];
+    }
+    __syncthreads();
+    const float fb = (float)B;
+    for (int64_t e = threadIdx.x; e < (int64_t)rows * ld; e += 256) {
+        const int r = (int)(e / ld);
+        const int col = (int)(e - (int64_t)r * ld);
+        const int64_t i = (b0 + r) * ld + col;
+        dlogits[i] = col < A ? ts::bc_elem_grad(logits[i], col, A, acts[r], stats[r]) / fb : 0.f;
+    }
+}
+
+// F.mse_loss(max_action * tanh(head), act_data) and d loss / d head on TD3's 32-column actor head (pre-tanh).  a is rounded
+// as det_policy_kernel rounds it -- one float32 product -- so the forward pass, the loss and the gradient see one action.
+// Workgroup 0: the sum of B A squares (thread t: elements t, t + 1024, ...; block_sum_1024); the others: thread (b, j < 32),
+// the whole row written (zeros beyond A), td3bc_policy_bwd_kernel's mse term.
+__global__ __launch_bounds__(1024) void bc_mse_kernel(const float* __restrict__ head, const float* __restrict__ a_data, int64_t B,
+                                                      int A, float max_action, float* __restrict__ loss,
+                                                      float* __restrict__ d_head) {
+    __shared__ float red[1024];
+    if (blockIdx.x == 0) {
+        float sq = 0.f;
+        for (int64_t i = threadIdx.x; i < B * A; i += 1024) {
+            const int64_t b = i / A;
+            const float dlt = __fmul_rn(max_action, tanhf(head[b * 32 + (i - b * A)])) - a_data[i];
+            sq += dlt * dlt;
+        }
+        const float tot = block_sum_1024(sq, red);
+        if (threadIdx.x == 0) *loss = tot / ((float)B * (float)A);
+        return;
+    }
+    const int64_t i = (int64_t)(blockIdx.x - 1) * 1024 + threadIdx.x;
+    const int64_t b = i >> 5;
+    const int j = (int)(i & 31);
+    if (b >= B) return;
+    if (j >= A) { d_head[b * 32 + j] = 0.f; return; }
+    // t and a are the float32 values the forward pass holds; everything after them runs in double and is rounded once, so the
+    // only errors left are tanhf's own and one rounding (in float32, the five roundings of the products and of 1 / (B A) add up
+    // to the size of 4 eps32 times the value's scale on some element of a 32,000-element batch).  t = +-1 still gives exactly 0.
+    const float t = tanhf(head[b * 32 + j]);
+    const double dlt = (double)__fmul_rn(max_action, t) - (double)a_data[b * A + j];
+    const double sech2 = 1.0 - (double)t * (double)t;
+    d_head[b * 32 + j] = (float)(2.0 * dlt * (double)max_action * sech2 / ((double)B * (double)A));
+}
+
+// first maximum of a row of logits, like torch.argmax; logits_out (nullable) = the rows without their padding
+__global__ __launch_bounds__(256) void bc_argmax_kernel(const float* __restrict__ logits, int64_t B, int A, int hw,
+                                                        float* __restrict__ logits_out, int64_t* __restrict__ act_out) {
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    float best = logits[b * hw];
+    int best_a = 0;
+    for (int a = 0; a < A; ++a) {
+        const float v = logits[b * hw + a];
+        if (logits_out) logits_out[b * A + a] = v;
+        if (v > best) { best = v; best_a = a; }
+    }
+    if (act_out) act_out[b] = best_a;
+}
+
+int launch_bc_ce(hipStream_t s, const float* logits, int64_t ld, const int64_t* act, int64_t B, int A, float* loss, float* dlogits) {
+    hipLaunchKernelGGL(bc_ce_kernel, dim3(1 + (unsigned)ts::ceil_div(B, 256)), dim3(256), 0, s, logits, ld, act, B, A, loss, dlogits);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+int launch_bc_mse(hipStream_t s, const float* head, const float* a_data, int64_t B, int A, float max_action, float* loss,
+                  float* d_head) {
+    hipLaunchKernelGGL(bc_mse_kernel, dim3(1 + (unsigned)ts::ceil_div(B * 32, 1024)), dim3(1024), 0, s, head, a_data, B, A,
+                       max_action, loss, d_head);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+// the network of a route: TD3's actor (continuous) or DiscreteSAC's (discrete: pad32(A) head columns)
+struct BcNet { Mlp m; int obs, out, ka, hw, hid, depth; };
+int bc_net(const char* who, int mode, const ts_mlp_trunk* trunk, int64_t B, int64_t obs_dim, int64_t n_out, BcNet* n) {
+    TS_REQUIRE(mode == TS_BC_DISCRETE || mode == TS_BC_CONTINUOUS, TS_ERR_INVALID_ARG, "%s: mode TS_BC_DISCRETE or TS_BC_CONTINUOUS", who);
+    if (mode == TS_BC_CONTINUOUS) {
+        TS_REQUIRE(n_out <= 32, TS_ERR_UNSUPPORTED, "%s: the MLP actor head holds at most 32 action dimensions (got %lld)", who,
+                   (long long)n_out);
+        Dims d;
+        if (int rc = make_dims(trunk, obs_dim, n_out, &d)) return rc;
+        *n = BcNet{make_mlp((int)B, d.ka, 32, d.hid, d.depth, d.fn), d.obs, d.act, d.ka, 32, d.hid, d.depth};
+        return TS_OK;
+    }
+    DDims d;
+    if (int rc = make_ddims(trunk, obs_dim, n_out, &d)) return rc;
+    *n = BcNet{make_mlp((int)B, d.ka, d.hw, d.hid, d.depth, d.fn), d.obs, d.act, d.ka, d.hw, d.hid, d.depth};
+    return TS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ts_bc_ce_loss(const float* logits, int64_t ld, const int64_t* act, int64_t B, int64_t A, float* loss, float* dlogits,
+                  ts_stream_t stream) {
+    TS_REQUIRE(A >= 1 && A <= ts::BC_MAX_ACT, TS_ERR_INVALID_ARG, "ts_bc_ce_loss: 1 <= A <= %d (got %lld)", ts::BC_MAX_ACT, (long long)A);
+    TS_REQUIRE(B >= 1 && ld >= A, TS_ERR_INVALID_ARG, "ts_bc_ce_loss: B >= 1 and a row pitch ld >= A");
+    TS_REQUIRE(logits && act && loss && dlogits, TS_ERR_INVALID_ARG, "ts_bc_ce_loss: NULL argument");
+    return launch_bc_ce(ts::as_stream(stream), logits, ld, act, B, (int)A, loss, dlogits);
+}
+
+int ts_bc_mse_loss(const float* head, const float* act_data, int64_t B, int64_t act_dim, double max_action, float* loss,
+                   float* dhead, ts_stream_t stream) {
+    TS_REQUIRE(act_dim >= 1 && B >= 1 && B <= (int64_t)1 << 40, TS_ERR_INVALID_ARG, "ts_bc_mse_loss: B >= 1 and act_dim >= 1");
+    TS_REQUIRE(act_dim <= 32, TS_ERR_UNSUPPORTED, "ts_bc_mse_loss: the MLP actor head holds at most 32 action dimensions (got %lld)",
+               (long long)act_dim);
+    TS_REQUIRE(head && act_data && loss && dhead, TS_ERR_INVALID_ARG, "ts_bc_mse_loss: NULL argument");
+    return launch_bc_mse(ts::as_stream(stream), head, act_data, B, (int)act_dim, (float)max_action, loss, dhead);
+}
+
+int ts_bc_mlp_forward(ts_workspace* ws, const float* params, const float* obs, int64_t B, int64_t obs_dim, int64_t n_out,
+                      const ts_mlp_trunk* trunk, float* logits_out, int64_t* act_out, ts_stream_t stream) {
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_bc_mlp_forward: workspace is NULL");
+    TS_REQUIRE(B >= 1 && params && obs && (logits_out || act_out), TS_ERR_INVALID_ARG, "ts_bc_mlp_forward: bad argument");
+    BcNet n;
+    if (int rc = bc_net("ts_bc_mlp_forward", TS_BC_DISCRETE, trunk, B, obs_dim, n_out, &n)) return rc;
+    hipStream_t s = ts::as_stream(stream);
+    if (int rc = ts::ws_reserve(ws, al(4 * B * n.ka) + (size_t)n.depth * al(4 * B * n.hid) + al(4 * B * n.hw) +
+                                        al(4 * split_floats(n.m)) + 4096))
+        return rc;
+    Carve c{static_cast<char*>(ws->base)};
+    float* x = c.take<float>(B * n.ka);
+    const Act a = take_act(c, B, n.hw, n.hid, n.depth);
+    float* split = c.take<float>(split_floats(n.m));
+    hipLaunchKernelGGL(sac_pack_kernel, dim3((unsigned)ts::ceil_div(B * n.ka / 4, 256)), dim3(256), 0, s, obs,
+                       (const float*)nullptr, B, n.obs, 0, n.ka, 0, x, (float*)nullptr, (float*)nullptr);
+    if (int rc = mlp_forward(s, ws, n.m, params, x, a, split)) return rc;
+    hipLaunchKernelGGL(bc_argmax_kernel, dim3((unsigned)ts::ceil_div(B, 256)), dim3(256), 0, s, a.out, B, n.out, n.hw, logits_out,
+                       act_out);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+int ts_bc_mlp_update(ts_workspace* ws, float* params, float* adam_m, float* adam_v, int64_t adam_step, const float* obs,
+                     const void* act, int64_t B, int64_t obs_dim, int64_t n_out, const ts_mlp_trunk* trunk, int mode,
+                     double max_action, double lr, double beta1, double beta2, double adam_eps, double max_grad_norm,
+                     float* loss_out, float* grad_out, ts_stream_t stream) {
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_bc_mlp_update: workspace is NULL");
+    TS_REQUIRE(B >= 1 && adam_step >= 1, TS_ERR_INVALID_ARG, "ts_bc_mlp_update: bad batch size / step");
+    TS_REQUIRE(params && adam_m && adam_v && obs && act && loss_out, TS_ERR_INVALID_ARG, "ts_bc_mlp_update: NULL argument");
+    BcNet n;
+    if (int rc = bc_net("ts_bc_mlp_update", mode, trunk, B, obs_dim, n_out, &n)) return rc;
+    hipStream_t s = ts::as_stream(stream);
+    const size_t slab = slab_floats(n.m), spl = split_floats(n.m);
+    const int64_t P = n.m.total();
+    // x | activations | d loss / d head | dh of every hidden layer, slabs | split | flat gradient | norm partials
+    const size_t bytes = al(4 * B * n.ka) + 2 * (size_t)n.depth * al(4 * B * n.hid) + 2 * al(4 * B * n.hw) + al(4 * slab) +
+                         al(4 * spl) + al(4 * P) + 8192;
+    if (int rc = ts::ws_reserve(ws, bytes)) return rc;
+    Carve c{static_cast<char*>(ws->base)};
+    float* x = c.take<float>(B * n.ka);
+    const Act a = take_act(c, B, n.hw, n.hid, n.depth);
+    float* d_out = c.take<float>(B * n.hw);
+    const BwdScratch sc = take_scratch(c, B, n.hid, n.depth, slab);
+    float* split = c.take<float>(spl);
+    float* grad = c.take<float>(P);
+    float* norm_part = c.take<float>(1024);
+    if (grad_out) grad = grad_out;
+    hipLaunchKernelGGL(sac_pack_kernel, dim3((unsigned)ts::ceil_div(B * n.ka / 4, 256)), dim3(256), 0, s, obs,
+                       (const float*)nullptr, B, n.obs, 0, n.ka, 0, x, (float*)nullptr, (float*)nullptr);
+    if (int rc = mlp_forward(s, ws, n.m, params, x, a, split)) return rc;
+    if (mode == TS_BC_DISCRETE) {
+        if (int rc = launch_bc_ce(s, a.out, n.hw, static_cast<const int64_t*>(act), B, n.out, loss_out, d_out)) return rc;
+    } else {
+        if (int rc = launch_bc_mse(s, a.out, static_cast<const float*>(act), B, n.out, (float)max_action, loss_out, d_out)) return rc;
+    }
+    if (int rc = mlp_backward(s, ws, n.m, params, x, a, d_out, grad, nullptr, 0, 0, sc)) return rc;
+    if (lr < 0.0) return TS_OK;          // gradient-only mode
+    return ts::adam_step(s, params, adam_m, adam_v, grad, P, adam_step, lr, beta1, beta2, adam_eps, max_grad_norm, norm_part);
 }
 
 }  // extern "C"

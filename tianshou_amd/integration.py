@@ -3128,6 +3128,196 @@ def make_hip_td3bc(ref=None):
 
 
 # ---------------------------------------------------------------------------------------------------
+# vanilla imitation learning / behaviour cloning (imitation/imitation_base.py)
+# ---------------------------------------------------------------------------------------------------
+class _BCRoute(NamedTuple):
+    """What `make_hip_imitation` reads off the actor at construction."""
+    kind: str             # "dqnet" | "discrete" | "continuous"
+    keys: list            # state_dict keys of the actor in the converters' order
+    n_out: int            # actions (discrete routes) or action dimensions
+    obs_dim: int          # MLP routes (DQNet: 0, the frame shape comes with the first batch)
+    sizes: tuple          # MLP routes: hidden widths of the torch network
+    activation: str       # MLP routes: "relu" | "tanh"
+    max_action: float     # continuous route
+
+
+def _bc_route(policy, who: str) -> _BCRoute:
+    """The engine route of an ImitationPolicy's actor, or NotImplementedError naming the actor's class: DQNet by its state_dict
+    keys (as HipDQN), a Net with an action head (Linear / activation pairs and a final bare Linear), or a
+    ContinuousActorDeterministic over a Net.  The action type must be the route's; activations nn.ReLU or nn.Tanh; no norm
+    layer, softmax or dueling head; anything else (a recurrent model, a probabilistic actor) is refused, never run in eager."""
+    from . import bc as BC
+    from . import dqn as D
+    from . import td3 as T
+    from . import widths as WD
+
+    actor = policy.actor
+    name = type(actor).__name__
+    action_type = getattr(policy, "action_type", None)
+    keys = list(actor.state_dict().keys())
+
+    def need(kind: str, want: str) -> None:
+        if action_type != want:
+            raise NotImplementedError(f"{who}: the {kind} route of actor {name} needs a {want} action space, the policy's action "
+                                      f"type is {action_type!r}")
+
+    if keys == D.TIANSHOU_KEYS:
+        need("DQNet", "discrete")
+        shapes = [tuple(p.shape) for p in params_by_keys(actor, keys)]
+        if not (len(shapes[0]) == 4 and shapes[0][0] == 32 and shapes[0][2:] == (8, 8) and shapes[2] == (64, 32, 4, 4)
+                and shapes[4] == (64, 64, 3, 3) and shapes[6][0] == 512):
+            raise NotImplementedError(f"{who}: unsupported actor {name}: not the DQNet(c, h, w, action_shape) convolution trunk")
+        n_act = int(shapes[8][0])
+        if not 1 <= n_act <= BC.MAX_ACT:
+            raise NotImplementedError(f"{who}: actor {name}: 1 .. {BC.MAX_ACT} actions, got {n_act}")
+        return _BCRoute("dqnet", keys, n_act, 0, (), "relu", 0.0)
+    # ContinuousActorDeterministic over a Net (`head`), or Net(state_shape, action_shape, hidden_sizes) itself
+    head = hasattr(actor, "preprocess") and hasattr(actor, "last") and hasattr(actor, "max_action")
+    seq = getattr(getattr(actor.preprocess if head else actor, "model", None), "model", None)
+    seq = list(seq) if isinstance(seq, torch.nn.Sequential) else None
+    if seq is None:
+        raise NotImplementedError(f"{who}: unsupported actor {name}: DQNet, Net(state_shape, action_shape, hidden_sizes) or "
+                                  "ContinuousActorDeterministic over a Net (a recurrent or probabilistic actor has no engine route)")
+    norms = [type(m).__name__ for m in seq if "Norm" in type(m).__name__]
+    if norms:
+        raise NotImplementedError(f"{who}: actor {name} has a norm layer ({norms[0]}); the engine's trunks have none")
+    body = seq if head else seq[:-1]
+    acts = {type(m) for m in body[1::2]}
+    pairs_ok = len(body) >= 2 and len(body) % 2 == 0 and all(isinstance(m, torch.nn.Linear) for m in body[0::2])
+    if not pairs_ok or (not head and not isinstance(seq[-1], torch.nn.Linear)):
+        raise NotImplementedError(f"{who}: unsupported actor {name}: the trunk must be Linear layers, each followed by its "
+                                  f"activation (got {[type(m).__name__ for m in seq]})")
+    if len(acts) != 1 or next(iter(acts)) not in (torch.nn.ReLU, torch.nn.Tanh):
+        raise NotImplementedError(f"{who}: actor {name}: activation nn.ReLU or nn.Tanh after every hidden layer, got "
+                                  f"{sorted(a.__name__ for a in acts)}")
+    activation = "relu" if next(iter(acts)) is torch.nn.ReLU else "tanh"
+    depth = len(body) // 2
+    if not 1 <= depth <= WD.MAX_DEPTH:
+        raise NotImplementedError(f"{who}: actor {name}: 1 .. {WD.MAX_DEPTH} hidden layers, got {depth}")
+    if head:
+        if keys != T.actor_keys(depth):
+            raise NotImplementedError(f"{who}: unsupported actor {name}: a Net trunk and a single-Linear action head are needed "
+                                      f"(got parameters {keys})")
+        need("continuous MLP", "continuous")
+    else:
+        if keys != [f"model.model.{2 * i}.{x}" for i in range(depth + 1) for x in ("weight", "bias")] \
+                or getattr(actor, "softmax", False) or getattr(actor, "use_dueling", False):
+            raise NotImplementedError(f"{who}: unsupported actor {name}: Net(state_shape, action_shape, hidden_sizes) without "
+                                      "softmax or dueling heads is needed")
+        need("discrete MLP", "discrete")
+    t = [p.detach() for p in params_by_keys(actor, keys)]
+    try:
+        sizes = WD.layer_widths(t, 1)
+        WD.engine_hidden([sizes])
+    except NotImplementedError as e:
+        raise NotImplementedError(f"{who}: actor {name}: hidden layers of widths up to 1024 ({e})") from None
+    n_out = int(t[-1].shape[0])
+    lo, hi = (1, BC.MAX_ACT_DIM) if head else (2, BC.MAX_ACT)
+    if not lo <= n_out <= hi:
+        raise NotImplementedError(f"{who}: actor {name}: the MLP head holds {lo} .. {hi} outputs, got {n_out}")
+    return _BCRoute("continuous" if head else "discrete", keys, n_out, int(t[0].shape[1]), tuple(sizes), activation,
+                    float(actor.max_action) if head else 0.0)
+
+
+def make_hip_imitation(offline: bool, ref=None):
+    """Returns HipOfflineImitationLearning(OfflineImitationLearning) (`offline=True`) or
+    HipOffPolicyImitationLearning(OffPolicyImitationLearning): `_update_with_batch` (imitation/imitation_base.py:109-127, 151-155,
+    179-183) on the engines of tianshou_amd/bc.py.  The route is chosen from `policy.actor` at construction (`_bc_route`): DQNet
+    on u8 / f32 frames, Net with an action head, ContinuousActorDeterministic over a Net; everything else raises
+    NotImplementedError, as does an optimizer other than Adam.  `_preprocess_batch` stays the base class's: the batch's `obs` and
+    `act` are what the buffer sampled ([B, c, h, w] frames are laid out NHWC on the device, as the other Atari classes' gathers
+    do).  The collector's `policy.forward` stays on torch; `action_scaling` / `action_bound_method` act in `map_action` only
+    and are not read.  The statistics are the reference's ImitationTrainingStats(loss).  `write_back`: as HipDQN.
+    `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    from . import bc as BC
+    from . import dqn as D
+
+    mod = "tianshou.algorithm.imitation.imitation_base"
+    Base = _ref(ref, mod, "OfflineImitationLearning" if offline else "OffPolicyImitationLearning")
+    ImitationTrainingStats = _ref(ref, mod, "ImitationTrainingStats")
+    who = "HipOfflineImitationLearning" if offline else "HipOffPolicyImitationLearning"
+
+    class HipImitation(_HipGlue, Base):
+        def __init__(self, *args, device="cuda", write_back="auto", **kwargs):
+            super().__init__(*args, **kwargs)
+            self._hip_device = torch.device(device)
+            self._hip_route = _bc_route(self.policy, who)
+            try:
+                _adam_of(self.optim)
+            except NotImplementedError as e:
+                raise NotImplementedError(f"{who}: {e} (got {type(self.optim._optim).__name__})") from None
+            own = {id(p) for p in self.policy.actor.parameters()}
+            if {id(p) for g in self.optim._optim.param_groups for p in g["params"]} != own:
+                raise NotImplementedError(f"{who}: one optimizer over the actor's parameters")
+            self._hip_chw = None
+            self._hip_engine = None
+            self._hip_glue_init()
+            self._hip_set_write_back(write_back, attached=False)
+
+        def _hip_parts(self, eng=None):
+            r, dev = self._hip_route, self._hip_device
+            params = params_by_keys(self.policy.actor, r.keys)
+            if r.kind == "dqnet":
+                dims = (*self._hip_chw, r.n_out)
+                fwd, back = (lambda t: D.flat_from_torch(t, *dims, dev)), (lambda f: D.flat_to_torch(f, *dims))
+            else:
+                h = self._hip_hidden
+                fwd = lambda t: BC.mlp_flat_from_torch(r.kind, t, r.obs_dim, r.n_out, h, dev)          # noqa: E731
+                back = lambda f: BC.mlp_flat_to_torch(r.kind, f, r.obs_dim, r.n_out, h, sizes=r.sizes)  # noqa: E731
+            return [_OnPart("params", ("adam_m", "adam_v"), self.optim, params, fwd, back)]
+
+        def _hip_config(self):
+            _, g = _adam_of(self.optim)
+            return BC.BCConfig(lr=g["lr"], betas=tuple(g["betas"]), adam_eps=g["eps"], max_grad_norm=self.optim._max_grad_norm,
+                               max_action=self._hip_route.max_action or 1.0)
+
+        def _engine(self, obs_shape):
+            r = self._hip_route
+            if r.kind == "dqnet":
+                if len(obs_shape) != 4 or obs_shape[1] != params_by_keys(self.policy.actor, r.keys)[0].shape[1]:
+                    raise NotImplementedError(f"{who}: DQNet observations must be [B, c, h, w] frames, got {tuple(obs_shape)}")
+                chw = tuple(int(x) for x in obs_shape[1:])
+                if self._hip_engine is not None and chw != self._hip_chw:
+                    raise ValueError(f"{who}: the frame shape changed from {self._hip_chw} to {chw}")
+                self._hip_chw = chw
+            if self._hip_engine is None:
+                if r.kind == "dqnet":
+                    eng = BC.BCDQNetEngine(*self._hip_chw, r.n_out, self._hip_parts()[0].flat(), self._hip_config())
+                else:
+                    from . import widths as WD
+
+                    self._hip_hidden = WD.engine_hidden([r.sizes])
+                    eng = BC.BCMlpEngine(r.kind, r.obs_dim, r.n_out, self._hip_parts()[0].flat(), self._hip_config(),
+                                         hidden=self._hip_hidden, depth=len(r.sizes), activation=r.activation)
+                self._hip_engine = _on_load(self, eng)                               # resume from a checkpoint
+            return self._hip_engine
+
+        def _update_with_batch(self, batch):
+            self._hip_refresh_lr()
+            _require_gpu(self._hip_device, who)
+            r, dev = self._hip_route, self._hip_device
+            obs = batch.obs if isinstance(batch.obs, torch.Tensor) else torch.as_tensor(np.asarray(batch.obs))
+            eng = self._engine(obs.shape)
+            eng.cfg.max_grad_norm = self.optim._max_grad_norm              # read at every update, as the learning rate
+            obs = obs.to(dev)
+            if r.kind == "dqnet":
+                if obs.dtype not in (torch.uint8, torch.float32):
+                    obs = obs.to(torch.float32)
+                obs = obs.permute(0, 2, 3, 1).contiguous()                  # [B, c, h, w] -> NHWC, dtype kept (u8 frames stay u8)
+            else:
+                obs = obs.reshape(obs.shape[0], -1)
+            act = batch.act if isinstance(batch.act, torch.Tensor) else torch.as_tensor(np.asarray(batch.act))
+            loss = eng.update_with_batch(obs, act.to(dev))
+            self._hip_after_update()
+            return ImitationTrainingStats(loss=float(loss.item()))                    # imitation_base.py:127
+
+        _hip_write_back = _on_write_back
+
+    HipImitation.__name__ = HipImitation.__qualname__ = who
+    return HipImitation
+
+
+# ---------------------------------------------------------------------------------------------------
 # continuous CQL (imitation/cql.py) on the nets of examples/offline/d4rl_cql.py
 # ---------------------------------------------------------------------------------------------------
 def make_hip_cql(ref=None):
