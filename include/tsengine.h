@@ -1499,6 +1499,46 @@ int ts_icm_update(ts_workspace* ws, float* params, float* state_m, float* state_
                   double rms_alpha, double rms_momentum, int32_t rms_centered, double max_grad_norm, float* stats_out3,
                   float* grad_out, ts_stream_t stream);
 
+/* ---- ICM on the Atari trunk (examples/atari/atari_ppo.py:136-160, atari_network.py DQNet(features_only=True).net): the same
+ * model with feature_net = conv1 8x8/4 -> 32, conv2 4x4/2 -> 64, conv3 3x3/1 -> 64, a ReLU behind EACH (the last one included:
+ * phi >= 0, unlike the MLP feature net above), Flatten.  Frames are NHWC [B, h, w, c], raw values, float32 (obs_u8 == 0) or uint8
+ * (obs_u8 != 0) as in ts_dqn_forward, 4-byte aligned.  F = 64 OH3 OW3; features are indexed in NHWC flatten order (h, w, channel).
+ * Flat vector `conv1 | conv2 | conv3 | forward | inverse`: the conv blocks are the wb matrices of ts_dqn_layer_offsets, the model
+ * blocks the [K_pad + 1, N_pad] blocks of ts_icm_layout (forward: F + A -> hidden -> F, inverse: 2F -> hidden -> A; model_net as
+ * above, its obs_dim is not read).  Padding entries are zero and stay zero.  The feature net runs ONCE over the stacked
+ * [obs; obs_next] (2B rows), forward and backward.  No entry point synchronises with the host, copies to it or allocates
+ * outside the workspace.
+ * TS_ERR_INVALID_ARG before any launch: a NULL pointer (nullable outputs excepted), B < 1, B > B_total, a frame smaller than
+ * the conv stack needs, w c not a multiple of 4, hidden widths outside [1, 1024], 2B h w c or 2B OH1 OW1 32 >= 2^31 (split the
+ * batch); TS_ERR_UNSUPPORTED: n_act > TS_ICM_MAX_ACTIONS, a model activation other than ReLU, non-zero flags.  An action outside
+ * [0, A) is clamped.
+ * h_out12 = {floats of the flat vector, F, then offset and floats of conv1, conv2, conv3, forward model, inverse model}. */
+int ts_icm_cnn_layout(int64_t c, int64_t h, int64_t w, const ts_net_desc* model_net, int64_t n_act, int64_t* h_out12);
+/* -> mse_out float32[B], act_hat_out (nullable) float32[B, A] */
+int ts_icm_cnn_forward(ts_workspace* ws, const float* params, int64_t c, int64_t h, int64_t w, const ts_net_desc* model_net, int64_t n_act,
+                       const void* obs_nhwc, int obs_u8, const int64_t* act, const void* obs_next_nhwc, int64_t B, float* mse_out,
+                       float* act_hat_out, ts_stream_t stream);
+/* rew_out[b] = rew[b] + (double)(mse[b] * (float)reward_scale) as ts_icm_reward; reward_scale == 0 copies rew bit for bit */
+int ts_icm_cnn_reward(ts_workspace* ws, const float* params, int64_t c, int64_t h, int64_t w, const ts_net_desc* model_net, int64_t n_act,
+                      const void* obs_nhwc, int obs_u8, const int64_t* act, const void* obs_next_nhwc, int64_t B, const double* rew,
+                      double reward_scale, double* rew_out, float* mse_out, ts_stream_t stream);
+/* Forward pass, loss and the reverse pass through all five blocks on the B rows of ONE chunk of a batch of B_total rows: the
+ * loss coefficients are w lr_scale / B_total and (1 - w) lr_scale / B_total (the means of icm.py:97-101 are over the whole
+ * batch).  accumulate == 0 overwrites grad float32[count] and sums2 = {sum mse, sum ce}; accumulate != 0 adds this chunk's
+ * onto them (no atomics: one thread per element, chunks in the order of the calls).  The same inputs and the same chunking
+ * give bit-identical results. */
+int ts_icm_cnn_grad(ts_workspace* ws, const float* params, int64_t c, int64_t h, int64_t w, const ts_net_desc* model_net, int64_t n_act,
+                    const void* obs_nhwc, int obs_u8, const int64_t* act, const void* obs_next_nhwc, int64_t B, int64_t B_total,
+                    double forward_loss_weight, double lr_scale, int accumulate, float* grad, float* sums2, ts_stream_t stream);
+/* stats_out3 = {((1 - w) sums2[1] / B_total + w sums2[0] / B_total) lr_scale, sums2[0] / B_total, sums2[1] / B_total} as
+ * ts_icm_loss, then clip_grad_norm_(max_grad_norm) and ONE ts_optim_step on `grad` with ts_icm_update's optimizer arguments;
+ * lr < 0: statistics only. */
+int ts_icm_cnn_apply(ts_workspace* ws, float* params, float* state_m, float* state_v, int64_t optim_step, int64_t c, int64_t h, int64_t w,
+                     const ts_net_desc* model_net, int64_t n_act, const float* grad, const float* sums2, int64_t B_total,
+                     double forward_loss_weight, double lr_scale, int32_t optim_kind, double lr, double beta1, double beta2, double eps,
+                     double weight_decay, double rms_alpha, double rms_momentum, int32_t rms_centered, double max_grad_norm,
+                     float* stats_out3, ts_stream_t stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * TD3 / DDPG: ContinuousActorDeterministic (utils/net/continuous.py:26-85) + the SAC critics,

@@ -4,7 +4,8 @@ The sub-modules are imported where they are used (`tianshou_amd.integration`, `t
 lazily, so importing the package loads neither torch nor the library."""
 
 _LAZY = {"make_hip_gail": "integration", "GAILConfig": "gail", "GAILDiscriminator": "gail",
-         "make_hip_icm": "integration", "ICMConfig": "icm", "ICMEngine": "icm"}
+         "make_hip_icm": "integration", "ICMConfig": "icm", "ICMEngine": "icm",
+         "make_hip_icm_cnn": "integration", "ICMCnnEngine": "icm_cnn"}
 __all__ = sorted(_LAZY)
 
 

@@ -504,3 +504,323 @@ int ts_icm_update(ts_workspace* ws, float* params, float* state_m, float* state_
 }
 
 }  // extern "C"
+
+// ---- ICM on the Atari trunk (ts_icm_cnn_*) ------------------------------------------------------------------------------------
+// The feature net is DQNet(features_only=True).net (atari_network.py: three convolutions, a ReLU behind EACH, Flatten) on NHWC
+// frames; phi = conv3's output [2B, OH3, OW3, 64] read as [2B, F] -- the NHWC flatten, F a multiple of 64, no padding columns.
+// The forward / inverse models, the pack / loss / reward kernels and the model chains' reverse pass are the ones above.  New
+// here: the frame stack (bytes, no float32 copy), the MASKED merge of the upstream feature gradient (phi carries a ReLU, the MLP
+// feature net's output does not) and the chunk accumulation: a rollout is walked in chunks of B rows whose gradients and loss
+// sums are added onto the caller's accumulators in chunk order, so one optimizer step sees the whole batch (icm.py:90-109).
+namespace {
+
+struct IcmCnn {
+    ts::ConvGeom cv[3];           // over 2B rows
+    int64_t coff[4];
+    Chain fwd, inv;               // over B rows
+    int c, h, w, A, F, Ap, KF, KI;
+    int64_t P;
+};
+
+int make_icm_cnn(int64_t c, int64_t h, int64_t w, const ts_net_desc* mn, int64_t n_act, int64_t B, const char* who, IcmCnn* m) {
+    TS_REQUIRE(mn != nullptr, TS_ERR_INVALID_ARG, "%s: the model descriptor is NULL", who);
+    TS_REQUIRE(c >= 1 && c <= 4096 && h >= 1 && h <= 16384 && w >= 1 && w <= 16384 && n_act >= 1 && mn->n_hidden >= 0 &&
+                   mn->n_hidden <= TS_NET_MAX_HIDDEN, TS_ERR_INVALID_ARG,
+               "%s: c in [1, 4096], h and w in [1, 16384], n_act >= 1, 0 .. %d hidden layers", who, TS_NET_MAX_HIDDEN);
+    TS_REQUIRE(n_act <= TS_ICM_MAX_ACTIONS, TS_ERR_UNSUPPORTED, "%s: at most %d actions (got %lld)", who, TS_ICM_MAX_ACTIONS,
+               (long long)n_act);
+    TS_REQUIRE(mn->activation == TS_NET_ACT_RELU, TS_ERR_UNSUPPORTED, "%s: the forward and the inverse model use ReLU", who);
+    TS_REQUIRE(mn->flags == 0, TS_ERR_UNSUPPORTED, "%s: layer norm / conditioned sigma are not part of an ICM model", who);
+    for (int i = 0; i < mn->n_hidden; ++i)
+        TS_REQUIRE(mn->hidden[i] >= 1 && mn->hidden[i] <= 1024, TS_ERR_INVALID_ARG, "%s: hidden widths must be in [1, 1024]", who);
+    TS_REQUIRE(B >= 1 && B <= (int64_t)1 << 29, TS_ERR_INVALID_ARG, "%s: 1 <= B <= 2^29", who);
+    static const int oc[3] = {32, 64, 64}, ks[3] = {8, 4, 3}, st[3] = {4, 2, 1};
+    int ic = (int)c, ih = (int)h, iw = (int)w;
+    int64_t o = 0;
+    for (int i = 0; i < 3; ++i) {
+        TS_REQUIRE(ih >= ks[i] && iw >= ks[i], TS_ERR_INVALID_ARG,
+                   "%s: a %lld x %lld frame is too small for the conv stack (layer %d sees %d x %d, kernel %d)", who, (long long)h,
+                   (long long)w, i + 1, ih, iw, ks[i]);
+        m->cv[i] = ts::ConvGeom{(int)(2 * B), ih, iw, ic, ks[i], ks[i], st[i], (ih - ks[i]) / st[i] + 1, (iw - ks[i]) / st[i] + 1, oc[i]};
+        m->coff[i] = o;
+        o += m->cv[i].param_elems();
+        ic = oc[i]; ih = m->cv[i].OH; iw = m->cv[i].OW;
+    }
+    m->coff[3] = o;
+    // (what ts_conv.hip's geometry check asks of conv1; conv2 / conv3 have 32 / 64 input channels)
+    TS_REQUIRE((w * c) % 4 == 0, TS_ERR_INVALID_ARG, "%s: w x c = %lld must be a multiple of 4 (the conv layer's 16-byte runs)", who,
+               (long long)(w * c));
+    TS_REQUIRE(2 * B * h * w * c < ((int64_t)1 << 31) && 2 * B * m->cv[0].OH * m->cv[0].OW * 32 < ((int64_t)1 << 31), TS_ERR_INVALID_ARG,
+               "%s: 2 B x the frame (%lld values) and 2 B x conv1's output (%lld) must stay below 2^31 elements (split the batch)", who,
+               (long long)(h * w * c), (long long)m->cv[0].OH * m->cv[0].OW * 32);
+    m->c = (int)c; m->h = (int)h; m->w = (int)w; m->A = (int)n_act;
+    m->F = 64 * ih * iw;
+    make_chain((int)B, m->F + n_act, mn->hidden, mn->n_hidden, m->F, TS_NET_ACT_RELU, o, &m->fwd);
+    make_chain((int)B, 2 * (int64_t)m->F, mn->hidden, mn->n_hidden, n_act, TS_NET_ACT_RELU, m->fwd.off[m->fwd.L], &m->inv);
+    m->KF = m->fwd.width[0]; m->KI = m->inv.width[0]; m->Ap = m->inv.width[m->inv.L];
+    m->P = m->inv.off[m->inv.L];
+    return TS_OK;
+}
+
+// out = [a; b], n vector elements each (V = 16 or 4 bytes): the two frame blocks as ONE 2B-row operand, bytes as they are
+template <typename V>
+__global__ __launch_bounds__(256) void icm_cnn_stack_kernel(const V* __restrict__ a, const V* __restrict__ b, int64_t n, V* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = a[i];
+    else if (i < 2 * n) out[i] = b[i - n];
+}
+
+// The upstream gradient of the stacked feature pass, [2B, F], four columns per thread: d_phi1 = dxf[:, :F] + dxi[:, :F], d_phi2 =
+// dxi[:, F:2F] - d_p2h, both times (phi > 0): phi is conv3's output AFTER its ReLU (torch's threshold_backward tests the output).
+__global__ __launch_bounds__(256) void icm_cnn_merge_kernel(const float* __restrict__ dxf, int KF, const float* __restrict__ dxi, int KI,
+                                                            const float* __restrict__ d_p2h, const float* __restrict__ phi, int64_t B,
+                                                            int F, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int q = F / 4;
+    if (i >= 2 * B * q) return;
+    const int64_t r = i / q;
+    const int j = 4 * (int)(i - r * q);
+    float4 v;
+    if (r < B) {
+        const float4 a = *reinterpret_cast<const float4*>(dxf + r * KF + j), b = *reinterpret_cast<const float4*>(dxi + r * KI + j);
+        v = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+    } else {
+        const float4 a = *reinterpret_cast<const float4*>(dxi + (r - B) * KI + F + j);
+        const float4 b = *reinterpret_cast<const float4*>(d_p2h + (r - B) * F + j);
+        v = make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
+    }
+    const float4 p = *reinterpret_cast<const float4*>(phi + r * F + j);
+    v.x = p.x > 0.f ? v.x : 0.f; v.y = p.y > 0.f ? v.y : 0.f; v.z = p.z > 0.f ? v.z : 0.f; v.w = p.w > 0.f ? v.w : 0.f;
+    *reinterpret_cast<float4*>(out + r * F + j) = v;
+}
+
+// acc += g (n a multiple of 4): one chunk's gradient onto the accumulator; every element is one thread's, chunks arrive in order
+__global__ __launch_bounds__(256) void icm_cnn_accum_kernel(float* __restrict__ acc, const float* __restrict__ g, int64_t n4) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    float4 a = reinterpret_cast<float4*>(acc)[i];
+    const float4 b = reinterpret_cast<const float4*>(g)[i];
+    a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+    reinterpret_cast<float4*>(acc)[i] = a;
+}
+
+// sums2 = {sum mse, sum ce} of this chunk's loss workgroups (the order of icm_loss_finish_kernel), overwriting or added onto it
+__global__ __launch_bounds__(256) void icm_cnn_sums_kernel(const float* __restrict__ partial, int n_blocks, int accumulate,
+                                                           float* __restrict__ sums2) {
+    __shared__ float red4[4];
+    float v0 = 0.f, v1 = 0.f;
+    for (int i = threadIdx.x; i < n_blocks; i += 256) { v0 += partial[2 * i]; v1 += partial[2 * i + 1]; }
+    const float t0 = block_sum256(v0, red4);
+    __syncthreads();
+    const float t1 = block_sum256(v1, red4);
+    if (threadIdx.x == 0) {
+        sums2[0] = accumulate ? sums2[0] + t0 : t0;
+        sums2[1] = accumulate ? sums2[1] + t1 : t1;
+    }
+}
+
+struct FwdCnn {
+    void* x0;
+    float* a[3];
+    float *xf, *xi, *split;
+    ActC aw, ai;
+    const float *phi, *p2h, *logits;
+};
+
+size_t cnn_split_floats(const IcmCnn& m, bool inverse) {
+    size_t s = std::max(split_floats(m.fwd), inverse ? split_floats(m.inv) : 4);
+    for (int i = 0; i < 3; ++i) { const int ns = ts::conv_fwd_splits(m.cv[i]); if (ns > 1) s = std::max(s, (size_t)ns * m.cv[i].out_elems()); }
+    return s;
+}
+
+size_t cnn_fwd_bytes(const IcmCnn& m, int64_t B, bool inverse) {
+    size_t s = al(4 * (size_t)m.cv[0].in_elems());
+    for (int i = 0; i < 3; ++i) s += al(4 * (size_t)m.cv[i].out_elems());
+    return s + al(4 * B * m.KF) + act_bytes(m.fwd, B) + (inverse ? al(4 * B * m.KI) + act_bytes(m.inv, B) : 0) +
+           al(4 * cnn_split_floats(m, inverse));
+}
+
+int cnn_check_frames(const void* obs, const void* obs_next, const char* who) {
+    TS_REQUIRE(((uintptr_t)obs | (uintptr_t)obs_next) % 4 == 0, TS_ERR_INVALID_ARG, "%s: the frame blocks must be 4-byte aligned", who);
+    return TS_OK;
+}
+
+// stack -> conv1..3 over 2B rows -> pack -> forward model (-> inverse model)
+int icm_cnn_forward_pass(hipStream_t s, ts_workspace* ws, const IcmCnn& m, const float* params, const void* obs, bool obs_u8,
+                         const int64_t* act, const void* obs_next, int64_t B, bool inverse, Carve& c, FwdCnn* f) {
+    f->x0 = c.f((size_t)m.cv[0].in_elems());
+    for (int i = 0; i < 3; ++i) f->a[i] = c.f((size_t)m.cv[i].out_elems());
+    f->xf = c.f(B * m.KF);
+    f->aw = take_act(c, m.fwd, B);
+    f->xi = nullptr;
+    if (inverse) { f->xi = c.f(B * m.KI); f->ai = take_act(c, m.inv, B); }
+    f->split = c.f(cnn_split_floats(m, inverse));
+    const int64_t nb = B * m.h * m.w * m.c * (obs_u8 ? 1 : 4);       // bytes of one block: a multiple of 4 (w c is)
+    if ((((uintptr_t)obs | (uintptr_t)obs_next) % 16 == 0) && nb % 16 == 0)
+        hipLaunchKernelGGL(icm_cnn_stack_kernel<uint4>, dim3(blocks_of(2 * (nb / 16))), dim3(256), 0, s, static_cast<const uint4*>(obs),
+                           static_cast<const uint4*>(obs_next), nb / 16, static_cast<uint4*>(f->x0));
+    else
+        hipLaunchKernelGGL(icm_cnn_stack_kernel<uint32_t>, dim3(blocks_of(2 * (nb / 4))), dim3(256), 0, s, static_cast<const uint32_t*>(obs),
+                           static_cast<const uint32_t*>(obs_next), nb / 4, static_cast<uint32_t*>(f->x0));
+    TS_LAUNCH_CHECK();
+    const float* x = static_cast<const float*>(f->x0);
+    for (int i = 0; i < 3; ++i) {
+        if (int rc = ts::conv_forward(s, m.cv[i], x, params + m.coff[i], f->a[i], true, f->split, ws, i == 0 && obs_u8)) return rc;
+        x = f->a[i];
+    }
+    f->phi = f->a[2];
+    hipLaunchKernelGGL(icm_pack_kernel, dim3(blocks_of(B * (m.KF + (inverse ? m.KI : 0)))), dim3(256), 0, s, f->phi, act, B, m.F, m.F,
+                       m.A, m.KF, m.KI, f->xf, f->xi);
+    TS_LAUNCH_CHECK();
+    if (int rc = chain_forward(s, ws, m.fwd, params, f->xf, f->aw, f->split, B)) return rc;
+    f->p2h = f->aw.h[m.fwd.L - 1];
+    f->logits = nullptr;
+    if (inverse) {
+        if (int rc = chain_forward(s, ws, m.inv, params, f->xi, f->ai, f->split, B)) return rc;
+        f->logits = f->ai.h[m.inv.L - 1];
+    }
+    return TS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ts_icm_cnn_layout(int64_t c, int64_t h, int64_t w, const ts_net_desc* model_net, int64_t n_act, int64_t* h_out12) {
+    TS_REQUIRE(h_out12 != nullptr, TS_ERR_INVALID_ARG, "ts_icm_cnn_layout: output is NULL");
+    IcmCnn m;
+    if (int rc = make_icm_cnn(c, h, w, model_net, n_act, 1, "ts_icm_cnn_layout", &m)) return rc;
+    h_out12[0] = m.P; h_out12[1] = m.F;
+    for (int i = 0; i < 3; ++i) { h_out12[2 + 2 * i] = m.coff[i]; h_out12[3 + 2 * i] = m.coff[i + 1] - m.coff[i]; }
+    h_out12[8] = m.fwd.off[0]; h_out12[9] = m.fwd.off[m.fwd.L] - m.fwd.off[0];
+    h_out12[10] = m.inv.off[0]; h_out12[11] = m.inv.off[m.inv.L] - m.inv.off[0];
+    return TS_OK;
+}
+
+int ts_icm_cnn_forward(ts_workspace* ws, const float* params, int64_t c, int64_t h, int64_t w, const ts_net_desc* model_net, int64_t n_act,
+                       const void* obs_nhwc, int obs_u8, const int64_t* act, const void* obs_next_nhwc, int64_t B, float* mse_out,
+                       float* act_hat_out, ts_stream_t stream) {
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_icm_cnn_forward: workspace is NULL");
+    TS_REQUIRE(params && obs_nhwc && act && obs_next_nhwc && mse_out, TS_ERR_INVALID_ARG, "ts_icm_cnn_forward: NULL argument");
+    IcmCnn m;
+    if (int rc = make_icm_cnn(c, h, w, model_net, n_act, B, "ts_icm_cnn_forward", &m)) return rc;
+    if (int rc = cnn_check_frames(obs_nhwc, obs_next_nhwc, "ts_icm_cnn_forward")) return rc;
+    const bool inverse = act_hat_out != nullptr;
+    const int n_blocks = (int)ts::ceil_div(B, LOSS_ROWS);
+    if (int rc = ts::ws_reserve(ws, cnn_fwd_bytes(m, B, inverse) + al(8 * (size_t)n_blocks) + 8192)) return rc;
+    hipStream_t s = ts::as_stream(stream);
+    Carve cv{static_cast<char*>(ws->base)};
+    FwdCnn f;
+    if (int rc = icm_cnn_forward_pass(s, ws, m, params, obs_nhwc, obs_u8 != 0, act, obs_next_nhwc, B, inverse, cv, &f)) return rc;
+    float* partial = cv.f(2 * (size_t)n_blocks);
+    hipLaunchKernelGGL(icm_loss_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, f.p2h, m.F, f.phi + B * m.F, m.F, (const float*)nullptr, 0,
+                       act, B, m.F, m.A, 0.f, 0.f, mse_out, (float*)nullptr, 0, (float*)nullptr, 0, partial);
+    if (inverse) hipLaunchKernelGGL(icm_unpad_kernel, dim3(blocks_of(B * m.A)), dim3(256), 0, s, f.logits, B, m.A, m.Ap, act_hat_out);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+int ts_icm_cnn_reward(ts_workspace* ws, const float* params, int64_t c, int64_t h, int64_t w, const ts_net_desc* model_net, int64_t n_act,
+                      const void* obs_nhwc, int obs_u8, const int64_t* act, const void* obs_next_nhwc, int64_t B, const double* rew,
+                      double reward_scale, double* rew_out, float* mse_out, ts_stream_t stream) {
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_icm_cnn_reward: workspace is NULL");
+    TS_REQUIRE(params && obs_nhwc && act && obs_next_nhwc && rew && rew_out, TS_ERR_INVALID_ARG, "ts_icm_cnn_reward: NULL argument");
+    IcmCnn m;
+    if (int rc = make_icm_cnn(c, h, w, model_net, n_act, B, "ts_icm_cnn_reward", &m)) return rc;
+    if (int rc = cnn_check_frames(obs_nhwc, obs_next_nhwc, "ts_icm_cnn_reward")) return rc;
+    const int n_blocks = (int)ts::ceil_div(B, LOSS_ROWS);
+    if (int rc = ts::ws_reserve(ws, cnn_fwd_bytes(m, B, false) + al(8 * (size_t)n_blocks) + al(4 * B) + 8192)) return rc;
+    hipStream_t s = ts::as_stream(stream);
+    Carve cv{static_cast<char*>(ws->base)};
+    FwdCnn f;
+    if (int rc = icm_cnn_forward_pass(s, ws, m, params, obs_nhwc, obs_u8 != 0, act, obs_next_nhwc, B, false, cv, &f)) return rc;
+    float* partial = cv.f(2 * (size_t)n_blocks);
+    float* mse = mse_out ? mse_out : cv.f(B);
+    hipLaunchKernelGGL(icm_loss_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, f.p2h, m.F, f.phi + B * m.F, m.F, (const float*)nullptr, 0,
+                       act, B, m.F, m.A, 0.f, 0.f, mse, (float*)nullptr, 0, (float*)nullptr, 0, partial);
+    hipLaunchKernelGGL(icm_reward_kernel, dim3(blocks_of(B)), dim3(256), 0, s, rew, mse, B, (float)reward_scale, rew_out);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+int ts_icm_cnn_grad(ts_workspace* ws, const float* params, int64_t c, int64_t h, int64_t w, const ts_net_desc* model_net, int64_t n_act,
+                    const void* obs_nhwc, int obs_u8, const int64_t* act, const void* obs_next_nhwc, int64_t B, int64_t B_total,
+                    double forward_loss_weight, double lr_scale, int accumulate, float* grad, float* sums2, ts_stream_t stream) {
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_icm_cnn_grad: workspace is NULL");
+    TS_REQUIRE(params && obs_nhwc && act && obs_next_nhwc && grad && sums2, TS_ERR_INVALID_ARG, "ts_icm_cnn_grad: NULL argument");
+    TS_REQUIRE(B >= 1 && B <= B_total, TS_ERR_INVALID_ARG, "ts_icm_cnn_grad: 1 <= B <= B_total (got %lld, %lld)", (long long)B,
+               (long long)B_total);
+    IcmCnn m;
+    if (int rc = make_icm_cnn(c, h, w, model_net, n_act, B, "ts_icm_cnn_grad", &m)) return rc;
+    if (int rc = cnn_check_frames(obs_nhwc, obs_next_nhwc, "ts_icm_cnn_grad")) return rc;
+    const int n_blocks = (int)ts::ceil_div(B, LOSS_ROWS);
+    const size_t sl = std::max(slab_floats(m.fwd), slab_floats(m.inv));
+    const size_t dh = std::max(hidden_grad_floats(m.fwd, B), hidden_grad_floats(m.inv, B));
+    size_t conv_sl[3], bytes = cnn_fwd_bytes(m, B, true) + al(8 * (size_t)n_blocks) + al(4 * B * m.F) + al(4 * B * m.Ap) + al(4 * B * m.KF) +
+                               al(4 * B * m.KI) + 2 * al(4 * dh) + al(4 * sl) + (accumulate ? al(4 * m.P) : 0) + 16384;
+    for (int i = 0; i < 3; ++i) {
+        conv_sl[i] = (size_t)ts::conv_wgrad_splits(m.cv[i]) * m.cv[i].param_elems();
+        bytes += al(4 * conv_sl[i]) + al(4 * (size_t)m.cv[i].out_elems());
+    }
+    if (int rc = ts::ws_reserve(ws, bytes)) return rc;
+    hipStream_t s = ts::as_stream(stream);
+    Carve cv{static_cast<char*>(ws->base)};
+    FwdCnn f;
+    if (int rc = icm_cnn_forward_pass(s, ws, m, params, obs_nhwc, obs_u8 != 0, act, obs_next_nhwc, B, true, cv, &f)) return rc;
+    float* partial = cv.f(2 * (size_t)n_blocks);
+    float* d_p2h = cv.f(B * m.F);
+    float* d_logits = cv.f(B * m.Ap);
+    float* dxf = cv.f(B * m.KF);
+    float* dxi = cv.f(B * m.KI);
+    float* dha = cv.f(dh);
+    float* dhb = cv.f(dh);
+    float* slabs = cv.f(sl);
+    float* g = accumulate ? cv.f(m.P) : grad;            // this chunk's gradient
+    float *dy[3], *cslab[3];
+    for (int i = 0; i < 3; ++i) { dy[i] = cv.f((size_t)m.cv[i].out_elems()); cslab[i] = cv.f(conv_sl[i]); }
+    const double wt = forward_loss_weight;
+    hipLaunchKernelGGL(icm_loss_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, f.p2h, m.F, f.phi + B * m.F, m.F, f.logits, m.Ap, act, B,
+                       m.F, m.A, (float)(wt * lr_scale / (double)B_total), (float)((1.0 - wt) * lr_scale / (double)B_total), (float*)nullptr,
+                       d_p2h, m.F, d_logits, m.Ap, partial);
+    hipLaunchKernelGGL(icm_cnn_sums_kernel, dim3(1), dim3(256), 0, s, partial, n_blocks, accumulate, sums2);
+    TS_LAUNCH_CHECK();
+    if (int rc = chain_backward(s, ws, m.fwd, params, f.xf, f.aw, d_p2h, g, dha, dhb, slabs, B, dxf, m.F)) return rc;
+    if (int rc = chain_backward(s, ws, m.inv, params, f.xi, f.ai, d_logits, g, dha, dhb, slabs, B, dxi, 2 * m.F)) return rc;
+    hipLaunchKernelGGL(icm_cnn_merge_kernel, dim3(blocks_of(2 * B * (m.F / 4))), dim3(256), 0, s, dxf, m.KF, dxi, m.KI, d_p2h, f.phi, B, m.F,
+                       dy[2]);
+    TS_LAUNCH_CHECK();
+    const float* x[3] = {static_cast<const float*>(f.x0), f.a[0], f.a[1]};
+    const float* wb[3] = {params + m.coff[0], params + m.coff[1], params + m.coff[2]};
+    float* gl[3] = {g + m.coff[0], g + m.coff[1], g + m.coff[2]};
+    if (int rc = ts::chain_backward(s, ws, 3, m.cv, x, dy, wb, cslab, gl, obs_u8 != 0)) return rc;
+    if (accumulate) {
+        hipLaunchKernelGGL(icm_cnn_accum_kernel, dim3(blocks_of(m.P / 4)), dim3(256), 0, s, grad, g, m.P / 4);
+        TS_LAUNCH_CHECK();
+    }
+    return TS_OK;
+}
+
+int ts_icm_cnn_apply(ts_workspace* ws, float* params, float* state_m, float* state_v, int64_t optim_step, int64_t c, int64_t h, int64_t w,
+                     const ts_net_desc* model_net, int64_t n_act, const float* grad, const float* sums2, int64_t B_total,
+                     double forward_loss_weight, double lr_scale, int32_t optim_kind, double lr, double beta1, double beta2, double eps,
+                     double weight_decay, double rms_alpha, double rms_momentum, int32_t rms_centered, double max_grad_norm,
+                     float* stats_out3, ts_stream_t stream) {
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_icm_cnn_apply: workspace is NULL");
+    TS_REQUIRE(params && state_m && state_v && grad && sums2 && stats_out3, TS_ERR_INVALID_ARG, "ts_icm_cnn_apply: NULL argument");
+    TS_REQUIRE(B_total >= 1 && optim_step >= 1 && (optim_kind == TS_OPT_ADAM || optim_kind == TS_OPT_RMSPROP), TS_ERR_INVALID_ARG,
+               "ts_icm_cnn_apply: B_total >= 1, optim_step >= 1, optim_kind Adam or RMSprop");
+    IcmCnn m;
+    if (int rc = make_icm_cnn(c, h, w, model_net, n_act, 1, "ts_icm_cnn_apply", &m)) return rc;
+    if (int rc = ts::ws_reserve(ws, al(4 * 1024) + 4096)) return rc;
+    hipStream_t s = ts::as_stream(stream);
+    hipLaunchKernelGGL(icm_loss_finish_kernel, dim3(1), dim3(256), 0, s, sums2, 1, (float)B_total, (float)forward_loss_weight, (float)lr_scale,
+                       stats_out3);
+    TS_LAUNCH_CHECK();
+    if (lr < 0.0) return TS_OK;
+    ts::OptimDesc o;
+    o.kind = optim_kind; o.centered = rms_centered; o.weight_decay = weight_decay; o.alpha = rms_alpha; o.momentum = rms_momentum;
+    return ts::optim_step(s, o, params, state_m, state_v, grad, m.P, optim_step, lr, beta1, beta2, eps, max_grad_norm,
+                          static_cast<float*>(ws->base));
+}
+
+}  // extern "C"

@@ -2761,12 +2761,19 @@ def make_hip_ppo_cnn(algo: str = "ppo", ref=None):
 
         _hip_write_back = _on_write_back
 
+        def _hip_rewards(self, eng, m):
+            """The rewards the returns are computed from, in sample_indices(0) order: None = the mirror's column, read in place
+            (a reward-supplying wrapper -- HipICMCnn -- leaves its float64 device tensor in `_hip_rew_source` for one call)."""
+            return self.__dict__.get("_hip_rew_source")
+
         def _preprocess_batch(self, batch, buffer, indices):
             _require_gpu(self._hip_device, "HipPPOCnn")
             c, h, w, stack = self._layout(buffer)
             eng = self._engine(c, h, w)
             m = _mirror(self, buffer, self._hip_device)
-            pre = eng.preprocess(m, m.obs, m.act, stack, obs_next_frames=m.obs_next)
+            rew = self._hip_rewards(eng, m)
+            kw = {} if rew is None else {"rew": rew}
+            pre = eng.preprocess(m, m.obs, m.act, stack, obs_next_frames=m.obs_next, **kw)
             self._hip_pre, self._hip_stack = pre, stack
             batch.v_s, batch.returns, batch.adv, batch.logp_old = pre["v_s"], pre["returns"], pre["adv"], pre["logp_old"]
             return batch
@@ -3010,6 +3017,115 @@ def make_hip_icm(ref=None):
             return ICMTrainingStats(original_stats, icm_loss=loss, icm_forward_loss=fwd, icm_inverse_loss=inv)
 
     return HipICM
+
+
+# ---------------------------------------------------------------------------------------------------
+# ICM around HipPPOCnn / HipA2CCnn: the examples/atari/atari_ppo.py:136-160 pairing (--icm-lr-scale)
+# ---------------------------------------------------------------------------------------------------
+def make_hip_icm_cnn(ref=None):
+    """Returns HipICMCnn(ICMOnPolicyWrapper) with the curiosity model of atari_ppo.py on the engine (tianshou_amd/icm_cnn.py).
+    `wrapped_algorithm` must be a HipPPOCnn / HipA2CCnn; `model` an IntrinsicCuriosityModule whose feature net is
+    DQNet(c, h, w, action_shape, features_only=True).net (`icm_cnn.describe_module` raises NotImplementedError naming anything
+    else); Adam or RMSprop.  The hooks are HipICM's (see `make_hip_icm`), over uint8 frames: `_preprocess_batch` walks
+    sample_indices(0) chunk by chunk, gathering (and frame-stacking) obs and obs_next from the wrapped algorithm's mirror --
+    obs_next from the stored column or, without one, obs at next(index) -- and hands the augmented float64 rewards to the
+    wrapped preprocessing; `_wrapper_update_with_batch` gathers the same chunks again for the one optimizer step
+    (ts_icm_cnn_grad per chunk, ts_icm_cnn_apply).  The frames of a rollout are never all resident as NHWC batches.
+    Only the on-policy wrapper exists: the reference's off-policy n-step return reads buffer.rew, not batch.rew
+    (algorithm_base.py:801-802), so ICMOffPolicyWrapper's intrinsic reward never reaches a target.
+    `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    ICMTrainingStats = _ref(ref, "tianshou.algorithm.modelbased.icm", "ICMTrainingStats")
+    HipICM = make_hip_icm(ref)
+
+    from . import icm_cnn as ICC
+    from .dqn import gather_obs_nhwc
+
+    class HipICMCnn(HipICM):
+        def __init__(self, *args, **kwargs):
+            super(HipICM, self).__init__(*args, **kwargs)                   # (HipICM's own checks are for the vector pairing)
+            w = self.wrapped_algorithm
+            if type(w).__name__ not in ("HipPPOCnn", "HipA2CCnn") or not hasattr(w, "_hip_rewards"):
+                raise NotImplementedError(f"HipICMCnn: the wrapped algorithm must be a HipPPOCnn or a HipA2CCnn "
+                                          f"(found {type(w).__name__})")
+            self._hip_device = w._hip_device
+            d = ICC.describe_module(self.model)           # raises NotImplementedError naming what was found; the frame size comes with the buffer
+            self._hip_icm = {k: v for k, v in d.items() if k != "tensors"}
+            optimizer_fields(self.optim._optim)
+            self._hip_rows = self._hip_orig_rew = self._hip_frame = None
+            self._hip_engine = None
+            self._hip_glue_init()
+
+        def _hip_dims(self, eng=None):
+            frame = (eng.c, eng.h, eng.w) if eng is not None else self._hip_frame
+            if frame is None:
+                raise RuntimeError("HipICMCnn: the frame size is known with the first buffer (no update has run yet)")
+            return (*frame, self._hip_icm["n_act"], self._hip_icm["model_hidden"])
+
+        def _hip_parts(self, eng=None):
+            dims, dev = self._hip_dims(eng), self._hip_device
+            params = ICC.describe_module(self.model, *dims[:3])["tensors"]
+            return [_OnPart("params", ("state_m", "state_v"), self.optim, params, lambda t: ICC.flat_from_torch(t, *dims, dev),
+                            lambda f: ICC.flat_to_torch(f, *dims), step="optim_step")]
+
+        def _engine(self):
+            if self._hip_engine is None:
+                (part,), dims = self._hip_parts(), self._hip_dims()
+                self._hip_engine = _on_load(self, ICC.ICMCnnEngine(*dims, part.flat(), self._hip_config()))
+            return self._hip_engine
+
+        def _hip_chunks(self, m, idx, stack):
+            """rows(lo, hi) -> (obs, act, obs_next) of the transitions idx[lo:hi] as uint8 NHWC batches, gathered on demand."""
+            act = m.act[idx].reshape(-1)
+
+            def rows(lo, hi):
+                i = idx[lo:hi]
+                nxt = gather_obs_nhwc(m.obs_next, m, i, stack, as_u8=True) if m.obs_next is not None else \
+                    gather_obs_nhwc(m.obs, m, m.next(i), stack, as_u8=True)         # buffer_base.py:622-626
+                return gather_obs_nhwc(m.obs, m, i, stack, as_u8=True), act[lo:hi], nxt
+
+            return rows
+
+        def _preprocess_batch(self, batch, buffer, indices):
+            """icm.py:236-243: the intrinsic reward with the model's current parameters, then the wrapped preprocessing."""
+            _require_gpu(self._hip_device, "HipICMCnn")
+            w = self.wrapped_algorithm
+            c, h, wd, stack = w._layout(buffer)
+            if self._hip_frame is not None and self._hip_frame != (c, h, wd):
+                self._hip_engine = None                      # (another frame size: another layout)
+            self._hip_frame = (c, h, wd)
+            if c != self._hip_icm["c"]:
+                raise NotImplementedError(f"HipICMCnn: the feature net takes {self._hip_icm['c']} channels, the buffer's frames have {c}")
+            eng = self._engine()
+            self._hip_refresh_lr()
+            m = _mirror(w, buffer, self._hip_device)
+            idx = m.sample_indices(0)
+            n = idx.numel()
+            rows = self._hip_rows = (self._hip_chunks(m, idx, stack), n)
+            base = m.rew[idx]
+            rew = torch.empty(n, dtype=torch.float64, device=self._hip_device)
+            for lo in range(0, n, ICC.DEFAULT_CHUNK):
+                hi = min(lo + ICC.DEFAULT_CHUNK, n)
+                rew[lo:hi] = eng.reward(*rows[0](lo, hi), base[lo:hi])
+            self._hip_orig_rew = getattr(batch, "rew", None)
+            w.__dict__["_hip_rew_source"] = rew              # the seam: HipPPOCnn._hip_rewards
+            try:
+                batch = w._preprocess_batch(batch, buffer, indices)
+            finally:
+                w.__dict__["_hip_rew_source"] = None
+            batch.rew = rew
+            return batch
+
+        def _wrapper_update_with_batch(self, batch, batch_size, repeat, original_stats):
+            """icm.py:90-109, after the wrapped update, on the rows of `_preprocess_batch` (the model has not changed since)."""
+            self._hip_refresh_lr()
+            eng = self._engine()
+            rows, n = self._hip_rows
+            stats = eng.update(rows, n=n)
+            self._hip_write_back()
+            loss, fwd, inv = (float(x) for x in stats.cpu().numpy())         # the one read of the three statistics
+            return ICMTrainingStats(original_stats, icm_loss=loss, icm_forward_loss=fwd, icm_inverse_loss=inv)
+
+    return HipICMCnn
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -177,22 +177,24 @@ class CnnPPOEngine:
         return v_s, v_next, logp
 
     def preprocess(self, buffer: DeviceReplayBuffer, frames: torch.Tensor, act: torch.Tensor, stack_num: int,
-                   obs_next_frames: torch.Tensor | None = None, chunk: int = 65536) -> dict:
+                   obs_next_frames: torch.Tensor | None = None, chunk: int = 65536, rew=None) -> dict:
         """Whole-buffer pass in sample_indices(0) order: V(s), V(s'), log pi_old(a|s) (one trunk pass per
-        observation), GAE, optional return scaling (a2c.py:115-153, ppo.py:146-162)."""
+        observation), GAE, optional return scaling (a2c.py:115-153, ppo.py:146-162).
+        `rew`: float64 rewards in sample_indices(0) order replacing the buffer's column (None: the column); kept in the
+        result so that `recompute` reads the same rewards (ppo.py:174-178 reads the augmented batch.rew again)."""
         idx = buffer.sample_indices(0)
         act_b = act[idx]
         v_s, v_next, logp_old = self._values(buffer, frames, idx, act_b, stack_num, obs_next_frames, chunk)
-        out = gae_and_return_scaling(self, buffer, idx, v_s, v_next)
+        out = gae_and_return_scaling(self, buffer, idx, v_s, v_next, rew)
         return {"indices": idx, "act": act_b, "v_s": v_s, "returns": out["returns"], "adv": out["adv"],
-                "logp_old": logp_old, "obs_next_frames": obs_next_frames, "chunk": chunk}
+                "logp_old": logp_old, "obs_next_frames": obs_next_frames, "chunk": chunk, "rew": rew}
 
     def recompute(self, buffer: DeviceReplayBuffer, frames: torch.Tensor, pre: dict, stack_num: int) -> None:
         """recompute_advantage (ppo.py:174-178): `_add_returns_and_advantages` again with the current parameters -- V(s),
         V(s'), GAE, return scaling incl. another RunningMeanStd update (a2c.py:148); log pi_old stays.  Updates `pre`."""
         v_s, v_next, _ = self._values(buffer, frames, pre["indices"], None, stack_num, pre.get("obs_next_frames"),
                                       pre.get("chunk", 65536))
-        out = gae_and_return_scaling(self, buffer, pre["indices"], v_s, v_next)
+        out = gae_and_return_scaling(self, buffer, pre["indices"], v_s, v_next, pre.get("rew"))
         pre["v_s"], pre["returns"], pre["adv"] = v_s, out["returns"], out["adv"]
 
     # -- one minibatch step ---------------------------------------------------------------------------------------
