@@ -507,6 +507,32 @@ int ts_conv_backward(ts_workspace* ws, const void* x, int x_u8, const float* wb,
  * Returns the previous mode.  Process-wide; not meant to be flipped while launches are being enqueued from other threads. */
 int ts_conv_set_generation(int mode);
 
+/* The fused three-layer MLP [K1 -> 256 -> 256 -> head_cols] (ReLU, ReLU, linear head) of the SAC-family engines as a
+ * layer-level call: h1 = relu(x W1 + b1), h2 = relu(h1 W2 + b2), out = h2 W3 + b3 for `nets` (1 .. 8) networks of one shape
+ * in ONE launch.  Every pointer argument is a HOST array of `nets` device pointers (as ts_gather_rows_multi takes its keys):
+ * x[k] float32[M, K1] (the same pointer for networks that share their input), wb_i[k] the layer matrices in the layout of
+ * ts_conv_forward ([K_i + 1, N_i], last row = bias), h1[k] / h2[k] float32[M, 256], out[k] float32[M, head_cols].  The arrays
+ * h1 / h2 are nullable as a whole (inference-only chain: the stores are skipped, `out` is the same bits).
+ * Shapes: K1 % 32 == 0, 32 <= K1 <= 1024, head_cols 32 or 64 (TS_ERR_UNSUPPORTED else); M >= 1.  ws (nullable) only
+ * carries the profiler scope. */
+int ts_mlp3_forward(ts_workspace* ws, int nets, const float* const* x, const float* const* wb1, const float* const* wb2,
+                    const float* const* wb3, float* const* h1, float* const* h2, float* const* out, int64_t M, int64_t K1,
+                    int64_t head_cols, ts_stream_t stream);
+/* The input gradients of the same chain in one launch: dh2 = (d_out W3^T) * (h2 > 0), dh1 = (dh2 W2^T) * (h1 > 0)
+ * (float32[M, 256] each) and, when the array dx is given (for all networks or for none), dx[k][:, col0:col1) = dh1 W1^T
+ * with row pitch K1: the 16-column tiles covering [col0, col1) are written, at most eight of them (TS_ERR_UNSUPPORTED
+ * beyond).  d_out[k] float32[M, head_cols]; h1 / h2 as ts_mlp3_forward wrote them. */
+int ts_mlp3_backward(ts_workspace* ws, int nets, const float* const* d_out, const float* const* wb1, const float* const* wb2,
+                     const float* const* wb3, const float* const* h1, const float* const* h2, float* const* dh1, float* const* dh2,
+                     float* const* dx, int64_t M, int64_t K1, int64_t head_cols, int64_t col0, int64_t col1, ts_stream_t stream);
+/* Kernel variant of the two calls above and of every engine built on them.  nw: 0 = automatic (eight waves per workgroup
+ * for one network, four for several while two such workgroups fit a CU's LDS), 4 / 8 = that many for every launch.
+ * rb: 0 = 16-row workgroups, 2 = 32-row eight-wave workgroups for launches of several networks that still fill 3/4 of
+ * the CUs with them (ignored while nw is forced).  Per output element the summation order depends on nw alone.  The
+ * environment variables TS_MLP_NW / TS_MLP_RB preset the two.  Returns the previous setting as 10 * nw + rb, or
+ * TS_ERR_INVALID_ARG (and changes nothing) for any other value.  Process-wide, with the caveat of ts_conv_set_generation. */
+int ts_mlp3_set_variant(int nw, int rb);
+
 /* ---------------------------------------------------------------------------------------------
  * DQN on NatureCNN (DQNet, tianshou/env/atari/atari_network.py:60-122)
  * ------------------------------------------------------------------------------------------- */

@@ -45,8 +45,8 @@ FUSED_HIDDEN = 256          # ts_mlp.hip:45    HID; mlp3_supported (:407) wants 
 K1_STEP, K1_MIN, K1_MAX = 32, 32, 1024      # ts_mlp.hip:407   K1 % 32 == 0 && K1 >= 32 && K1 <= 1024
 FUSED_DEPTH = 2             # ts_sac.hip:54    Mlp::three(): two ReLU hidden layers of one width
 HP = FUSED_HIDDEN + 4       # ts_mlp.hip:46    LDS pitch of a hidden activation row
-ROWS = 16                   # ts_mlp.hip:451   batch rows of a workgroup
-LDS4_MAX = 80 * 1024        # ts_mlp.hip:463   four-wave workgroups for nets > 1 only while lds4 <= 80 KB
+ROWS = 16                   # ts_mlp.hip:463   batch rows of a workgroup
+LDS4_MAX = 80 * 1024        # ts_mlp.hip:475   four-wave workgroups for nets > 1 only while lds4 <= 80 KB
 MAX_ENSEMBLE = 64           # ts_sac.hip:2341  E <= 64 (Act acts[64] :2371, loss_parts :2386); tianshou_amd/redq.py:93
 LOSS_STRIDE = 1024          # ts_sac.hip:1149, :1157, :1192   batch stride of redq_critic_loss_kernel / redq_actor_loss_kernel
 
@@ -66,7 +66,7 @@ def part_floats(nw: int, rows: int) -> int:
 
 
 def lds4_bytes(k1: int) -> int:
-    """ts_mlp.hip:462: sizeof(float) * (ROWS (K1 + 4) + 2 ROWS HP + part_floats(4, ROWS)) = 64 K1 + 50944."""
+    """ts_mlp.hip:474: sizeof(float) * (ROWS (K1 + 4) + 2 ROWS HP + part_floats(4, ROWS)) = 64 K1 + 50944."""
     return 4 * (ROWS * (k1 + 4) + 2 * ROWS * HP + part_floats(4, ROWS))
 
 
@@ -80,7 +80,7 @@ def fused_shape(hidden: int, kc: int, depth: int = 2) -> bool:
 
 
 def forward_kernel(nets: int, k1: int) -> str:
-    """mlp3_forward_nx (ts_mlp.hip:463): `four = nets > 1 && lds4 <= 80 KB`."""
+    """mlp3_forward_nx (ts_mlp.hip:475): `four = nets > 1 && lds4 <= 80 KB`."""
     return "four-wave" if nets > 1 and lds4_bytes(k1) <= LDS4_MAX else "eight-wave"
 
 

@@ -41,6 +41,49 @@ def test_argument_validation_without_gpu(lib):
     assert rc == _lib.TS_ERR_INVALID_ARG
     rc = lib.ts_segtree_setitem(None, None, ctypes.c_int64(6), None, None, 1, ctypes.c_int64(1), None)
     assert rc == _lib.TS_ERR_INVALID_ARG and b"power of two" in lib.ts_last_error()
+    # the layer-level entry points of the fused three-layer MLP: host arrays of (never dereferenced) device pointers
+    i64 = ctypes.c_int64
+    two = (ctypes.c_void_p * 2)(4096, 8192)
+    hole = (ctypes.c_void_p * 2)(4096, None)
+
+    def fwd(nets=2, x=two, wb1=two, out=two, M=17, K1=64, head=32):
+        return lib.ts_mlp3_forward(None, nets, x, wb1, two, two, None, None, out, i64(M), i64(K1), i64(head), None)
+
+    def bwd(nets=2, d_out=two, h1=two, dx=two, M=17, K1=64, head=32, col0=3, col1=20):
+        return lib.ts_mlp3_backward(None, nets, d_out, two, two, two, h1, two, two, two, dx, i64(M), i64(K1), i64(head), i64(col0),
+                                    i64(col1), None)
+
+    for call in (fwd, bwd):
+        for kw in (dict(K1=0), dict(K1=16), dict(K1=48), dict(K1=1056), dict(head=16), dict(head=96), dict(head=128)):
+            assert call(**kw) == _lib.TS_ERR_UNSUPPORTED and b"unsupported shape" in lib.ts_last_error(), kw
+        for kw in (dict(nets=0), dict(nets=9)):
+            assert call(**kw) == _lib.TS_ERR_INVALID_ARG and b"networks" in lib.ts_last_error(), kw
+        for kw in (dict(M=0), dict(M=-1), dict(M=1 << 31), dict(K1=-32), dict(head=-32)):
+            assert call(**kw) == _lib.TS_ERR_INVALID_ARG, kw
+    for kw in (dict(x=None), dict(wb1=None), dict(out=None)):
+        assert fwd(**kw) == _lib.TS_ERR_INVALID_ARG and b"NULL pointer array" in lib.ts_last_error(), kw
+    for kw in (dict(x=hole), dict(wb1=hole), dict(out=hole)):
+        assert fwd(**kw) == _lib.TS_ERR_INVALID_ARG and b"bad argument" in lib.ts_last_error(), kw
+    for kw in (dict(d_out=None), dict(h1=None)):
+        assert bwd(**kw) == _lib.TS_ERR_INVALID_ARG and b"NULL pointer array" in lib.ts_last_error(), kw
+    for kw in (dict(d_out=hole), dict(h1=hole)):
+        assert bwd(**kw) == _lib.TS_ERR_INVALID_ARG and b"bad argument" in lib.ts_last_error(), kw
+    for kw in (dict(col0=5, col1=5), dict(col0=9, col1=5), dict(col0=60, col1=65), dict(col0=-1, col1=5)):
+        assert bwd(**kw) == _lib.TS_ERR_INVALID_ARG and b"column range" in lib.ts_last_error(), kw
+    for kw in (dict(K1=160, col0=0, col1=129), dict(K1=160, col0=15, col1=144)):
+        assert bwd(**kw) == _lib.TS_ERR_UNSUPPORTED and b"wider than 128" in lib.ts_last_error(), kw
+    for dx in (hole, (ctypes.c_void_p * 2)(None, 4096)):
+        assert bwd(dx=dx) == _lib.TS_ERR_INVALID_ARG and b"all networks or none" in lib.ts_last_error()
+    # ts_mlp3_set_variant: the previous setting as 10 nw + rb; anything but nw in {0, 4, 8}, rb in {0, 2} changes nothing
+    prev = lib.ts_mlp3_set_variant(4, 2)
+    try:
+        assert prev in (0, 2, 40, 42, 80, 82)
+        for nw, rb in ((3, 0), (16, 0), (-4, 0), (0, 1), (0, -2), (8, 4)):
+            assert lib.ts_mlp3_set_variant(nw, rb) == _lib.TS_ERR_INVALID_ARG and b"ts_mlp3_set_variant" in lib.ts_last_error()
+        assert lib.ts_mlp3_set_variant(8, 0) == 42 and lib.ts_mlp3_set_variant(0, 0) == 80 and lib.ts_mlp3_set_variant(0, 2) == 0
+        assert lib.ts_mlp3_set_variant(0, 0) == 2
+    finally:
+        lib.ts_mlp3_set_variant(prev // 10, prev % 10)
 
 
 @pytest.mark.parametrize("hidden,depth", [(100, 2), (256, 7)])

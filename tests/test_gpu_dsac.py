@@ -34,7 +34,10 @@ def make_engine(obs_dim, n_act, hidden, seed, cfg):
     return eng, nets
 
 
-@pytest.mark.parametrize("obs_dim,n_act,hidden,B", [(11, 5, 64, 300), (128, 18, 256, 4096), (33, 2, 32, 1), (4, 64, 96, 77)])
+@pytest.mark.parametrize("obs_dim,n_act,hidden,B", [(11, 5, 64, 300), (128, 18, 256, 4096), (33, 2, 32, 1), (4, 64, 96, 77),
+                                                   # 33 .. 64 actions at hidden 256: the fused kernels with a 64-column head on four
+                                                   # waves (mlp3_*_kernel<64, 4, 1>, tests/mlp3_edge_cases.py)
+                                                   (11, 33, 256, 33), (128, 64, 256, 300)])
 def test_logits_and_target_q_vs_oracle(obs_dim, n_act, hidden, B):
     from tianshou_amd import dsac as DS
 
@@ -57,7 +60,8 @@ def test_logits_and_target_q_vs_oracle(obs_dim, n_act, hidden, B):
 
 
 @pytest.mark.parametrize("obs_dim,n_act,hidden,B,auto,weighted", [(128, 18, 256, 4096, True, False),
-                                                                  (11, 5, 64, 200, False, True)])
+                                                                  (11, 5, 64, 200, False, True),
+                                                                  (11, 33, 256, 33, True, True), (128, 64, 256, 300, False, False)])
 def test_update_gradients_vs_oracle(obs_dim, n_act, hidden, B, auto, weighted):
     """All three gradients of one update (learning rates 0, so the actor phase sees the same critics)."""
     from tianshou_amd import dsac as DS

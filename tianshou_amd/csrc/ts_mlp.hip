@@ -408,6 +408,18 @@ bool mlp3_supported(int K1, int hidden, int head_cols) {
 }
 
 namespace {
+// Kernel variant of the multi-network dispatch below (ts_mlp3_set_variant; TS_MLP_NW / TS_MLP_RB preset it).
+//   nw: 0 = automatic, 4 / 8 = that many waves per workgroup for every launch; rb: 0 = automatic (16-row workgroups),
+//   2 = 32-row workgroups where the rule in mlp3_forward_nx admits them.
+struct Variant { int nw, rb; };
+Variant& variant_ref() {
+    static Variant v = [] {
+        const int nw = getenv("TS_MLP_NW") ? atoi(getenv("TS_MLP_NW")) : 0;
+        const int rb = getenv("TS_MLP_RB") ? atoi(getenv("TS_MLP_RB")) : 0;
+        return Variant{nw == 0 ? 0 : (nw == 4 ? 4 : 8), rb == 2 ? 2 : 0};       // as the dispatch has always read them
+    }();
+    return v;
+}
 int n_cus() {
     static int cus = 0;
     if (!cus) {
@@ -447,16 +459,16 @@ int mlp3_forward_nx(hipStream_t s, int nets, const float* const* xs, int M, int 
         a.h1[k] = h1 ? h1[k] : nullptr; a.h2[k] = h2 ? h2[k] : nullptr; a.out[k] = out[k];
     }
     // four-wave workgroups (two per CU) when several networks share the launch and two such workgroups fit a CU's LDS
-    static const int force_nw = getenv("TS_MLP_NW") ? atoi(getenv("TS_MLP_NW")) : 0;
+    const int force_nw = variant_ref().nw;
     constexpr int ROWS = 16;
     // four-wave 16-row workgroups (two per CU) for several networks when two of them fit a CU's LDS, eight-wave 16-row
-    // workgroups for one network; TS_MLP_RB=2: 32-row workgroups (eight waves, one per CU) when several networks share the
+    // workgroups for one network; rb = 2 (ts_mlp3_set_variant / TS_MLP_RB=2): 32-row workgroups (eight waves, one per CU) when several networks share the
     // launch and 32-row workgroups still fill the chip
-    static const int force_rb = getenv("TS_MLP_RB") ? atoi(getenv("TS_MLP_RB")) : 0;
+    const int force_rb = variant_ref().rb;
     const size_t lds32 = sizeof(float) * (size_t)(std::max(32 * (K1 + 4), 32 * HP) + 32 * HP + part_floats(8, 32));
     // Measured (profiles/r05_mlp3_32_row_workgroups.txt): SAC C5 2,619 -> 2,660, TD3 / DDPG +0.6 / +1.1 %, DiscreteSAC
     // 3,724 -> 3,589 updates/s -- the twin launches are at 62 % of the fp32-MFMA issue rate already (2.95 GFLOP in 34 us), not
-    // bound by the weight stream; off unless TS_MLP_RB=2.
+    // bound by the weight stream; off unless asked for.
     const bool two = force_rb == 2 && nets > 1 && (int64_t)nets * ceil_div(M, 32) >= 3 * n_cus() / 4 &&
                      lds32 <= 160 * 1024 && !force_nw;
     const size_t lds4 = sizeof(float) * (size_t)(ROWS * (K1 + 4) + 2 * ROWS * HP + part_floats(4, ROWS));
@@ -491,7 +503,8 @@ int mlp3_backward_n(hipStream_t s, int nets, const float* const* d_out, int M, i
     TS_REQUIRE(M >= 1, TS_ERR_INVALID_ARG, "mlp3_backward: bad argument");
     BwdArgs a{};
     a.M = M; a.K1 = K1;
-    const bool want_dx = dx && dx[0];
+    bool want_dx = false;               // any network: a range given for some networks only is refused below, whichever they are
+    for (int k = 0; dx && k < nets; ++k) want_dx = want_dx || dx[k] != nullptr;
     for (int k = 0; k < nets; ++k) {
         TS_REQUIRE(d_out[k] && wb1[k] && wb2[k] && wb3[k] && h1[k] && h2[k] && dh1[k] && dh2[k], TS_ERR_INVALID_ARG,
                    "mlp3_backward: bad argument");
@@ -505,8 +518,8 @@ int mlp3_backward_n(hipStream_t s, int nets, const float* const* d_out, int M, i
         a.dx_nt = (int)ceil_div(col1 - a.dx_c0, 16);
         TS_REQUIRE(a.dx_nt <= 8, TS_ERR_UNSUPPORTED, "mlp3_backward: input-gradient range wider than 128 columns");
     }
-    static const int force_nw = getenv("TS_MLP_NW") ? atoi(getenv("TS_MLP_NW")) : 0;
-    static const int force_rb = getenv("TS_MLP_RB") ? atoi(getenv("TS_MLP_RB")) : 0;
+    const int force_nw = variant_ref().nw;
+    const int force_rb = variant_ref().rb;
     constexpr int ROWS = 16;
     const bool two = force_rb == 2 && nets > 1 && (int64_t)nets * ceil_div(M, 32) >= 3 * n_cus() / 4 && !force_nw;
     const bool four = force_nw ? force_nw == 4 : nets > 1;
@@ -539,3 +552,38 @@ bool mlp3_backward_supported(int K1, int hidden, int head_cols, bool want_dx, in
 }
 
 }  // namespace ts
+
+// ---- the layer-level entry points (include/tsengine.h): thin wrappers, every check before any HIP call ----------------------
+extern "C" {
+
+int ts_mlp3_forward(ts_workspace* ws, int nets, const float* const* x, const float* const* wb1, const float* const* wb2,
+                    const float* const* wb3, float* const* h1, float* const* h2, float* const* out, int64_t M, int64_t K1,
+                    int64_t head_cols, ts_stream_t stream) {
+    TS_REQUIRE(x && wb1 && wb2 && wb3 && out, TS_ERR_INVALID_ARG, "ts_mlp3_forward: NULL pointer array");
+    TS_REQUIRE(M >= 0 && M < (1ll << 31) && K1 >= 0 && K1 < (1 << 24) && head_cols >= 0 && head_cols < (1 << 24), TS_ERR_INVALID_ARG,
+               "ts_mlp3_forward: size out of range");
+    return ts::mlp3_forward_nx(ts::as_stream(stream), nets, x, (int)M, (int)K1, wb1, wb2, wb3, (int)head_cols, h1, h2, out, ws);
+}
+
+int ts_mlp3_backward(ts_workspace* ws, int nets, const float* const* d_out, const float* const* wb1, const float* const* wb2,
+                     const float* const* wb3, const float* const* h1, const float* const* h2, float* const* dh1, float* const* dh2,
+                     float* const* dx, int64_t M, int64_t K1, int64_t head_cols, int64_t col0, int64_t col1, ts_stream_t stream) {
+    TS_REQUIRE(d_out && wb1 && wb2 && wb3 && h1 && h2 && dh1 && dh2, TS_ERR_INVALID_ARG, "ts_mlp3_backward: NULL pointer array");
+    TS_REQUIRE(M >= 0 && M < (1ll << 31) && K1 >= 0 && K1 < (1 << 24) && head_cols >= 0 && head_cols < (1 << 24), TS_ERR_INVALID_ARG,
+               "ts_mlp3_backward: size out of range");
+    TS_REQUIRE(dx == nullptr || (col0 >= 0 && col0 < (1 << 24) && col1 >= 0 && col1 < (1 << 24)), TS_ERR_INVALID_ARG,
+               "ts_mlp3_backward: bad column range");
+    return ts::mlp3_backward_n(ts::as_stream(stream), nets, d_out, (int)M, (int)K1, wb1, wb2, wb3, (int)head_cols, h1, h2, dh1, dh2, dx,
+                               dx ? (int)col0 : 0, dx ? (int)col1 : 0, ws);
+}
+
+int ts_mlp3_set_variant(int nw, int rb) {
+    TS_REQUIRE((nw == 0 || nw == 4 || nw == 8) && (rb == 0 || rb == 2), TS_ERR_INVALID_ARG,
+               "ts_mlp3_set_variant: nw is 0, 4 or 8 and rb is 0 or 2 (got %d, %d)", nw, rb);
+    ts::Variant& v = ts::variant_ref();
+    const int prev = v.nw * 10 + v.rb;            // 0, 2, 40, 42, 80 or 82: never negative, so never an error code
+    v = ts::Variant{nw, rb};
+    return prev;
+}
+
+}  // extern "C"
