@@ -1283,6 +1283,62 @@ int ts_dsac_update(ts_workspace* ws, const ts_sac_state* st, int64_t adam_step, 
                    float* grads_out, ts_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * DiscreteSAC on the Atari trunk (examples/atari/atari_sac.py): an actor and two critics, single Linear heads H -> n_act, on
+ * ONE shared DQNet(features_only=True, output_dim_added_layer=H); observations NHWC, uint8 (obs_u8) or float32.
+ *   feat = relu(fc(relu(conv3(relu(conv2(relu(conv1(obs))))))))      fc: F -> H, H a multiple of 32 in [32, 1024]
+ * Flat parameters: conv1 | conv2 | conv3 | fc | actor head | critic-1 head | critic-2 head, each [K + 1, OC] with the bias as
+ * last row; head width ld = n_act rounded up to 32, padding columns exactly zero.  Lagged vector (critic_old and critic2_old
+ * share ONE lagged trunk): conv1 | conv2 | conv3 | fc | critic-1 head | critic-2 head.  Three optimizers (critic 1, critic 2,
+ * actor) each own trunk + own head: gradients and Adam moments come as three sets of T + Hd floats in that order.
+ * ------------------------------------------------------------------------------------------- */
+
+/* -> the length of the flat parameter vector, -1 for an unsupported network. */
+int64_t ts_dsac_cnn_param_count(int64_t c, int64_t h, int64_t w, int64_t n_act, int64_t hidden);
+/* out11 = {F, ld, total, T (trunk length), starts of conv1, conv2, conv3, fc, actor head, critic-1 head, critic-2 head}. */
+int ts_dsac_cnn_layout(int64_t c, int64_t h, int64_t w, int64_t n_act, int64_t hidden, int64_t* out11);
+
+/* The head kernels on raw arrays float32[B, n_act] (one wave per sample; 1 <= n_act <= 64, 1 <= B < 2^24).
+ * alpha = exp(*log_alpha) read on the device when log_alpha != NULL, else fixed_alpha.
+ * target (discrete_sac.py:147-155): out[b] = sum_j p_j min(q1_old, q2_old)[b, j] + alpha H(p), p = softmax(logits[b]). */
+int ts_dsac_cnn_target(const float* logits, const float* q1_old, const float* q2_old, const float* log_alpha, double fixed_alpha,
+                       int64_t B, int64_t n_act, float* out, ts_stream_t stream);
+/* critic (discrete_sac.py:163-174): td_out[b] = q[b, act[b]] - target[b]; terms_out[b] = td^2 w_b (weight nullable = 1);
+ * loss_out[0] = their mean in a fixed order; dq_out float32[B, ld] = 2 w_b td / B at act[b], zero elsewhere (padding too).
+ * act[b] outside [0, n_act) is not reported: it is clamped into the range, as in ts_crr_loss (ts_dsac_cnn_update likewise). */
+int ts_dsac_cnn_critic(const float* q, const int64_t* act, const float* target, const float* weight, int64_t B, int64_t n_act,
+                       float* dq_out, float* td_out, float* terms_out, float* loss_out, ts_stream_t stream);
+/* actor (discrete_sac.py:177-184): terms_out[b] = alpha H_b + sum_j p_j min(q1, q2)[b, j]; loss_out[0] = -mean; entropy_out[b]
+ * = H_b; dlogits_out float32[B, ld] = the gradient of the loss at the logits (q without gradient; padding exactly 0). */
+int ts_dsac_cnn_actor(const float* logits, const float* q1, const float* q2, const float* log_alpha, double fixed_alpha, int64_t B,
+                      int64_t n_act, float* dlogits_out, float* entropy_out, float* terms_out, float* loss_out,
+                      ts_stream_t stream);
+
+/* DiscreteSACPolicy.forward (discrete_sac.py:67-80) up to the logits: logits_out float32[B, n_act]. */
+int ts_dsac_cnn_forward(ts_workspace* ws, const float* params, int64_t c, int64_t h, int64_t w, int64_t n_act, int64_t hidden,
+                        const void* obs_nhwc, int obs_u8, int64_t B, float* logits_out, ts_stream_t stream);
+
+/* _target_q_compute_value on obs_next: the live trunk + actor head on the caller's stream, the lagged trunk + both lagged critic
+ * heads on a side stream of the workspace, then the target kernel: out float32[B]. */
+int ts_dsac_cnn_target_q(ts_workspace* ws, const float* params, const float* params_old, const float* log_alpha,
+                         double fixed_alpha, int64_t c, int64_t h, int64_t w, int64_t n_act, int64_t hidden,
+                         const void* obs_next_nhwc, int obs_u8, int64_t B, float* out, ts_stream_t stream);
+
+/* DiscreteSAC._update_with_batch (discrete_sac.py:157-196) in the reference's order: critic 1 (forward, loss, backward, Adam
+ * over trunk + head 1 with moment set 0), critic 2 on the trunk that step has just moved (moment set 1), the actor on ONE pass
+ * of the twice-moved trunk that also feeds both updated critic heads (moment set 2), AutoAlpha.update (hp->auto_alpha; one Adam
+ * step on log_alpha with its [1] moments), Polyak of the lagged vector (hp->tau; <= 0 skips it).  adam_step = 1-based step of
+ * this call (all optimizers advance together).  adam_m3 / adam_v3 float32[3, T + Hd]; returns float32[B]; weight nullable.
+ * stats_out5 = {actor_loss, critic1_loss, critic2_loss, alpha (after the update), alpha_loss}; weight_out float32[B] =
+ * (td1 + td2) / 2 (ts_dqn_wait_td waits for it).  hp->actor_lr < 0 and hp->critic_lr < 0: gradient only -- grads_out
+ * float32[3, T + Hd] receives the three gradients at the UNCHANGED parameters and no state is touched; grads_out is nullable
+ * otherwise. */
+int ts_dsac_cnn_update(ts_workspace* ws, float* params, float* params_old, float* adam_m3, float* adam_v3, float* log_alpha,
+                       float* log_alpha_m, float* log_alpha_v, int64_t adam_step, int64_t c, int64_t h, int64_t w, int64_t n_act,
+                       int64_t hidden, const void* obs_nhwc, int obs_u8, const int64_t* act, const float* returns,
+                       const float* weight, int64_t B, const ts_sac_hparams* hp, float* stats_out5, float* weight_out,
+                       float* grads_out, ts_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * REDQ (tianshou/algorithm/modelfree/redq.py): SAC's tanh-Gaussian policy + an ensemble of E critics whose
  * Linear layers are EnsembleLinear (utils/net/common.py:518-550), nets of test/continuous/test_redq.py:86-107 with hidden
  * [256, 256].  The ensemble's parameters are E consecutive blocks in ts_sac_layout's critic layout; actor as SAC's.

@@ -2706,6 +2706,198 @@ def make_hip_discrete_sac(ref=None):
     return HipDiscreteSAC
 
 
+def make_hip_discrete_sac_cnn(ref=None):
+    """Returns HipDiscreteSACCnn(DiscreteSAC): `_preprocess_batch` / `_update_with_batch` (ddpg.py:287-301,
+    discrete_sac.py:147-196) on the engine (tianshou_amd/dsac_cnn.py) for the networks of examples/atari/atari_sac.py:
+    DiscreteActor(softmax_output=False), DiscreteCritic(last_size=n_act) and a second, explicitly given DiscreteCritic, single
+    Linear heads on ONE shared DQNet(features_only=True, output_dim_added_layer=H), H a multiple of 32 in [32, 1024]; Adam on
+    all three optimizers (each over the shared trunk and its own head, no gradient clipping) and on AutoAlpha; anything else
+    raises NotImplementedError naming what is unsupported.  The trunk is stepped three times per update with three moment sets,
+    as the reference's three optimizers step it.  `critic_old` and `critic2_old` each own a trunk copy that the reference keeps
+    bit-equal; the engine keeps ONE lagged trunk, refuses two lagged trunks that differ and writes the lagged trunk back into
+    both.  Buffer layouts as HipDQN / HipIQN (whole [c, h, w] observations, or single frames with `stack_num`); a prioritized
+    buffer's weights go in and `batch.weight` = (td1 + td2) / 2 comes out.  `match_rng_stream` as in HipDiscreteSAC.  The
+    collector's `policy.forward` stays on torch.  `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    from torch.distributions import Categorical
+
+    DiscreteSAC = _ref(ref, "tianshou.algorithm.modelfree.discrete_sac", "DiscreteSAC")
+    DiscreteSACTrainingStats = _ref(ref, "tianshou.algorithm.modelfree.discrete_sac", "DiscreteSACTrainingStats")
+    AutoAlpha = _ref(ref, "tianshou.algorithm.modelfree.sac", "AutoAlpha")
+
+    from . import dqn as D
+    from . import dsac_cnn as DC
+    from .sac import SACConfig
+
+    who = "HipDiscreteSACCnn"
+    supported = (f"{who}: policy.actor must be DiscreteActor(preprocess_net, softmax_output=False), critic and critic2 "
+                 "DiscreteCritic(preprocess_net, last_size=n_act), single Linear heads on one shared "
+                 "DQNet(features_only=True, output_dim_added_layer=H)")
+    set_keys = DC.TRUNK_KEYS + DC.HEAD_KEYS                                   # one module's ten tensors: trunk + own head
+
+    class HipDiscreteSACCnn(_HipGlue, DiscreteSAC):
+        _HIP_LR = (("actor_lr", "policy_optim"), ("critic_lr", "critic_optim"), ("critic_lr", "critic2_optim"),
+                   ("alpha_lr", "alpha"))
+
+        def __init__(self, *args, device="cuda", match_rng_stream: bool = True, **kwargs):
+            super().__init__(*args, **kwargs)
+            self._hip_device = torch.device(device)
+            self._hip_match_rng = match_rng_stream
+            self._hip_check_model()
+            self._hip_engine = None
+            self._hip_glue_init()
+
+        def _hip_live_params(self):
+            named = dict(torch.nn.ModuleList([self.policy, self.critic, self.critic2]).named_parameters())
+            if list(named.keys()) != DC.TIANSHOU_KEYS:
+                raise NotImplementedError(f"{supported}; got parameters {list(named.keys())}")
+            return [named[k] for k in DC.TIANSHOU_KEYS]
+
+        def _hip_sets(self):
+            """(optimizer wrapper, its ten parameters: the shared trunk and the own head) in the engine's SETS order."""
+            p = self._hip_live_params()
+            return ((self.critic_optim, p[:8] + p[10:12]), (self.critic2_optim, p[:8] + p[12:14]), (self.policy_optim, p[:10]))
+
+        def _hip_check_model(self) -> None:
+            actor = getattr(self.policy, "actor", None)
+            trunks = [getattr(m, "preprocess", None) for m in (actor, self.critic, self.critic2)]
+            if trunks[0] is None or trunks[1] is not trunks[0]:
+                raise NotImplementedError(f"{supported}; the actor and the critic do not share one feature-net object")
+            if trunks[2] is not trunks[0]:
+                raise NotImplementedError(f"{supported}; critic2 does not share the feature-net object (critic2=None deep-copies "
+                                          "the first critic and its trunk, which is a different network: pass critic2 explicitly)")
+            params = self._hip_live_params()
+            shapes = [tuple(p.shape) for p in params]
+            convs_ok = (len(shapes[0]) == 4 and shapes[0][0] == 32 and shapes[0][2:] == (8, 8) and shapes[2] == (64, 32, 4, 4)
+                        and shapes[4] == (64, 64, 3, 3))
+            if not convs_ok or len(shapes[6]) != 2:
+                raise NotImplementedError(f"{supported}; the preprocess_net is not the DQNet convolution trunk with an added layer")
+            # the kernel shapes do not tell the strides: the engine computes stride 4 / 2 / 1 without padding, and nothing else
+            convs = [m for m in trunks[0].modules() if isinstance(m, torch.nn.Conv2d)]
+            got = [(m.kernel_size, m.stride, m.padding, m.dilation, m.groups) for m in convs]
+            if got != [((k, k), (st, st), (0, 0), (1, 1), 1) for k, st in ((8, 4), (4, 2), (3, 1))]:
+                raise NotImplementedError(f"{supported}; the convolutions must be DQNet's (kernel 8 / 4 / 3, stride 4 / 2 / 1, no "
+                                          f"padding, dilation or groups), got (kernel, stride, padding, dilation, groups) {got}")
+            mods = [m for m in trunks[0].modules() if not list(m.children())]
+            kinds = [type(m).__name__ for m in mods]
+            if kinds != ["Conv2d", "ReLU", "Conv2d", "ReLU", "Conv2d", "ReLU", "Flatten", "Linear", "ReLU"]:
+                raise NotImplementedError(f"{supported}; the preprocess_net must be DQNet's chain conv, ReLU, conv, ReLU, conv, "
+                                          f"ReLU, Flatten, Linear, ReLU on the raw pixel values, got {kinds}")
+            hidden = shapes[6][0]
+            if hidden % 32 or not 32 <= hidden <= 1024:
+                raise NotImplementedError(f"{who}: output_dim_added_layer must be a multiple of 32 in [32, 1024], got {hidden}")
+            n_act = shapes[8][0]
+            if any(shapes[j] != (n_act, hidden) for j in (8, 10, 12)) or not 1 <= n_act <= 64:
+                raise NotImplementedError(f"{who}: the three heads must be Linear({hidden}, n_act) with the same 1 <= n_act <= 64")
+            if getattr(actor, "softmax_output", False):
+                raise NotImplementedError(f"{supported}; got softmax_output=True")
+            for name, (opt, own) in zip(("critic_optim", "critic2_optim", "policy_optim"), self._hip_sets()):
+                o, _ = _adam_of(opt)
+                if opt._max_grad_norm:
+                    raise NotImplementedError(f"{who}: {name} clips the gradient norm; the engine steps without clipping")
+                if {id(p) for g in o.param_groups for p in g["params"]} != {id(p) for p in own}:
+                    raise NotImplementedError(f"{who}: {name} must hold the shared trunk and its own head, ten tensors")
+            if isinstance(self.alpha, AutoAlpha):
+                o = self.alpha._optim
+                g = o.param_groups[0]
+                if type(o).__name__ != "Adam" or g.get("weight_decay", 0) != 0 or g.get("amsgrad", False):
+                    raise NotImplementedError(f"{who}: AutoAlpha must use torch.optim.Adam without weight decay / amsgrad")
+            self._hip_hidden, self._hip_n_act = int(hidden), int(n_act)
+
+        def _hip_old_modules(self):
+            return [getattr(m, "module", m) for m in (self.critic_old, self.critic2_old)]
+
+        def _hip_old_params(self):
+            """The lagged vector's twelve tensors: the trunk and the head of `critic_old`, the head of `critic2_old`, whose own
+            trunk must equal `critic_old`'s bit for bit -- the reference moves both with the same tau from the same live trunk."""
+            o1, o2 = (params_by_keys(m, set_keys) for m in self._hip_old_modules())
+            if not all(torch.equal(x.detach(), y.detach()) for x, y in zip(o1[:8], o2[:8])):
+                raise NotImplementedError(f"{who}: the trunks of critic_old and critic2_old differ; the engine keeps one lagged "
+                                          "trunk (the reference averages both from the same live trunk with the same tau)")
+            return o1 + o2[8:]
+
+        def _engine(self, c, h, w):
+            if self._hip_engine is None:
+                dev, hid, n_act = self._hip_device, self._hip_hidden, self._hip_n_act
+                dims = (c, h, w, n_act, hid)
+                cfg = SACConfig(**_ac_config_fields(self), **_ac_entropy_fields(self, AutoAlpha))
+                eng = DC.DiscreteSACCnnEngine(c, h, w, n_act, hid,
+                                              DC.flat_from_torch([p.detach() for p in self._hip_live_params()], *dims, dev), cfg)
+                eng.params_old = DC.flat_from_torch([p.detach() for p in self._hip_old_params()], *dims, dev)
+                for k, (opt, own) in enumerate(self._hip_sets()):          # resume from a loaded checkpoint
+                    ms, vs, step = adam_state(opt._optim, own)
+                    eng.adam_m[k], eng.adam_v[k] = DC.flat_from_torch(ms, *dims, dev), DC.flat_from_torch(vs, *dims, dev)
+                    eng.adam_step = max(eng.adam_step, step)
+                if cfg.auto_alpha:
+                    st = self.alpha._optim.state.get(self.alpha._log_alpha, {})
+                    if "exp_avg" in st:
+                        eng.log_alpha_m[0], eng.log_alpha_v[0] = float(st["exp_avg"]), float(st["exp_avg_sq"])
+                self._hip_engine = eng
+            return self._hip_engine
+
+        def _hip_write_back(self) -> None:
+            """Engine state -> the torch modules and torch.optim: fourteen live tensors (the shared trunk once); the ONE lagged
+            trunk into both lagged modules, each lagged head into its own; the three optimizers' moments over trunk + own head
+            and the shared step count; log alpha and its optimizer."""
+            eng = self.__dict__.get("_hip_engine_obj")
+            if eng is None:
+                return
+            dims = (eng.c, eng.h, eng.w, eng.n_act, eng.hidden)
+            with torch.no_grad():
+                for p, t in zip(self._hip_live_params(), DC.flat_to_torch(eng.params, *dims)):
+                    self._hip_put(p, t)
+                old = DC.flat_to_torch(eng.params_old, *dims)
+                o1, o2 = (params_by_keys(m, set_keys) for m in self._hip_old_modules())
+                for p, t in zip(o1 + o2, old[:10] + old[:8] + old[10:12]):
+                    self._hip_put(p, t)
+                if eng.adam_step:
+                    for k, (opt, own) in enumerate(self._hip_sets()):
+                        store_adam_state(opt._optim, own, DC.flat_to_torch(eng.adam_m[k], *dims),
+                                         DC.flat_to_torch(eng.adam_v[k], *dims), eng.adam_step)
+                if eng.cfg.auto_alpha:
+                    self._hip_put(self.alpha._log_alpha, eng.log_alpha[0])
+                    if eng.adam_step:
+                        store_adam_state(self.alpha._optim, [self.alpha._log_alpha], [eng.log_alpha_m[0]], [eng.log_alpha_v[0]],
+                                         eng.adam_step)
+
+        def _hip_draw(self, obs):
+            if self._hip_match_rng:                  # discrete_sac.py:74-78: dist.sample() inside the training step
+                Categorical(logits=self._hip_engine.policy_forward(obs).cpu()).sample()
+
+        def _preprocess_batch(self, batch, buffer, indices):
+            c, h, w, self._hip_stack = self._layout(buffer, who)
+            m, idx = _q_begin(self, who, batch, buffer, indices)
+            eng = self._engine(c, h, w)
+            if self._hip_match_rng:
+                from .returns import nstep_indices
+
+                after = nstep_indices(m, idx, eng.cfg.n_step)
+                if m.obs_next is None:
+                    self._hip_draw(D.gather_obs_nhwc(m.obs, m, m.next(after), self._hip_stack, as_u8=True))
+                else:
+                    self._hip_draw(D.gather_obs_nhwc(m.obs_next, m, after, self._hip_stack, as_u8=True))
+            batch.returns = eng.preprocess(m, m.obs, idx, self._hip_stack, obs_next_frames=m.obs_next).reshape(-1, 1)
+            return batch
+
+        def _update_with_batch(self, batch):
+            self._hip_refresh_lr()
+            eng, m = self._hip_engine, self._hip_mirror
+            weight = getattr(batch, "weight", None)
+            obs = D.gather_obs_nhwc(m.obs, m, self._hip_idx, self._hip_stack, as_u8=True)
+            self._hip_draw(obs)
+            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device)
+            stats, w = eng.update_with_batch(obs, act, batch.returns.reshape(-1), weight)
+            batch.weight = w                                                      # prio-buffer, discrete_sac.py:174
+            s = stats.cpu().numpy()                                               # one D2H per update()
+            self._hip_after_update()
+            auto = eng.cfg.auto_alpha
+            return DiscreteSACTrainingStats(actor_loss=float(s[0]), critic1_loss=float(s[1]), critic2_loss=float(s[2]),
+                                            alpha=float(s[3]), alpha_loss=float(s[4]) if auto else None)
+
+        _layout = staticmethod(_q_layout)
+
+    return HipDiscreteSACCnn
+
+
 # ---------------------------------------------------------------------------------------------------
 # PPO on the Atari actor-critic (examples/atari/atari_ppo.py:106-135)
 # ---------------------------------------------------------------------------------------------------
