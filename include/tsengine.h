@@ -1621,6 +1621,65 @@ int ts_icm_cnn_apply(ts_workspace* ws, float* params, float* state_m, float* sta
                      double weight_decay, double rms_alpha, double rms_momentum, int32_t rms_centered, double max_grad_norm,
                      float* stats_out3, ts_stream_t stream);
 
+/* ---- Branching DQN (modelfree/bdqn.py:106-224, utils/net/common.py:553-674 BranchingNet, arXiv 1711.08946): D independent
+ * action dimensions of A discrete values each on one trunk, dueling combine q[b, d, a] = v[b] + adv[b, d, a] - mean_a adv[b, d, :].
+ * The model is described by five arguments in every entry point:
+ *   common_net:        obs_dim, n_hidden 1 .. TS_NET_MAX_HIDDEN, hidden[] (1 .. 1024 each), activation TS_NET_ACT_RELU or
+ *                      TS_NET_ACT_TANH (behind EVERY layer of `common`, `value` and the branches except their last Linear: the
+ *                      common net's last hidden layer is its output); flags must be 0, max_action / ln_eps are not read;
+ *   value_hidden:      width of the value net's one hidden layer, 0 = none (value_hidden_sizes = []);
+ *   action_hidden:     the same for every branch (action_hidden_sizes);
+ *   num_branches D:    1 .. TS_BDQN_MAX_BRANCHES;  action_per_branch A: 1 .. TS_BDQN_MAX_ACTIONS.
+ * Flat vector, every block [K_pad + 1, N_pad] (widths rounded up to 32, last row = bias, padding entries zero and staying zero
+ * through ts_bdqn_update) as in ts_net_layout: the common layers | the "fan" block (present when value_hidden + action_hidden >
+ * 0): the first layers of `value` and of all D branches read the same input and are ONE matrix of Hvp + D Hap columns (Hvp =
+ * pad32(value_hidden), Hap = pad32(action_hidden); value columns first, then branch 0, 1, ...) | the value head [Kv_pad + 1, 32]
+ * (column 0 = V; Kv = value_hidden or, without it, the common output width) | D branch heads [Ka_pad + 1, pad32(A)].
+ * ts_bdqn_layout: h_out8 = {floats of the flat vector, offset of the fan block, its columns (0: no fan), Hvp, Hap, offset of
+ * the value head, offset of branch head 0, floats of one branch head}.
+ * The common chain and the fan run on the GEMM kernels of ts_conv_*; the heads are one forward launch (all D + 1 heads and the
+ * combine; per-branch argmax with ties to the LOWEST index) and one backward launch (loss, priorities, dueling backward, input
+ * gradient).  Head weight gradients are summed from slabs in a fixed order: no atomics, the same inputs give the same bits.
+ * All arithmetic float32.  An action index outside [0, A) is CLAMPED into it (no access leaves an array).
+ * TS_ERR_INVALID_ARG before any launch: a NULL pointer (nullable arguments excepted), B < 1, D < 1, A < 1, B x the widest layer
+ * >= 2^31; TS_ERR_UNSUPPORTED before any launch: D or A beyond the limits, n_hidden outside 1 .. TS_NET_MAX_HIDDEN, a width
+ * beyond 1024, another activation, non-zero flags.  No entry point synchronises with the host, copies to it or allocates
+ * outside the workspace. */
+#define TS_BDQN_MAX_BRANCHES 32
+#define TS_BDQN_MAX_ACTIONS 64
+int ts_bdqn_layout(const ts_net_desc* common_net, int64_t value_hidden, int64_t action_hidden, int64_t num_branches,
+                   int64_t action_per_branch, int64_t* h_out8);
+/* BranchingNet.forward: obs float32[B, obs_dim] -> q_out float32[B, D, A] and act_out int64[B, D] = argmax_a q (either nullable,
+ * not both). */
+int ts_bdqn_forward(ts_workspace* ws, const float* params, const ts_net_desc* common_net, int64_t value_hidden, int64_t action_hidden,
+                    int64_t num_branches, int64_t action_per_branch, const float* obs, int64_t B, float* q_out, int64_t* act_out,
+                    ts_stream_t stream);
+/* bdqn.py:155-195 on caller-supplied tables q_sel / q_eval float32[B, D, A], rew float32[B], end uint8[B] (non-zero = the
+ * transition ends an episode or is the buffer's last): a*[b, d] = argmax_a q_sel[b, d, :];
+ * ret_out[b] = rew[b] + gamma mean_d q_eval[b, d, a*[b, d]] (1 - end[b]), the mean in branch order. */
+int ts_bdqn_target(const float* q_sel, const float* q_eval, const float* rew, const uint8_t* end, int64_t B, int64_t D, int64_t A,
+                   double gamma, float* ret_out, ts_stream_t stream);
+/* bdqn.py:211-221 on a caller-supplied q float32[B, D, A], act int64[B, D], ret float32[B], weight float32[B] (NULL = 1):
+ * td[b, d] = ret[b] - q[b, d, act[b, d]]; loss_out[0] = mean_b(weight[b] mean_d td^2); prio_out[b] = sum_d td[b, d] (SIGNED: the
+ * prioritized buffer takes the absolute value); dq_out (nullable) float32[B, D, A] = d loss / d q. */
+int ts_bdqn_loss(ts_workspace* ws, const float* q, const int64_t* act, const float* ret, const float* weight, int64_t B, int64_t D,
+                 int64_t A, float* loss_out, float* prio_out, float* dq_out, ts_stream_t stream);
+/* The target of one update from the networks: q_sel = Q(obs_next; params) when is_double != 0, otherwise the evaluating
+ * network's; the evaluating network is params_old when given (target_update_freq > 0), otherwise params.  -> ret_out float32[B]. */
+int ts_bdqn_target_q(ts_workspace* ws, const float* params, const float* params_old, const ts_net_desc* common_net, int64_t value_hidden,
+                     int64_t action_hidden, int64_t num_branches, int64_t action_per_branch, const float* obs_next, const float* rew,
+                     const uint8_t* end, int64_t B, double gamma, int32_t is_double, float* ret_out, ts_stream_t stream);
+/* bdqn.py:211-222: forward pass, loss, reverse pass and ONE optimizer step (ts_optim_step's kinds TS_OPT_ADAM / TS_OPT_RMSPROP
+ * and hyper-parameters; clip_grad_norm_(max_grad_norm) first, <= 0: none).  loss_out float32[1] and prio_out float32[B] (device)
+ * as in ts_bdqn_loss, at the parameters before the step.  grad_out (nullable) float32[count] receives the gradient, padding
+ * entries zero; lr < 0: gradient, loss and priorities only, the parameters and the optimizer state unchanged.  Additionally
+ * TS_ERR_INVALID_ARG: optim_step < 1, another optim_kind. */
+int ts_bdqn_update(ts_workspace* ws, float* params, float* state_m, float* state_v, int64_t optim_step, const ts_net_desc* common_net,
+                   int64_t value_hidden, int64_t action_hidden, int64_t num_branches, int64_t action_per_branch, const float* obs,
+                   const int64_t* act, const float* ret, const float* weight, int64_t B, int32_t optim_kind, double lr, double beta1,
+                   double beta2, double eps, double weight_decay, double rms_alpha, double rms_momentum, int32_t rms_centered,
+                   double max_grad_norm, float* loss_out, float* prio_out, float* grad_out, ts_stream_t stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * TD3 / DDPG: ContinuousActorDeterministic (utils/net/continuous.py:26-85) + the SAC critics,

@@ -115,8 +115,27 @@ def load() -> C.CDLL:
     if hasattr(lib, "ts_ppo_param_count"):
         lib.ts_ppo_param_count.restype = C.c_int64
         lib.ts_ppo_param_count.argtypes = [C.c_int64, C.c_int64]
+    _bdqn_prototypes(lib)
     _lib = lib
     return lib
+
+
+def _bdqn_prototypes(lib) -> None:
+    """ts_bdqn_* (include/tsengine.h): with argtypes ctypes checks the arity and the kind of every argument of these calls."""
+    p, i64_, i32, f64_ = C.c_void_p, C.c_int64, C.c_int32, C.c_double
+    model = [p, i64_, i64_, i64_, i64_]              # common_net, value_hidden, action_hidden, num_branches, action_per_branch
+    protos = {
+        "ts_bdqn_layout": [*model, p],
+        "ts_bdqn_forward": [p, p, *model, p, i64_, p, p, p],
+        "ts_bdqn_target": [p, p, p, p, i64_, i64_, i64_, f64_, p, p],
+        "ts_bdqn_loss": [p, p, p, p, p, i64_, i64_, i64_, p, p, p, p],
+        "ts_bdqn_target_q": [p, p, p, *model, p, p, p, i64_, f64_, i32, p, p],
+        "ts_bdqn_update": [p, p, p, p, i64_, *model, p, p, p, p, i64_, i32, f64_, f64_, f64_, f64_, f64_, f64_, f64_, i32, f64_, p, p, p, p],
+    }
+    for name, argtypes in protos.items():
+        if hasattr(lib, name):                       # (a library built before these existed still serves every other engine)
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = argtypes, C.c_int
 
 
 def check(code: int) -> None:

@@ -4019,3 +4019,97 @@ def make_hip_bcq(ref=None):
         _hip_write_back = _ac_write_back
 
     return HipBCQ
+
+
+# ---------------------------------------------------------------------------------------------------
+# Branching DQN (bdqn.py:106-224) on BranchingNet: examples/box2d/bipedal_bdq.py
+# ---------------------------------------------------------------------------------------------------
+def make_hip_bdqn(ref=None):
+    """Returns HipBDQN(BDQN): `_preprocess_batch` / `_update_with_batch` (bdqn.py:155-224) on the engine (tianshou_amd/bdqn.py).
+    Supported model: BranchingNet with 1 .. 7 common hidden layers, at most one hidden layer in `value_hidden_sizes` and in
+    `action_hidden_sizes`, widths up to 1024, ReLU or tanh, no norm_layer, num_branches <= 32, action_per_branch <= 64; Adam or
+    RMSprop.  Anything else raises NotImplementedError naming this envelope (`bdqn.describe_model`); there is no torch fallback.
+    `_preprocess_batch` takes obs_next / rew of the sampled batch and the buffer's end flags as the reference does and makes ONE
+    target call; `batch.returns` is the device [B] result expanded as a view to [B, D, A].  `_update_with_batch` synchronises the
+    lagged network first, then one update call; the signed sum_d td goes to `batch.weight`.  Unlike the reference at B = 1 with
+    D > 1 (whose `.squeeze()` drops the batch axis) the target is the same formula at every B.  Like the reference, the targets
+    discount with the default of `_compute_return`'s `gamma` argument (0.99), not with `BDQN(gamma=...)`.  The collector's
+    `policy.forward` / `add_exploration_noise` stay the reference's.  `ref`: optional namespace replacing the tianshou imports
+    (see `_ref`)."""
+    from . import bdqn as BD
+
+    SimpleLossTrainingStats = _ref(ref, "tianshou.algorithm.modelfree.reinforce", "SimpleLossTrainingStats")
+    Base = _ref(ref, "tianshou.algorithm.modelfree.bdqn", "BDQN")
+
+    class HipBDQN(_HipGlue, Base):
+        def __init__(self, *args, device="cuda", **kwargs):
+            super().__init__(*args, **kwargs)
+            self._hip_device = torch.device(device)
+            self._hip_desc = BD.describe_model(self.policy.model)            # raises NotImplementedError naming the envelope
+            optimizer_fields(self.optim._optim)                             # (raises on an optimizer the engine does not implement)
+            if float(self.gamma) != self._hip_target_gamma():
+                import warnings
+
+                warnings.warn(f"HipBDQN: gamma = {self.gamma} is not used by the targets: like the reference's BDQN they discount with "
+                              f"the default of `_compute_return`'s `gamma` argument, {self._hip_target_gamma()}", stacklevel=2)
+            self._hip_engine = None
+            self._hip_glue_init()
+
+        def _hip_qstate(self):
+            return _QState(self._hip_desc["keys"], BD.flat_from_torch, BD.flat_to_torch, lambda eng: eng.dims)
+
+        def _hip_config(self):
+            of = optimizer_fields(self.optim._optim)
+            return BD.BDQNConfig(gamma=self._hip_target_gamma(), target_update_freq=int(self.target_update_freq),
+                                 is_double=bool(self.is_double), max_grad_norm=self.optim._max_grad_norm, **of)
+
+        def _hip_target_gamma(self) -> float:
+            """The discount of the targets.  bdqn.py:197-204 calls `_compute_return(batch, buffer, indices)` without its `gamma`
+            argument, so the reference discounts with that signature's default (0.99) whatever `BDQN(gamma=...)` was given; the
+            drop-in computes what the reference computes and reads the same default."""
+            import inspect
+
+            return float(inspect.signature(Base._compute_return).parameters["gamma"].default)
+
+        def _engine(self):
+            if self._hip_engine is None:
+                dims = self._hip_desc["dims"]
+                self._hip_engine = _q_load(self, BD.BDQNEngine(*dims, _q_flat(self, dims), self._hip_config()))
+            return self._hip_engine
+
+        def _hip_refresh_lr(self) -> None:
+            super()._hip_refresh_lr()
+            eng = self._hip_engine
+            if eng is not None:                  # plain attributes of the algorithm, read at every update like the learning rate
+                eng.cfg.gamma, eng.cfg.is_double = self._hip_target_gamma(), bool(self.is_double)
+                eng.cfg.max_grad_norm = self.optim._max_grad_norm
+
+        def _preprocess_batch(self, batch, buffer, indices):
+            """bdqn.py:173-204: the 1-step target of the sampled transitions."""
+            _require_gpu(self._hip_device, "HipBDQN")
+            eng = self._engine()
+            self._hip_refresh_lr()
+            end = np.asarray(buffer.done).copy()                            # bdqn.py:184-186
+            end[buffer.unfinished_index()] = True
+            obs_next = batch.obs_next.obs if hasattr(batch.obs_next, "obs") else batch.obs_next
+            ret = eng.target_q(np.asarray(obs_next, np.float32), np.asarray(batch.rew, np.float32), end[np.asarray(indices)])
+            batch.returns = ret.view(-1, 1, 1).expand(-1, eng.D, eng.A)
+            if hasattr(batch, "weight"):                                    # prio buffer (bdqn.py:193-194)
+                batch.weight = torch.as_tensor(np.asarray(batch.weight), dtype=torch.float32, device=self._hip_device)
+            return batch
+
+        def _update_with_batch(self, batch):
+            self._hip_refresh_lr()
+            eng = self._engine()
+            weight = batch.pop("weight", None)
+            obs = batch.obs.obs if hasattr(batch.obs, "obs") else batch.obs
+            ret = batch.returns[:, 0, 0]
+            loss, prio = eng.update(np.asarray(obs, np.float32), np.asarray(batch.act, np.int64), ret, weight)
+            self._iter = eng.iter
+            batch.weight = prio                                             # prio-buffer, bdqn.py:221: signed
+            self._hip_after_update()
+            return SimpleLossTrainingStats(loss=float(loss.item()))
+
+        _hip_write_back = _q_write_back
+
+    return HipBDQN
