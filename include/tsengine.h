@@ -1680,6 +1680,37 @@ int ts_bdqn_update(ts_workspace* ws, float* params, float* state_m, float* state
                    double beta2, double eps, double weight_decay, double rms_alpha, double rms_momentum, int32_t rms_centered,
                    double max_grad_norm, float* loss_out, float* prio_out, float* grad_out, ts_stream_t stream);
 
+/* ---- DQN on vector observations (modelfree/dqn.py:365-404 on utils/net/common.py:246-370 `Net`, dueling or not; the networks
+ * of examples/discrete/discrete_dqn.py, box2d/lunarlander_dqn.py, box2d/acrobot_dualdqn.py): one 32-row tile per workgroup,
+ * activations resident in LDS, weights streamed (ts_dqn_mlp.hip).  Three launches per update: target, step, apply.
+ * `desc` is a HOST array of TS_DQN_MLP_DESC_LEN int64: {obs_dim, n_act, dueling (0 / 1), n_trunk, n_q, n_v, trunk[4], q_hidden[2],
+ * v_hidden[2]} (unused widths are ignored).  Envelope (TS_ERR_UNSUPPORTED beyond it, before any HIP call): obs_dim in [1, 256],
+ * 1 .. 4 trunk hidden layers, 0 .. 2 hidden layers in each of Q and V, every width a multiple of 32 in [32, 256], ReLU,
+ * 1 <= n_act <= 32, 1 <= B <= 4096, and the LDS carve of one tile within 160 KB.
+ * Flat vector: per layer [K + 1, N], row K the bias (as ts_conv_forward's), in the order trunk | Q hidden | V hidden |
+ * Q head [., n_act] | V head [., 1] (plain Net: trunk | the last Linear as the Q head); no padding entries.
+ * ts_dqn_mlp_layout: h_out int64[16] = {floats of the flat vector, LDS bytes of a tile, workspace bytes at this B, offsets of
+ * trunk[0..3], q_hidden[0..1], v_hidden[0..1], Q head, V head (-1: absent)}. */
+#define TS_DQN_MLP_DESC_LEN 14
+int ts_dqn_mlp_layout(const int64_t* desc, int64_t B, int64_t* h_out);
+/* Net.forward + the greedy action (dqn.py:101-143): q_out float32[B, n_act] and act_out int64[B] = argmax, first index on
+ * ties; either may be NULL. */
+int ts_dqn_mlp_forward(const float* params, const int64_t* desc, const float* obs, int64_t B, float* q_out, int64_t* act_out,
+                       ts_stream_t stream);
+/* DQN._target_q (dqn.py:365-379) in one launch: out[b] = Q_old(s')[argmax Q_new(s')] (is_double) or max Q_old(s');
+ * params_old NULL = no lagged network.  With the three outputs of ts_nstep_coefficients (all or none) out[b] is instead
+ * float(double(target_q[b] * mask[b]) * gpow[b] + mc[b]), compute_nstep_return's arithmetic (as ts_dqn_target_returns). */
+int ts_dqn_mlp_target_q(const float* params, const float* params_old, const int64_t* desc, const float* obs_next, int64_t B,
+                        int is_double, const float* nstep_mask, const double* nstep_gpow, const double* nstep_mc, float* out,
+                        ts_stream_t stream);
+/* DQN._update_with_batch (dqn.py:381-404) in two launches.  sync_old != 0: params_old receives the parameters as they are
+ * BEFORE this step (dqn.py:283-285; written by the apply kernel).  td_out float32[B], loss_out float32[1]; grad_out
+ * (nullable) float32[count] receives the unclipped gradient; hp->lr < 0: gradient (and lagged copy) only.  The slabs are
+ * summed in tile order: the result is bit-identical from run to run.  hp->max_grad_norm > 0 adds ts_adam_step's launches. */
+int ts_dqn_mlp_update(ts_workspace* ws, float* params, float* params_old, int sync_old, float* adam_m, float* adam_v, int64_t adam_step,
+                      const int64_t* desc, const float* obs, const int64_t* act, const float* returns, const float* weight, int64_t B,
+                      const ts_dqn_hparams* hp, float* td_out, float* loss_out, float* grad_out, ts_stream_t stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * TD3 / DDPG: ContinuousActorDeterministic (utils/net/continuous.py:26-85) + the SAC critics,

@@ -131,6 +131,11 @@ def _bdqn_prototypes(lib) -> None:
         "ts_bdqn_loss": [p, p, p, p, p, i64_, i64_, i64_, p, p, p, p],
         "ts_bdqn_target_q": [p, p, p, *model, p, p, p, i64_, f64_, i32, p, p],
         "ts_bdqn_update": [p, p, p, p, i64_, *model, p, p, p, p, i64_, i32, f64_, f64_, f64_, f64_, f64_, f64_, f64_, i32, f64_, p, p, p, p],
+        # ts_dqn_mlp_* (desc: a host int64[TS_DQN_MLP_DESC_LEN])
+        "ts_dqn_mlp_layout": [p, i64_, p],
+        "ts_dqn_mlp_forward": [p, p, p, i64_, p, p, p],
+        "ts_dqn_mlp_target_q": [p, p, p, p, i64_, i32, p, p, p, p, p],
+        "ts_dqn_mlp_update": [p, p, p, i32, p, p, i64_, p, p, p, p, p, i64_, p, p, p, p, p],
     }
     for name, argtypes in protos.items():
         if hasattr(lib, name):                       # (a library built before these existed still serves every other engine)

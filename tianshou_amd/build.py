@@ -21,7 +21,10 @@ LIB = os.path.join(LIBDIR, "libtsengine.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 # per-file extra flags (experiments: TS_EXTRA_FLAGS="ts_ppo.hip:-mllvm -amdgpu-sched-strategy=max-ilp")
-EXTRA_FLAGS: dict[str, list[str]] = {}
+EXTRA_FLAGS: dict[str, list[str]] = {
+    # no packed-fp32 VALU forms in the element-wise tails of this file (every product and sum there is a scalar fp32 op)
+    "ts_dqn_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def _hipcc() -> str:

@@ -1737,6 +1737,62 @@ def make_hip_drqn(ref=None):
 
 
 # ---------------------------------------------------------------------------------------------------
+# DQN on the (dueling) MLP Net over vector observations (examples/discrete/discrete_dqn.py, box2d/lunarlander_dqn.py,
+# box2d/acrobot_dualdqn.py)
+# ---------------------------------------------------------------------------------------------------
+def make_hip_dqn_mlp(ref=None):
+    """Returns HipDQNMlp(DQN): the DQN hooks (dqn.py:257-275, 381-404) on tianshou_amd.dqn_mlp.DQNMlpEngine for a `Net`
+    (utils/net/common.py:246-370, with or without `dueling_param`) over a plain or prioritized buffer of vector observations:
+    `_target_q` + the n-step returns, the update and the optimizer step are three launches.  What is outside the envelope
+    (dqn_mlp.ENVELOPE) raises NotImplementedError in the constructor; nothing falls back to eager PyTorch.  `policy.forward` and
+    the collector's `add_exploration_noise` stay the reference's.
+    `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    DQN = _ref(ref, "tianshou.algorithm.modelfree.dqn", "DQN")
+    SimpleLossTrainingStats = _ref(ref, "tianshou.algorithm.modelfree.reinforce", "SimpleLossTrainingStats")
+
+    from . import dqn_mlp as M
+
+    class HipDQNMlp(_HipGlue, DQN):
+        def __init__(self, *args, device="cuda", **kwargs):
+            super().__init__(*args, **kwargs)
+            self._hip_device = torch.device(device)
+            self._hip_layers = M.describe_module(self.policy.model)
+            _adam_of(self.optim)
+            self._hip_engine = None
+            self._hip_glue_init()
+
+        def _hip_qstate(self):
+            layers = self._hip_layers             # what the engine was built with
+            return _QState(M.state_dict_keys(layers), M.flat_from_torch, M.flat_to_torch, lambda eng: layers)
+
+        def _engine(self):
+            if self._hip_engine is None:
+                layers = self._hip_layers
+                self._hip_engine = _q_load(self, M.DQNMlpEngine(layers, _q_flat(self, layers), _dqn_config(self)))
+            return self._hip_engine
+
+        def _preprocess_batch(self, batch, buffer, indices):
+            obs = np.asarray(buffer.obs)
+            if obs.ndim < 2 or int(np.prod(obs.shape[1:])) != self._hip_layers[0] or int(getattr(buffer, "stack_num", 1)) != 1:
+                raise NotImplementedError("HipDQNMlp: the buffer must hold vector observations of the model's state_shape, stack_num 1")
+            m, idx = _q_begin(self, "HipDQNMlp", batch, buffer, indices)
+            eng = self._engine()
+            rows = m.obs.reshape(m.obs.shape[0], -1)
+            nxt = m.obs_next.reshape(m.obs_next.shape[0], -1) if m.obs_next is not None else None
+            self._hip_obs, ret = eng.preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt)
+            batch.returns = ret.reshape(-1, 1)
+            return batch
+
+        def _update_with_batch(self, batch):
+            self._hip_refresh_lr()
+            return _dqn_update(self, batch, SimpleLossTrainingStats)
+
+        _hip_write_back = _q_write_back
+
+    return HipDQNMlp
+
+
+# ---------------------------------------------------------------------------------------------------
 # QRDQN (qrdqn.py) / C51 (c51.py) on QRDQNet / C51Net
 # ---------------------------------------------------------------------------------------------------
 def _make_hip_distq(kind: str, ref=None, cql: bool = False):
