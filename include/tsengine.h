@@ -1711,6 +1711,36 @@ int ts_dqn_mlp_update(ts_workspace* ws, float* params, float* params_old, int sy
                       const int64_t* desc, const float* obs, const int64_t* act, const float* returns, const float* weight, int64_t B,
                       const ts_dqn_hparams* hp, float* td_out, float* loss_out, float* grad_out, ts_stream_t stream);
 
+/* ---- QRDQN on vector observations (modelfree/qrdqn.py:94-131 on the plain `Net(softmax=False, num_atoms=N)`; the network of
+ * test/discrete/test_qrdqn.py): ts_dqn_mlp's tile scheme with the A N wide head walked action by action and the N^2 pair loss
+ * inside the tile (ts_qrdqn_mlp.hip).  Three launches per update: target, step, apply.
+ * `desc` is a HOST array of TS_QRDQN_MLP_DESC_LEN int64: the TS_DQN_MLP_DESC_LEN entries of ts_dqn_mlp (dueling, n_q and n_v must
+ * be 0) and the number of quantiles N.  Envelope (TS_ERR_UNSUPPORTED beyond it, before any HIP call): obs_dim in [1, 256], 1 .. 4
+ * hidden layers, every width a multiple of 32 in [32, 256], ReLU, 1 <= n_act <= 32, 2 <= N <= 256, 1 <= B <= 4096, and the LDS
+ * carve of one tile (activations + two [32][N | 1] tables) within 160 KB.
+ * Flat vector: per layer [K + 1, width], row K the bias; the hidden layers, then the head [top + 1, n_act N], column a N + j.
+ * ts_qrdqn_mlp_layout: h_out int64[16] = {floats of the flat vector, LDS bytes of a tile, workspace bytes at this B, offsets of
+ * trunk[0..3] (-1: absent), offset of the head}. */
+#define TS_QRDQN_MLP_DESC_LEN 15
+int ts_qrdqn_mlp_layout(const int64_t* desc, int64_t B, int64_t* h_out);
+/* Net.forward + QRDQNPolicy.compute_q_value + the greedy action: dist_out float32[B, n_act, N], q_out float32[B, n_act] = the
+ * mean over the quantiles, act_out int64[B] = argmax q, first index on ties; each may be NULL, not all. */
+int ts_qrdqn_mlp_forward(const float* params, const int64_t* desc, const float* obs, int64_t B, float* dist_out, float* q_out,
+                         int64_t* act_out, ts_stream_t stream);
+/* QRDQN._target_q (qrdqn.py:94-106) in one launch: out[b, :] = the quantiles of the action that the online network (is_double,
+ * with a lagged network) or the evaluating network itself selects, read from params_old (NULL = no lagged network).  With the
+ * three outputs of ts_nstep_coefficients (all or none) out[b, j] is instead float(double(out[b, j] * mask[b]) * gpow[b] + mc[b]). */
+int ts_qrdqn_mlp_target_dist(const float* params, const float* params_old, const int64_t* desc, const float* obs_next, int64_t B,
+                             int is_double, const float* nstep_mask, const double* nstep_gpow, const double* nstep_mc, float* out,
+                             ts_stream_t stream);
+/* QRDQN._update_with_batch (qrdqn.py:108-131) in two launches.  returns float32[B, N]; weight (nullable) float32[B]; tau_hat
+ * float32[N] (qrdqn.py:87-91).  loss_out float32[1] = mean_b(huber_b weight_b), prio_out float32[B] = the new priorities
+ * (qrdqn.py:128); sync_old, grad_out, hp->lr < 0 and hp->max_grad_norm as ts_dqn_mlp_update (hp->huber_delta is not read). */
+int ts_qrdqn_mlp_update(ts_workspace* ws, float* params, float* params_old, int sync_old, float* adam_m, float* adam_v, int64_t adam_step,
+                        const int64_t* desc, const float* obs, const int64_t* act, const float* returns, const float* weight,
+                        const float* tau_hat, int64_t B, const ts_dqn_hparams* hp, float* loss_out, float* prio_out, float* grad_out,
+                        ts_stream_t stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * TD3 / DDPG: ContinuousActorDeterministic (utils/net/continuous.py:26-85) + the SAC critics,

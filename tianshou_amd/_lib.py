@@ -136,6 +136,11 @@ def _bdqn_prototypes(lib) -> None:
         "ts_dqn_mlp_forward": [p, p, p, i64_, p, p, p],
         "ts_dqn_mlp_target_q": [p, p, p, p, i64_, i32, p, p, p, p, p],
         "ts_dqn_mlp_update": [p, p, p, i32, p, p, i64_, p, p, p, p, p, i64_, p, p, p, p, p],
+        # ts_qrdqn_mlp_* (desc: a host int64[TS_QRDQN_MLP_DESC_LEN])
+        "ts_qrdqn_mlp_layout": [p, i64_, p],
+        "ts_qrdqn_mlp_forward": [p, p, p, i64_, p, p, p, p],
+        "ts_qrdqn_mlp_target_dist": [p, p, p, p, i64_, i32, p, p, p, p, p],
+        "ts_qrdqn_mlp_update": [p, p, p, i32, p, p, i64_, p, p, p, p, p, p, i64_, p, p, p, p, p],
     }
     for name, argtypes in protos.items():
         if hasattr(lib, name):                       # (a library built before these existed still serves every other engine)

@@ -21,6 +21,8 @@
 
 #pragma clang fp contract(off)
 
+#include "ts_qr_terms.h"      // qr_terms: the inner sums of the quantile-Huber loss (shared with ts_qrdqn_mlp.hip)
+
 namespace ts {
 int adam_step(hipStream_t s, float* params, float* m, float* v, const float* grad, int64_t n, int64_t step,
               double lr, double beta1, double beta2, double eps, double max_grad_norm, float* norm_scratch);
@@ -150,26 +152,6 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {      // al
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// The quantile-Huber terms of one theta_i against the N targets T_j (the inner sums of the QRDQN loss below), shared by
-// qr_loss_kernel and cql_loss_kernel:  li = sum_j l_ij w_ij,  ai = sum_j l_ij,  g = sum_j w_ij clamp(d_ij, -1, 1)
-__device__ __forceinline__ void qr_terms(const float* T, int N, float theta, float tau, float& li, float& ai, float& g) {
-    float gc = 0.f;                                        // gc: compensation of g (Kahan)
-    li = 0.f; ai = 0.f; g = 0.f;
-    for (int j = 0; j < N; ++j) {
-        const float d = T[j] - theta, ad = fabsf(d);
-        const bool quad = ad < 1.f;
-        const float l = quad ? 0.5f * d * d : ad - 0.5f;
-        const float w = fabsf(tau - (d <= 0.f ? 1.f : 0.f));
-        li += l * w;
-        ai += l;
-        // in the linear region the N terms are all +-w: added one after the other they round the same way every time
-        // and the error grows with N (27 ulp of the sum at N = 255), so the gradient sum is compensated
-        const float y = w * (quad ? d : (d > 0.f ? 1.f : -1.f)) - gc, t = g + y;
-        gc = (t - g) - y;
-        g = t;
-    }
 }
 
 // ---- QRDQN loss (qrdqn.py:111-128), one workgroup per sample:

@@ -1,0 +1,503 @@
+// ts_qrdqn_mlp.hip -- QRDQN on vector observations: the plain MLP `Net(softmax=False, num_atoms=N)` (utils/net/common.py:286-369)
+// under QRDQN._target_q / _update_with_batch (modelfree/qrdqn.py:94-131) as three launches per update.
+//
+// The trunk is ts_dqn_mlp.hip's (ts_mlp_tile.h): one four-wave workgroup per 32-row tile, activations resident in odd-pitch LDS,
+// weights streamed from L2 into v_mfma_f32_32x32x2_f32 operands, a hidden layer's gradient overwrites its activation, one
+// gradient slab per tile summed in tile order by dqnm_apply_kernel.  New here are the A N wide head and the N^2 pair loss:
+//   * the head is walked ACTION BY ACTION, so the LDS footprint does not depend on A: action a's N columns are ceil(N / 32)
+//     MFMA column blocks (round-robin over the waves) whose weight loads are masked past column N (the address is clamped
+//     into the action's own columns, the value replaced by 0): N need be no multiple of 32, 4 or 2;
+//   * step kernel: a block's rows are stored only where act[m] == a, into a compact theta table [32][N | 1]; the n-step targets
+//     T sit in a second table of the same shape.  Actions that no row of the tile selected are skipped (a 32-bit presence mask
+//     in LDS, a workgroup-uniform branch);
+//   * pair loss in the tile: eight threads per row, thread t takes the quantiles i = t (mod 8) against all N targets of the
+//     row (qr_terms of ts_qr_terms.h: smooth-L1 with kappa 1, weight |tau_i - 1{d <= 0}|, compensated gradient sum); the eight
+//     partial sums of a row meet in a fixed butterfly; d theta overwrites theta;
+//   * head weight gradient: per present action an MFMA over the tile rows whose d theta operand is masked by act[m] == a; an
+//     absent action's slab columns are written as zeros with no matrix work.  Input gradient of the top hidden layer: the sum
+//     over the present actions of masked d theta W[:, aN .. aN + N)^T in one accumulator per 32-column block, ReLU mask in place;
+//   * target kernel: a "current" and a "kept" table; per action the quantile mean of every row, a running argmax (strictly
+//     greater: the first index wins ties) that copies current -> kept.  With a lagged network and double-Q selection the online
+//     pass leaves sel[32] only, the lagged pass keeps row sel (and skips actions nobody selected).  The epilogue writes
+//     float(double(theta' mask) gamma^n + mc) per quantile: compute_nstep_return's arithmetic on a [B, N] target.
+// Flat parameter vector: per layer [K + 1, N] (row K = bias), trunk layers then the head [top + 1, A N], column a N + j.
+#pragma clang fp contract(off)
+#include <algorithm>
+
+#include "ts_mlp_tile.h"
+#include "ts_qr_terms.h"
+
+namespace {
+
+constexpr int MAX_TRUNK = 4, MAX_ATOMS = 256, MAX_ACT = 32;
+constexpr int RPT = 8;                      // threads per row in the row-wise passes (THREADS / TILE)
+static_assert(RPT * TILE == THREADS, "thread (row, t) = (tid >> 3, tid & 7)");
+
+struct QNet {
+    int obs_dim, n_act, n_atoms, nt;
+    Lay t[MAX_TRUNK], head;                 // head: K = top width, N = n_act * n_atoms
+    int x_at, t_at[MAX_TRUNK];              // LDS float offsets of obs and of every hidden activation
+    int ta_at, tb_at, row_at, pitch;        // two [32][pitch] tables (pitch = n_atoms | 1), per-row scalars [4][32]
+    int P, lds_floats;
+};
+
+// the trunk on the tile whose observations are in LDS -> the top activation (LDS) and its pitch.  Ends behind a barrier.
+__device__ const float* trunk_forward(const QNet& net, const float* __restrict__ p, float* sm, int* ptop) {
+    const float* x = sm + net.x_at;
+    int px = net.obs_dim + 1;
+    for (int l = 0; l < net.nt; ++l) {
+        float* y = sm + net.t_at[l];
+        dense_relu(p + net.t[l].off, net.t[l].K, net.t[l].N, x, px, y, net.t[l].N + 1);
+        __syncthreads();
+        x = y; px = net.t[l].N + 1;
+    }
+    *ptop = px;
+    return x;
+}
+
+// out[m][c] = top[m][:] W[:, aN + c] + b[aN + c], c < N.  ROWSEL: only the rows with sel[m] == a are stored.
+template <bool ROWSEL>
+__device__ void head_action(const QNet& net, const float* __restrict__ p, int a, const float* top, int ptop, float* out, const int* sel) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
+    const int K = net.head.K, N = net.n_atoms, ld = net.head.N, pt = net.pitch;
+    const float* w = p + net.head.off + a * N;
+    for (int cb = wave; cb < (N + 31) / 32; cb += 4) {
+        const int c = cb * 32 + i;
+        const bool live = c < N;
+        const float* wp = w + (live ? c : 0);               // past column N: the action's first column is read, 0 is used
+        const float* xp = top + i * ptop + h;
+        f32x16 acc = {};
+#pragma unroll 8
+        for (int k = 0; k < K; k += 2) {                    // (K is a hidden width: even)
+            const float b = wp[(size_t)(k + h) * ld];
+            acc = mfma32(xp[k], live ? b : 0.f, acc);
+        }
+        const float bias = wp[(size_t)K * ld];
+        if (live) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = featF(r, h);
+                if (!ROWSEL || sel[m] == a) out[m * pt + c] = acc[r] + bias;
+            }
+        }
+    }
+}
+
+// the eight partial sums of a row (lanes 8 row .. 8 row + 7 of a wave) in a fixed butterfly: all eight threads hold the same bits
+__device__ __forceinline__ float row_sum8(float s) {
+    s += __shfl_xor(s, 1);
+    s += __shfl_xor(s, 2);
+    s += __shfl_xor(s, 4);
+    return s;
+}
+
+// ---- launch 1: QRDQN._target_q with the n-step arithmetic (INFER: Net.forward, the quantile means, the greedy action) -----------
+struct TargetArgs {
+    QNet net;
+    const float* params; const float* params_old;     // params_old NULL: no lagged network
+    const float* obs; int64_t B; int is_double;
+    float* dist_out; float* q_out; int64_t* act_out;    // INFER
+    float* out;                                         // target_dist[B, N], or the n-step returns when mask != NULL
+    const float* mask; const double* gpow; const double* mc;
+};
+
+enum { SCAN_INFER, SCAN_SELECT, SCAN_KEEP, SCAN_GATHER };
+
+// The head, action by action, on the tile whose top activation is in LDS.  SELECT / KEEP / INFER: the running argmax of the
+// quantile mean -> returned (thread (row, t): its row's); KEEP also leaves that action's row in `kept`.  GATHER: `kept` = the row
+// of action sel[row], actions outside `present` skipped.  Ends behind a barrier.
+template <int MODE>
+__device__ int head_scan(const QNet& net, const float* __restrict__ p, const float* top, int ptop, float* sm, const int* sel, unsigned present,
+                         const TargetArgs& a, int64_t b) {
+    float* cur = sm + net.ta_at;
+    float* kept = sm + net.tb_at;
+    const int N = net.n_atoms, A = net.n_act, pt = net.pitch, row = threadIdx.x >> 3, t = threadIdx.x & 7;
+    float best = 0.f;
+    int arg = 0;
+    for (int act = 0; act < A; ++act) {
+        if (MODE == SCAN_GATHER && !((present >> act) & 1)) continue;          // workgroup-uniform
+        head_action<false>(net, p, act, top, ptop, cur, nullptr);
+        __syncthreads();
+        const float* mine = cur + row * pt;
+        bool take;
+        if (MODE == SCAN_GATHER) {
+            take = sel[row] == act;
+        } else {
+            float s = 0.f;
+            for (int j = t; j < N; j += RPT) s += mine[j];
+            const float q = row_sum8(s) / (float)N;
+            take = act == 0 || q > best;                                       // strictly greater: the first index wins ties
+            if (take) { best = q; arg = act; }
+            if (MODE == SCAN_INFER && b < a.B) {
+                if (a.dist_out) for (int j = t; j < N; j += RPT) a.dist_out[(b * A + act) * N + j] = mine[j];
+                if (a.q_out && t == 0) a.q_out[b * A + act] = q;
+            }
+        }
+        if ((MODE == SCAN_KEEP || MODE == SCAN_GATHER) && take)
+            for (int j = t; j < N; j += RPT) kept[row * pt + j] = mine[j];
+        __syncthreads();                                                       // the next action overwrites `cur`
+    }
+    return arg;
+}
+
+template <bool INFER>
+__global__ __launch_bounds__(THREADS) void qrm_target_kernel(TargetArgs a) {
+    extern __shared__ float sm[];
+    const QNet& net = stage_net(a.net);
+    const int64_t row0 = (int64_t)blockIdx.x * TILE;
+    const int row = threadIdx.x >> 3, t = threadIdx.x & 7;
+    const int64_t b = row0 + row;
+    load_obs(net, a.obs, row0, a.B, sm);
+    int* sel = reinterpret_cast<int*>(sm + net.row_at + TILE);
+    unsigned* present = reinterpret_cast<unsigned*>(sm + net.row_at + 2 * TILE);
+    int ptop;
+    if (INFER) {
+        const float* top = trunk_forward(net, a.params, sm, &ptop);
+        const int arg = head_scan<SCAN_INFER>(net, a.params, top, ptop, sm, nullptr, 0u, a, b);
+        if (a.act_out && t == 0 && b < a.B) a.act_out[b] = arg;
+        return;
+    }
+    // the selecting network is needed only for the double-Q gather from a lagged network; otherwise the evaluating one selects
+    const bool two = a.params_old != nullptr && a.is_double;
+    const float* pe = a.params_old ? a.params_old : a.params;
+    if (two) {
+        const float* top = trunk_forward(net, a.params, sm, &ptop);
+        const int arg = head_scan<SCAN_SELECT>(net, a.params, top, ptop, sm, nullptr, 0u, a, b);
+        if (t == 0) sel[row] = arg;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned m = 0u;
+            for (int r = 0; r < TILE; ++r) m |= 1u << sel[r];
+            *present = m;
+        }
+        top = trunk_forward(net, pe, sm, &ptop);                               // (its barriers publish `present`)
+        head_scan<SCAN_GATHER>(net, pe, top, ptop, sm, sel, *present, a, b);
+    } else {
+        const float* top = trunk_forward(net, pe, sm, &ptop);
+        head_scan<SCAN_KEEP>(net, pe, top, ptop, sm, nullptr, 0u, a, b);
+    }
+    if (b >= a.B) return;
+    const int N = net.n_atoms;
+    const float* kept = sm + net.tb_at + row * net.pitch;
+    if (a.mask) {                                                              // compute_nstep_return's arithmetic, per quantile
+        const float mk = a.mask[b];
+        const double gp = a.gpow[b], mc = a.mc[b];
+        for (int j = t; j < N; j += RPT) a.out[b * N + j] = (float)((double)(kept[j] * mk) * gp + mc);
+    } else {
+        for (int j = t; j < N; j += RPT) a.out[b * N + j] = kept[j];
+    }
+}
+
+// ---- launch 2: forward, pair loss, backward, the tile's slab ---------------------------------------------------------------------
+
+// the head's part of the slab: for action a the columns [aN, aN + N) of rows 0 .. K (row K = bias) = sum over the rows m with
+// sel[m] == a of top[m][k] dth[m][c]; an absent action's columns are zeros
+__device__ void head_wgrad(const QNet& net, float* __restrict__ slab, const float* top, int ptop, const float* dth, const int* sel, unsigned present) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
+    const int K = net.head.K, N = net.n_atoms, ld = net.head.N, pt = net.pitch;
+    const int cbs = (N + 31) / 32, kbs = K / 32;
+    for (int a = 0; a < net.n_act; ++a) {
+        float* sa = slab + a * N;
+        if (!((present >> a) & 1)) {                                           // workgroup-uniform
+            for (int idx = threadIdx.x; idx < (K + 1) * N; idx += THREADS) {
+                const int k = idx / N, c = idx - k * N;
+                sa[(size_t)k * ld + c] = 0.f;
+            }
+            continue;
+        }
+        for (int blk = wave; blk < kbs * cbs; blk += 4) {
+            const int kb = blk / cbs, cb = blk - kb * cbs;
+            const int kc = kb * 32 + i, c = cb * 32 + i;
+            const bool live = c < N;
+            const float* zp = dth + (live ? c : 0);
+            f32x16 acc = {};
+#pragma unroll
+            for (int m = 0; m < TILE; m += 2) {
+                const float z = zp[(m + h) * pt];
+                acc = mfma32(top[(m + h) * ptop + kc], live && sel[m + h] == a ? z : 0.f, acc);
+            }
+            if (live) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) sa[(size_t)(kb * 32 + featF(r, h)) * ld + c] = acc[r];
+            }
+        }
+        for (int c = threadIdx.x; c < N; c += THREADS) {
+            float s = 0.f;
+            for (int m = 0; m < TILE; ++m) s += sel[m] == a ? dth[m * pt + c] : 0.f;
+            sa[(size_t)K * ld + c] = s;
+        }
+    }
+}
+
+// top[32][K] <- (sum over the present actions a of (dth masked by sel == a) W[:, aN .. aN + N)^T) * (top > 0), in place.  Block k on
+// wave k mod 4; A(i, c) = dth[i][c] from LDS, B(c, i) = W[k0 + i][aN + c] along c (N and aN need no alignment: 4-byte loads)
+__device__ void head_dgrad(const QNet& net, const float* __restrict__ p, float* top, int ptop, const float* dth, const int* sel, unsigned present) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
+    const int K = net.head.K, N = net.n_atoms, ld = net.head.N, pt = net.pitch;
+    const int mysel = sel[i];
+    const float* zp = dth + i * pt;
+    for (int kb = wave; kb < K / 32; kb += 4) {
+        const int kc = kb * 32 + i;
+        const float* wrow = p + net.head.off + (size_t)kc * ld;
+        f32x16 acc = {};
+        for (int a = 0; a < net.n_act; ++a) {
+            if (!((present >> a) & 1)) continue;                               // workgroup-uniform
+            const bool mine = mysel == a;
+            const float* wa = wrow + a * N;
+#pragma unroll 4
+            for (int c = 0; c < N; c += 2) {
+                const bool in = c + h < N;                                     // odd N: the last pair is half empty
+                const int cc = in ? c + h : 0;
+                const float z = zp[cc], w = wa[cc];
+                acc = mfma32(in && mine ? z : 0.f, in ? w : 0.f, acc);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float* q = top + featF(r, h) * ptop + kc;
+            *q = *q > 0.f ? acc[r] : 0.f;
+        }
+    }
+}
+
+struct StepArgs {
+    QNet net;
+    const float* params; const float* obs; const int64_t* act; const float* returns; const float* weight; const float* tau_hat;
+    int64_t B;
+    float* prio_out; float* slabs; float* partials;
+};
+
+__global__ __launch_bounds__(THREADS) void qrm_step_kernel(StepArgs a) {
+    extern __shared__ float sm[];
+    const QNet& net = stage_net(a.net);
+    const int64_t row0 = (int64_t)blockIdx.x * TILE;
+    const float* p = a.params;
+    float* slab = a.slabs + (size_t)blockIdx.x * net.P;
+    float* th = sm + net.ta_at;                              // theta of the taken action, then d loss / d theta
+    float* tg = sm + net.tb_at;                              // the targets T
+    float* term = sm + net.row_at;
+    int* sel = reinterpret_cast<int*>(sm + net.row_at + TILE);
+    unsigned* present = reinterpret_cast<unsigned*>(sm + net.row_at + 2 * TILE);
+    const int N = net.n_atoms, A = net.n_act, pt = net.pitch;
+    if (threadIdx.x < TILE) {                                // rows beyond B select nothing: exactly zero in the loss and in every slab
+        const int64_t b = row0 + threadIdx.x;
+        int s = -1;
+        if (b < a.B) {
+            const int64_t ab = a.act[b];
+            s = ab < 0 ? 0 : ab >= A ? A - 1 : (int)ab;
+        }
+        sel[threadIdx.x] = s;
+    }
+    for (int idx = threadIdx.x; idx < TILE * pt; idx += THREADS) {
+        const int row = idx / pt, j = idx - row * pt;
+        th[idx] = 0.f;
+        tg[idx] = row0 + row < a.B && j < N ? a.returns[(row0 + row) * N + j] : 0.f;
+    }
+    load_obs(net, a.obs, row0, a.B, sm);
+    if (threadIdx.x == 0) {
+        unsigned m = 0u;
+        for (int r = 0; r < TILE; ++r) if (sel[r] >= 0) m |= 1u << sel[r];
+        *present = m;
+    }
+    int ptop;
+    float* top = const_cast<float*>(trunk_forward(net, p, sm, &ptop));         // (its barriers publish `present`)
+    const unsigned pres = *present;
+    for (int act = 0; act < A; ++act)
+        if ((pres >> act) & 1) head_action<true>(net, p, act, top, ptop, th, sel);     // disjoint rows: no barrier between actions
+    __syncthreads();
+    {   // the pair loss of row (tid >> 3): thread t takes theta_i, i = t (mod 8), against the row's N targets
+        const int row = threadIdx.x >> 3, t = threadIdx.x & 7;
+        const int64_t b = row0 + row;
+        const bool live = b < a.B;
+        const float wb = live ? (a.weight ? a.weight[b] : 1.f) : 0.f;
+        const float scale = wb / ((float)a.B * (float)N);
+        float wl = 0.f, sl = 0.f;
+        if (live) {
+            float* mine = th + row * pt;
+            for (int i = t; i < N; i += RPT) {
+                float li, ai, g;
+                qr_terms(tg + row * pt, N, mine[i], a.tau_hat[i], li, ai, g);
+                mine[i] = -g * scale;                        // only this thread reads theta_i
+                wl += li;
+                sl += ai;
+            }
+        }
+        wl = row_sum8(wl);
+        sl = row_sum8(sl);
+        if (t == 0) {
+            const float huber = wl / (float)N;
+            if (live) a.prio_out[b] = sl / (float)N;
+            term[row] = live ? huber * wb / (float)a.B : 0.f;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int m = 0; m < TILE; ++m) s += term[m];
+        a.partials[blockIdx.x] = s;
+    }
+    head_wgrad(net, slab + net.head.off, top, ptop, th, sel, pres);
+    __syncthreads();
+    head_dgrad(net, p, top, ptop, th, sel, pres);
+    __syncthreads();
+    for (int l = net.nt - 1; l >= 0; --l) {
+        const float* in = l > 0 ? sm + net.t_at[l - 1] : sm + net.x_at;
+        wgrad(slab + net.t[l].off, in, l > 0 ? net.t[l - 1].N + 1 : net.obs_dim + 1, net.t[l].K, sm + net.t_at[l], net.t[l].N + 1, net.t[l].N);
+        if (l == 0) break;
+        __syncthreads();
+        MSrc ms{sm + net.t_at[l], net.t[l].N + 1, p + net.t[l].off, net.t[l].N};
+        dgrad(sm + net.t_at[l - 1], net.t[l - 1].N + 1, net.t[l - 1].N, ms, MSrc{}, HSrc{}, HSrc{});
+        __syncthreads();
+    }
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------
+
+// desc (host, TS_QRDQN_MLP_DESC_LEN int64): ts_dqn_mlp's 14 entries {obs_dim, n_act, dueling, n_trunk, n_q, n_v, trunk[4], q_hidden[2],
+// v_hidden[2]} and the number of quantiles.  LDS carve of one tile, in floats: obs 32 (obs_dim + 1) + sum over the hidden layers of
+// 32 (width + 1) + 2 x 32 (N | 1) (the two tables) + 4 x 32 (per-row scalars), and 256 bytes for the staged description.  Checked:
+//   test_qrdqn.py   obs 4, [128] x 4, A = 2, N = 200: 160 + 4 x 4,128 + 2 x 6,432 + 128 = 29,664 floats = 118,912 B
+//   LunarLander     obs 8, [128] x 4, A = 4, N = 200: 288 + 4 x 4,128 + 2 x 6,432 + 128 = 29,792 floats = 119,424 B
+//   (refused) [256] x 4, N = 256: 4 x 8,224 + 2 x 8,224 = 49,344 floats > 163,840 B
+int make_net(const int64_t* d, const char* who, QNet* out) {
+    TS_REQUIRE(d != nullptr, TS_ERR_INVALID_ARG, "%s: NULL network description", who);
+    QNet n{};
+    const int64_t obs_dim = d[0], n_act = d[1], nt = d[3], n_atoms = d[14];
+    TS_REQUIRE(obs_dim >= 1 && obs_dim <= 256, TS_ERR_UNSUPPORTED, "%s: obs_dim %lld outside [1, 256]", who, (long long)obs_dim);
+    TS_REQUIRE(n_act >= 1 && n_act <= MAX_ACT, TS_ERR_UNSUPPORTED, "%s: %lld actions outside [1, 32]", who, (long long)n_act);
+    TS_REQUIRE(n_atoms >= 2 && n_atoms <= MAX_ATOMS, TS_ERR_UNSUPPORTED, "%s: %lld quantiles outside [2, 256]", who, (long long)n_atoms);
+    TS_REQUIRE(nt >= 1 && nt <= MAX_TRUNK, TS_ERR_UNSUPPORTED, "%s: %lld trunk hidden layers outside [1, 4]", who, (long long)nt);
+    TS_REQUIRE(d[2] == 0 && d[4] == 0 && d[5] == 0, TS_ERR_UNSUPPORTED, "%s: a dueling head with quantiles is not supported", who);
+    n.obs_dim = (int)obs_dim; n.n_act = (int)n_act; n.n_atoms = (int)n_atoms; n.nt = (int)nt;
+    int off = 0, at = 0;
+    auto add = [&](Lay* l, int K, int N) { l->K = K; l->N = N; l->off = off; off += (K + 1) * N; };
+    auto carve = [&](int floats) { const int o = at; at += floats; return o; };
+    n.x_at = carve(TILE * (n.obs_dim + 1));
+    int k = n.obs_dim;
+    for (int i = 0; i < n.nt; ++i) {
+        const int64_t w = d[6 + i];
+        TS_REQUIRE(w >= 32 && w <= 256 && w % 32 == 0, TS_ERR_UNSUPPORTED, "%s: hidden width %lld is no multiple of 32 in [32, 256]", who, (long long)w);
+        add(&n.t[i], k, (int)w);
+        n.t_at[i] = carve(TILE * (n.t[i].N + 1));
+        k = n.t[i].N;
+    }
+    add(&n.head, k, n.n_act * n.n_atoms);
+    n.pitch = n.n_atoms | 1;
+    n.ta_at = carve(TILE * n.pitch);
+    n.tb_at = carve(TILE * n.pitch);
+    n.row_at = carve(4 * TILE);
+    n.P = off;
+    n.lds_floats = at;
+    TS_REQUIRE((size_t)at * 4 + 256 <= (size_t)LDS_LIMIT, TS_ERR_UNSUPPORTED,
+               "%s: the activations and quantile tables of one 32-row tile need %zu bytes of LDS, the workgroup limit is %d", who,
+               (size_t)at * 4 + 256, LDS_LIMIT);
+    *out = n;
+    return TS_OK;
+}
+
+inline int64_t tiles_of(int64_t B) { return ts::ceil_div(B, TILE); }
+inline size_t ws_bytes(const QNet& n, int64_t B) { return ((size_t)tiles_of(B) * n.P + (size_t)tiles_of(B) + (size_t)n.P) * 4 + 4096 + 1024; }
+
+template <typename Kern>
+int allow_lds(ts::DynLds& slot, Kern kern, const QNet& n) {
+    return slot.allow(reinterpret_cast<const void*>(kern), (size_t)n.lds_floats * 4);
+}
+
+int check_batch(int64_t B, const char* who) {
+    TS_REQUIRE(B >= 1 && B <= 4096, B < 1 ? TS_ERR_INVALID_ARG : TS_ERR_UNSUPPORTED, "%s: B = %lld outside [1, 4096]", who, (long long)B);
+    return TS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ts_qrdqn_mlp_layout(const int64_t* desc, int64_t B, int64_t* h_out) {
+    TS_REQUIRE(h_out != nullptr, TS_ERR_INVALID_ARG, "ts_qrdqn_mlp_layout: NULL output");
+    QNet n;
+    if (int rc = make_net(desc, "ts_qrdqn_mlp_layout", &n)) return rc;
+    if (int rc = check_batch(B, "ts_qrdqn_mlp_layout")) return rc;
+    h_out[0] = n.P;
+    h_out[1] = (int64_t)n.lds_floats * 4 + 256;
+    h_out[2] = (int64_t)ws_bytes(n, B);
+    for (int i = 0; i < MAX_TRUNK; ++i) h_out[3 + i] = i < n.nt ? n.t[i].off : -1;
+    h_out[7] = n.head.off;
+    return TS_OK;
+}
+
+int ts_qrdqn_mlp_forward(const float* params, const int64_t* desc, const float* obs, int64_t B, float* dist_out, float* q_out,
+                         int64_t* act_out, ts_stream_t stream) {
+    QNet n;
+    if (int rc = make_net(desc, "ts_qrdqn_mlp_forward", &n)) return rc;
+    if (int rc = check_batch(B, "ts_qrdqn_mlp_forward")) return rc;
+    TS_REQUIRE(params && obs && (dist_out || q_out || act_out), TS_ERR_INVALID_ARG, "ts_qrdqn_mlp_forward: NULL argument");
+    static ts::DynLds lds;
+    if (int rc = allow_lds(lds, qrm_target_kernel<true>, n)) return rc;
+    TargetArgs a{n, params, nullptr, obs, B, 0, dist_out, q_out, act_out, nullptr, nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL(qrm_target_kernel<true>, dim3((unsigned)tiles_of(B)), dim3(THREADS), (size_t)n.lds_floats * 4, ts::as_stream(stream), a);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+int ts_qrdqn_mlp_target_dist(const float* params, const float* params_old, const int64_t* desc, const float* obs_next, int64_t B,
+                             int is_double, const float* nstep_mask, const double* nstep_gpow, const double* nstep_mc, float* out,
+                             ts_stream_t stream) {
+    QNet n;
+    if (int rc = make_net(desc, "ts_qrdqn_mlp_target_dist", &n)) return rc;
+    if (int rc = check_batch(B, "ts_qrdqn_mlp_target_dist")) return rc;
+    TS_REQUIRE(params && obs_next && out, TS_ERR_INVALID_ARG, "ts_qrdqn_mlp_target_dist: NULL argument");
+    TS_REQUIRE((nstep_mask != nullptr) == (nstep_gpow != nullptr) && (nstep_mask != nullptr) == (nstep_mc != nullptr), TS_ERR_INVALID_ARG,
+               "ts_qrdqn_mlp_target_dist: the three n-step coefficient arrays come together or not at all");
+    static ts::DynLds lds;
+    if (int rc = allow_lds(lds, qrm_target_kernel<false>, n)) return rc;
+    TargetArgs a{n, params, params_old == params ? nullptr : params_old, obs_next, B, is_double, nullptr, nullptr, nullptr, out,
+                 nstep_mask, nstep_gpow, nstep_mc};
+    hipLaunchKernelGGL(qrm_target_kernel<false>, dim3((unsigned)tiles_of(B)), dim3(THREADS), (size_t)n.lds_floats * 4, ts::as_stream(stream), a);
+    TS_LAUNCH_CHECK();
+    return TS_OK;
+}
+
+int ts_qrdqn_mlp_update(ts_workspace* ws, float* params, float* params_old, int sync_old, float* adam_m, float* adam_v, int64_t adam_step,
+                        const int64_t* desc, const float* obs, const int64_t* act, const float* returns, const float* weight,
+                        const float* tau_hat, int64_t B, const ts_dqn_hparams* hp, float* loss_out, float* prio_out, float* grad_out,
+                        ts_stream_t stream) {
+    QNet n;
+    if (int rc = make_net(desc, "ts_qrdqn_mlp_update", &n)) return rc;
+    if (int rc = check_batch(B, "ts_qrdqn_mlp_update")) return rc;
+    TS_REQUIRE(params && adam_m && adam_v && obs && act && returns && tau_hat && hp && loss_out && prio_out, TS_ERR_INVALID_ARG,
+               "ts_qrdqn_mlp_update: NULL argument");
+    TS_REQUIRE(adam_step >= 1, TS_ERR_INVALID_ARG, "ts_qrdqn_mlp_update: adam_step is 1-based");
+    TS_REQUIRE(!sync_old || params_old, TS_ERR_INVALID_ARG, "ts_qrdqn_mlp_update: sync_old without a lagged network");
+    TS_REQUIRE(ws != nullptr, TS_ERR_WORKSPACE, "ts_qrdqn_mlp_update: workspace is NULL");
+    if (int rc = ts::ws_reserve(ws, ws_bytes(n, B))) return rc;
+    hipStream_t s = ts::as_stream(stream);
+    const int tiles = (int)tiles_of(B);
+    float* slabs = static_cast<float*>(ws->base);
+    float* partials = slabs + (size_t)tiles * n.P;
+    float* grad_ws = partials + ((tiles + 63) / 64) * 64;
+    float* norm_part = grad_ws + ((n.P + 63) / 64) * 64;            // 1024 floats behind it (ws_bytes' tail)
+    static ts::DynLds lds;
+    if (int rc = allow_lds(lds, qrm_step_kernel, n)) return rc;
+    StepArgs sa{n, params, obs, act, returns, weight, tau_hat, B, prio_out, slabs, partials};
+    hipLaunchKernelGGL(qrm_step_kernel, dim3((unsigned)tiles), dim3(THREADS), (size_t)n.lds_floats * 4, s, sa);
+    TS_LAUNCH_CHECK();
+    const bool step = hp->lr >= 0.0, clip = step && hp->max_grad_norm > 0.0;
+    ApplyArgs aa{};
+    aa.p = params; aa.m = adam_m; aa.v = adam_v; aa.p_old = sync_old ? params_old : nullptr;
+    aa.slabs = slabs; aa.partials = partials; aa.tiles = tiles; aa.P = n.P;
+    aa.grad_out = grad_out ? grad_out : (clip ? grad_ws : nullptr);
+    aa.loss_out = loss_out;
+    aa.adam = step && !clip;               // clip_grad_norm_ needs the whole gradient first: the sum here, then ts_adam_step's kernels
+    float sc[2];
+    ts::adam_step_scalars(adam_step, hp->lr, hp->beta1, hp->beta2, sc);
+    aa.lr_step = sc[0]; aa.bc2_sqrt = sc[1];
+    aa.beta2 = (float)hp->beta2; aa.eps = (float)hp->adam_eps;
+    aa.omb1 = (float)(1.0 - hp->beta1); aa.omb2 = (float)(1.0 - hp->beta2);
+    hipLaunchKernelGGL(dqnm_apply_kernel, dim3((unsigned)ts::ceil_div(n.P, THREADS)), dim3(THREADS), 0, s, aa);
+    TS_LAUNCH_CHECK();
+    if (!clip) return TS_OK;
+    return ts::optim_step(s, ts::OptimDesc{}, params, adam_m, adam_v, aa.grad_out, n.P, adam_step, hp->lr, hp->beta1, hp->beta2,
+                          hp->adam_eps, hp->max_grad_norm, norm_part);
+}
+
+}  // extern "C"

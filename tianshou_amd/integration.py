@@ -1793,6 +1793,72 @@ def make_hip_dqn_mlp(ref=None):
 
 
 # ---------------------------------------------------------------------------------------------------
+# QRDQN on the plain MLP Net with num_atoms quantiles per action (test/discrete/test_qrdqn.py)
+# ---------------------------------------------------------------------------------------------------
+def make_hip_qrdqn_mlp(ref=None):
+    """Returns HipQRDQNMlp(QRDQN): the QRDQN hooks (qrdqn.py:94-131) on tianshou_amd.qrdqn_mlp.QRDQNMlpEngine for a
+    `Net(softmax=False, num_atoms=num_quantiles)` over a plain or prioritized buffer of vector observations: `_target_q` + the
+    n-step returns ([B, N]), the update and the optimizer step are three launches.  What is outside the envelope
+    (qrdqn_mlp.ENVELOPE) raises NotImplementedError in the constructor; nothing falls back to eager PyTorch.  `policy.forward` and
+    the collector's `add_exploration_noise` stay the reference's.
+    `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    QRDQN = _ref(ref, "tianshou.algorithm.modelfree.qrdqn", "QRDQN")
+    SimpleLossTrainingStats = _ref(ref, "tianshou.algorithm.modelfree.reinforce", "SimpleLossTrainingStats")
+
+    from . import dqn as D
+    from . import qrdqn_mlp as M
+
+    class HipQRDQNMlp(_HipGlue, QRDQN):
+        def __init__(self, *args, device="cuda", **kwargs):
+            super().__init__(*args, **kwargs)
+            self._hip_device = torch.device(device)
+            self._hip_layers = M.describe_module(self.policy.model)
+            if self._hip_layers[3] != int(self.num_quantiles):
+                raise NotImplementedError(f"HipQRDQNMlp: the Net has num_atoms = {self._hip_layers[3]}, the algorithm num_quantiles = "
+                                          f"{self.num_quantiles}")
+            _adam_of(self.optim)
+            self._hip_engine = None
+            self._hip_glue_init()
+
+        def _hip_qstate(self):
+            layers = self._hip_layers             # what the engine was built with
+            return _QState(M.state_dict_keys(layers), M.flat_from_torch, M.flat_to_torch, lambda eng: layers)
+
+        def _engine(self):
+            if self._hip_engine is None:
+                layers = self._hip_layers
+                cfg = D.DQNConfig(is_double=True, **_q_config_fields(self))      # qrdqn.py:99-101: the online network selects
+                self._hip_engine = _q_load(self, M.QRDQNMlpEngine(layers, _q_flat(self, layers), cfg))
+            return self._hip_engine
+
+        def _preprocess_batch(self, batch, buffer, indices):
+            obs = np.asarray(buffer.obs)
+            if obs.ndim < 2 or int(np.prod(obs.shape[1:])) != self._hip_layers[0] or int(getattr(buffer, "stack_num", 1)) != 1:
+                raise NotImplementedError("HipQRDQNMlp: the buffer must hold vector observations of the model's state_shape, stack_num 1")
+            m, idx = _q_begin(self, "HipQRDQNMlp", batch, buffer, indices)
+            eng = self._engine()
+            rows = m.obs.reshape(m.obs.shape[0], -1)
+            nxt = m.obs_next.reshape(m.obs_next.shape[0], -1) if m.obs_next is not None else None
+            self._hip_obs, batch.returns = eng.preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt)
+            return batch
+
+        def _update_with_batch(self, batch):
+            self._hip_refresh_lr()
+            eng, m = self._hip_engine, self._hip_mirror
+            weight = batch.pop("weight", None)
+            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device) if hasattr(batch, "act") else m.act[self._hip_idx]
+            loss, prio = eng.update_with_batch(self._hip_obs, act, batch.returns, weight)
+            self._iter = eng.iter
+            batch.weight = prio                                                   # prio-buffer, qrdqn.py:128
+            self._hip_after_update()
+            return SimpleLossTrainingStats(loss=float(loss.item()))
+
+        _hip_write_back = _q_write_back
+
+    return HipQRDQNMlp
+
+
+# ---------------------------------------------------------------------------------------------------
 # QRDQN (qrdqn.py) / C51 (c51.py) on QRDQNet / C51Net
 # ---------------------------------------------------------------------------------------------------
 def _make_hip_distq(kind: str, ref=None, cql: bool = False):
