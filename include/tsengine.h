@@ -1741,6 +1741,35 @@ int ts_qrdqn_mlp_update(ts_workspace* ws, float* params, float* params_old, int 
                         const float* tau_hat, int64_t B, const ts_dqn_hparams* hp, float* loss_out, float* prio_out, float* grad_out,
                         ts_stream_t stream);
 
+/* ---- C51 on vector observations (modelfree/c51.py:120-160 on the plain `Net(softmax=True, num_atoms=N)`; the network of
+ * test/discrete/test_c51.py): the tile and the action-by-action head of ts_qrdqn_mlp with a softmax over the atoms of each action,
+ * the categorical projection and the cross-entropy inside the tile (ts_c51_mlp.hip).  Two launches per update: step, apply.
+ * `desc` is the HOST array of the QRDQN-MLP route (TS_C51_MLP_DESC_LEN int64, entry 14 = the number of atoms N); the envelope is
+ * that route's, with three [32][N | 1] tables in the LDS carve of a tile.  `support` is a DEVICE float32[N]
+ * (torch.linspace(v_min, v_max, N), as C51Policy builds it); delta_z = (v_max - v_min) / (N - 1) as C51 computes it, rounded to float.
+ * Flat vector and ts_c51_mlp_layout's h_out: as ts_qrdqn_mlp_layout. */
+#define TS_C51_MLP_DESC_LEN 15
+int ts_c51_mlp_layout(const int64_t* desc, int64_t B, int64_t* h_out);
+/* Net.forward (softmax over the atoms) + C51Policy.compute_q_value + the greedy action: dist_out float32[B, n_act, N] probabilities,
+ * q_out float32[B, n_act] = sum_j p_j z_j, act_out int64[B] = argmax q, first index on ties; each may be NULL, not all. */
+int ts_c51_mlp_forward(const float* params, const int64_t* desc, const float* support, const float* obs, int64_t B, float* dist_out,
+                       float* q_out, int64_t* act_out, ts_stream_t stream);
+/* C51._target_dist (c51.py:123-141) in one launch: the online network selects, params_old (NULL or == params: the online network
+ * itself, read once) gives next_dist; out float32[B, N] = the projection of clamp(returns, v_min, v_max) onto the support. */
+int ts_c51_mlp_target_dist(const float* params, const float* params_old, const int64_t* desc, const float* support, float v_min,
+                           float v_max, float delta_z, const float* obs_next, const float* returns, int64_t B, float* out,
+                           ts_stream_t stream);
+/* C51._update_with_batch (c51.py:143-160) in two launches; the target distribution is a phase of the step kernel.  sync_old != 0:
+ * the target is read from `params` alone (the sync precedes the target, c51.py:147-149) and params_old receives the parameters as
+ * they are BEFORE this step.  returns float32[B, N] = the n-step returns of the support; weight (nullable) float32[B].  loss_out
+ * float32[1] = mean_b(ce_b weight_b), prio_out float32[B] = ce_b (c51.py:157); target_out (nullable) float32[B, N]; grad_out,
+ * hp->lr < 0 and hp->max_grad_norm as ts_dqn_mlp_update (hp->huber_delta is not read). */
+int ts_c51_mlp_update(ts_workspace* ws, float* params, float* params_old, int sync_old, float* adam_m, float* adam_v, int64_t adam_step,
+                      const int64_t* desc, const float* support, float v_min, float v_max, float delta_z, const float* obs,
+                      const int64_t* act, const float* obs_next, const float* returns, const float* weight, int64_t B,
+                      const ts_dqn_hparams* hp, float* loss_out, float* prio_out, float* grad_out, float* target_out,
+                      ts_stream_t stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * TD3 / DDPG: ContinuousActorDeterministic (utils/net/continuous.py:26-85) + the SAC critics,

@@ -122,7 +122,7 @@ def load() -> C.CDLL:
 
 def _bdqn_prototypes(lib) -> None:
     """ts_bdqn_* (include/tsengine.h): with argtypes ctypes checks the arity and the kind of every argument of these calls."""
-    p, i64_, i32, f64_ = C.c_void_p, C.c_int64, C.c_int32, C.c_double
+    p, i64_, i32, f64_, f32 = C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_float
     model = [p, i64_, i64_, i64_, i64_]              # common_net, value_hidden, action_hidden, num_branches, action_per_branch
     protos = {
         "ts_bdqn_layout": [*model, p],
@@ -141,6 +141,11 @@ def _bdqn_prototypes(lib) -> None:
         "ts_qrdqn_mlp_forward": [p, p, p, i64_, p, p, p, p],
         "ts_qrdqn_mlp_target_dist": [p, p, p, p, i64_, i32, p, p, p, p, p],
         "ts_qrdqn_mlp_update": [p, p, p, i32, p, p, i64_, p, p, p, p, p, p, i64_, p, p, p, p, p],
+        # ts_c51_mlp_* (the same desc; v_min, v_max, delta_z as C floats)
+        "ts_c51_mlp_layout": [p, i64_, p],
+        "ts_c51_mlp_forward": [p, p, p, p, i64_, p, p, p, p],
+        "ts_c51_mlp_target_dist": [p, p, p, p, f32, f32, f32, p, p, i64_, p, p],
+        "ts_c51_mlp_update": [p, p, p, i32, p, p, i64_, p, p, f32, f32, f32, p, p, p, p, p, i64_, p, p, p, p, p, p],
     }
     for name, argtypes in protos.items():
         if hasattr(lib, name):                       # (a library built before these existed still serves every other engine)

@@ -25,6 +25,7 @@ EXTRA_FLAGS: dict[str, list[str]] = {
     # no packed-fp32 VALU forms in the element-wise tails of this file (every product and sum there is a scalar fp32 op)
     "ts_dqn_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "ts_qrdqn_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "ts_c51_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

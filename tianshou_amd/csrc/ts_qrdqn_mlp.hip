@@ -24,72 +24,10 @@
 #pragma clang fp contract(off)
 #include <algorithm>
 
-#include "ts_mlp_tile.h"
+#include "ts_atom_head.h"     // QNet, trunk_forward, head_action / head_wgrad / head_dgrad, row_sum8, launch helpers (shared with ts_c51_mlp.hip)
 #include "ts_qr_terms.h"
 
 namespace {
-
-constexpr int MAX_TRUNK = 4, MAX_ATOMS = 256, MAX_ACT = 32;
-constexpr int RPT = 8;                      // threads per row in the row-wise passes (THREADS / TILE)
-static_assert(RPT * TILE == THREADS, "thread (row, t) = (tid >> 3, tid & 7)");
-
-struct QNet {
-    int obs_dim, n_act, n_atoms, nt;
-    Lay t[MAX_TRUNK], head;                 // head: K = top width, N = n_act * n_atoms
-    int x_at, t_at[MAX_TRUNK];              // LDS float offsets of obs and of every hidden activation
-    int ta_at, tb_at, row_at, pitch;        // two [32][pitch] tables (pitch = n_atoms | 1), per-row scalars [4][32]
-    int P, lds_floats;
-};
-
-// the trunk on the tile whose observations are in LDS -> the top activation (LDS) and its pitch.  Ends behind a barrier.
-__device__ const float* trunk_forward(const QNet& net, const float* __restrict__ p, float* sm, int* ptop) {
-    const float* x = sm + net.x_at;
-    int px = net.obs_dim + 1;
-    for (int l = 0; l < net.nt; ++l) {
-        float* y = sm + net.t_at[l];
-        dense_relu(p + net.t[l].off, net.t[l].K, net.t[l].N, x, px, y, net.t[l].N + 1);
-        __syncthreads();
-        x = y; px = net.t[l].N + 1;
-    }
-    *ptop = px;
-    return x;
-}
-
-// out[m][c] = top[m][:] W[:, aN + c] + b[aN + c], c < N.  ROWSEL: only the rows with sel[m] == a are stored.
-template <bool ROWSEL>
-__device__ void head_action(const QNet& net, const float* __restrict__ p, int a, const float* top, int ptop, float* out, const int* sel) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
-    const int K = net.head.K, N = net.n_atoms, ld = net.head.N, pt = net.pitch;
-    const float* w = p + net.head.off + a * N;
-    for (int cb = wave; cb < (N + 31) / 32; cb += 4) {
-        const int c = cb * 32 + i;
-        const bool live = c < N;
-        const float* wp = w + (live ? c : 0);               // past column N: the action's first column is read, 0 is used
-        const float* xp = top + i * ptop + h;
-        f32x16 acc = {};
-#pragma unroll 8
-        for (int k = 0; k < K; k += 2) {                    // (K is a hidden width: even)
-            const float b = wp[(size_t)(k + h) * ld];
-            acc = mfma32(xp[k], live ? b : 0.f, acc);
-        }
-        const float bias = wp[(size_t)K * ld];
-        if (live) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = featF(r, h);
-                if (!ROWSEL || sel[m] == a) out[m * pt + c] = acc[r] + bias;
-            }
-        }
-    }
-}
-
-// the eight partial sums of a row (lanes 8 row .. 8 row + 7 of a wave) in a fixed butterfly: all eight threads hold the same bits
-__device__ __forceinline__ float row_sum8(float s) {
-    s += __shfl_xor(s, 1);
-    s += __shfl_xor(s, 2);
-    s += __shfl_xor(s, 4);
-    return s;
-}
 
 // ---- launch 1: QRDQN._target_q with the n-step arithmetic (INFER: Net.forward, the quantile means, the greedy action) -----------
 struct TargetArgs {
@@ -189,76 +127,6 @@ __global__ __launch_bounds__(THREADS) void qrm_target_kernel(TargetArgs a) {
 }
 
 // ---- launch 2: forward, pair loss, backward, the tile's slab ---------------------------------------------------------------------
-
-// the head's part of the slab: for action a the columns [aN, aN + N) of rows 0 .. K (row K = bias) = sum over the rows m with
-// sel[m] == a of top[m][k] dth[m][c]; an absent action's columns are zeros
-__device__ void head_wgrad(const QNet& net, float* __restrict__ slab, const float* top, int ptop, const float* dth, const int* sel, unsigned present) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
-    const int K = net.head.K, N = net.n_atoms, ld = net.head.N, pt = net.pitch;
-    const int cbs = (N + 31) / 32, kbs = K / 32;
-    for (int a = 0; a < net.n_act; ++a) {
-        float* sa = slab + a * N;
-        if (!((present >> a) & 1)) {                                           // workgroup-uniform
-            for (int idx = threadIdx.x; idx < (K + 1) * N; idx += THREADS) {
-                const int k = idx / N, c = idx - k * N;
-                sa[(size_t)k * ld + c] = 0.f;
-            }
-            continue;
-        }
-        for (int blk = wave; blk < kbs * cbs; blk += 4) {
-            const int kb = blk / cbs, cb = blk - kb * cbs;
-            const int kc = kb * 32 + i, c = cb * 32 + i;
-            const bool live = c < N;
-            const float* zp = dth + (live ? c : 0);
-            f32x16 acc = {};
-#pragma unroll
-            for (int m = 0; m < TILE; m += 2) {
-                const float z = zp[(m + h) * pt];
-                acc = mfma32(top[(m + h) * ptop + kc], live && sel[m + h] == a ? z : 0.f, acc);
-            }
-            if (live) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sa[(size_t)(kb * 32 + featF(r, h)) * ld + c] = acc[r];
-            }
-        }
-        for (int c = threadIdx.x; c < N; c += THREADS) {
-            float s = 0.f;
-            for (int m = 0; m < TILE; ++m) s += sel[m] == a ? dth[m * pt + c] : 0.f;
-            sa[(size_t)K * ld + c] = s;
-        }
-    }
-}
-
-// top[32][K] <- (sum over the present actions a of (dth masked by sel == a) W[:, aN .. aN + N)^T) * (top > 0), in place.  Block k on
-// wave k mod 4; A(i, c) = dth[i][c] from LDS, B(c, i) = W[k0 + i][aN + c] along c (N and aN need no alignment: 4-byte loads)
-__device__ void head_dgrad(const QNet& net, const float* __restrict__ p, float* top, int ptop, const float* dth, const int* sel, unsigned present) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
-    const int K = net.head.K, N = net.n_atoms, ld = net.head.N, pt = net.pitch;
-    const int mysel = sel[i];
-    const float* zp = dth + i * pt;
-    for (int kb = wave; kb < K / 32; kb += 4) {
-        const int kc = kb * 32 + i;
-        const float* wrow = p + net.head.off + (size_t)kc * ld;
-        f32x16 acc = {};
-        for (int a = 0; a < net.n_act; ++a) {
-            if (!((present >> a) & 1)) continue;                               // workgroup-uniform
-            const bool mine = mysel == a;
-            const float* wa = wrow + a * N;
-#pragma unroll 4
-            for (int c = 0; c < N; c += 2) {
-                const bool in = c + h < N;                                     // odd N: the last pair is half empty
-                const int cc = in ? c + h : 0;
-                const float z = zp[cc], w = wa[cc];
-                acc = mfma32(in && mine ? z : 0.f, in ? w : 0.f, acc);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float* q = top + featF(r, h) * ptop + kc;
-            *q = *q > 0.f ? acc[r] : 0.f;
-        }
-    }
-}
 
 struct StepArgs {
     QNet net;
@@ -392,19 +260,6 @@ int make_net(const int64_t* d, const char* who, QNet* out) {
                "%s: the activations and quantile tables of one 32-row tile need %zu bytes of LDS, the workgroup limit is %d", who,
                (size_t)at * 4 + 256, LDS_LIMIT);
     *out = n;
-    return TS_OK;
-}
-
-inline int64_t tiles_of(int64_t B) { return ts::ceil_div(B, TILE); }
-inline size_t ws_bytes(const QNet& n, int64_t B) { return ((size_t)tiles_of(B) * n.P + (size_t)tiles_of(B) + (size_t)n.P) * 4 + 4096 + 1024; }
-
-template <typename Kern>
-int allow_lds(ts::DynLds& slot, Kern kern, const QNet& n) {
-    return slot.allow(reinterpret_cast<const void*>(kern), (size_t)n.lds_floats * 4);
-}
-
-int check_batch(int64_t B, const char* who) {
-    TS_REQUIRE(B >= 1 && B <= 4096, B < 1 ? TS_ERR_INVALID_ARG : TS_ERR_UNSUPPORTED, "%s: B = %lld outside [1, 4096]", who, (long long)B);
     return TS_OK;
 }
 

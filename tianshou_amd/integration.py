@@ -1859,6 +1859,73 @@ def make_hip_qrdqn_mlp(ref=None):
 
 
 # ---------------------------------------------------------------------------------------------------
+# C51 on the plain MLP Net with a softmax over num_atoms atoms per action (test/discrete/test_c51.py)
+# ---------------------------------------------------------------------------------------------------
+def make_hip_c51_mlp(ref=None):
+    """Returns HipC51Mlp(C51): the C51 hooks (c51.py:120-160) on tianshou_amd.c51_mlp.C51MlpEngine for a
+    `Net(softmax=True, num_atoms=policy.num_atoms)` over a plain or prioritized buffer of vector observations: the n-step returns
+    of the support need no network, the target distribution, the update and the optimizer step are two launches.  What is outside
+    the envelope (c51_mlp.ENVELOPE) raises NotImplementedError in the constructor; nothing falls back to eager PyTorch.
+    `policy.forward` and the collector's `add_exploration_noise` stay the reference's.
+    `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    C51 = _ref(ref, "tianshou.algorithm.modelfree.c51", "C51")
+    LossSequenceTrainingStats = _ref(ref, "tianshou.algorithm.modelfree.reinforce", "LossSequenceTrainingStats")
+
+    from . import c51_mlp as M
+    from . import dqn as D
+
+    class HipC51Mlp(_HipGlue, C51):
+        def __init__(self, *args, device="cuda", **kwargs):
+            super().__init__(*args, **kwargs)
+            self._hip_device = torch.device(device)
+            self._hip_layers = M.describe_module(self.policy.model)
+            if self._hip_layers[3] != int(self.policy.num_atoms):
+                raise NotImplementedError(f"HipC51Mlp: the Net has num_atoms = {self._hip_layers[3]}, the policy num_atoms = "
+                                          f"{self.policy.num_atoms}")
+            _adam_of(self.optim)
+            self._hip_engine = None
+            self._hip_glue_init()
+
+        def _hip_qstate(self):
+            layers = self._hip_layers             # what the engine was built with
+            return _QState(M.state_dict_keys(layers), M.flat_from_torch, M.flat_to_torch, lambda eng: layers)
+
+        def _engine(self):
+            if self._hip_engine is None:
+                layers = self._hip_layers
+                eng = M.C51MlpEngine(layers, _q_flat(self, layers), D.DQNConfig(**_q_config_fields(self)),
+                                     v_min=float(self.policy.v_min), v_max=float(self.policy.v_max))
+                self._hip_engine = _q_load(self, eng)
+            return self._hip_engine
+
+        def _preprocess_batch(self, batch, buffer, indices):
+            obs = np.asarray(buffer.obs)
+            if obs.ndim < 2 or int(np.prod(obs.shape[1:])) != self._hip_layers[0] or int(getattr(buffer, "stack_num", 1)) != 1:
+                raise NotImplementedError("HipC51Mlp: the buffer must hold vector observations of the model's state_shape, stack_num 1")
+            m, idx = _q_begin(self, "HipC51Mlp", batch, buffer, indices)
+            eng = self._engine()
+            rows = m.obs.reshape(m.obs.shape[0], -1)
+            nxt = m.obs_next.reshape(m.obs_next.shape[0], -1) if m.obs_next is not None else None
+            self._hip_obs, self._hip_obs_next, batch.returns = eng.preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt)
+            return batch
+
+        def _update_with_batch(self, batch):
+            self._hip_refresh_lr()
+            eng, m = self._hip_engine, self._hip_mirror
+            weight = batch.pop("weight", None)
+            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device) if hasattr(batch, "act") else m.act[self._hip_idx]
+            loss, prio = eng.update_with_batch(self._hip_obs, act, self._hip_obs_next, batch.returns, weight)
+            self._iter = eng.iter
+            batch.weight = prio                                                   # prio-buffer, c51.py:157
+            self._hip_after_update()
+            return LossSequenceTrainingStats(loss=float(loss.item()))            # as c51.py:160
+
+        _hip_write_back = _q_write_back
+
+    return HipC51Mlp
+
+
+# ---------------------------------------------------------------------------------------------------
 # QRDQN (qrdqn.py) / C51 (c51.py) on QRDQNet / C51Net
 # ---------------------------------------------------------------------------------------------------
 def _make_hip_distq(kind: str, ref=None, cql: bool = False):
