@@ -1770,6 +1770,38 @@ int ts_c51_mlp_update(ts_workspace* ws, float* params, float* params_old, int sy
                       const ts_dqn_hparams* hp, float* loss_out, float* prio_out, float* grad_out, float* target_out,
                       ts_stream_t stream);
 
+/* ---- Rainbow on vector observations (modelfree/rainbow.py:93-101 -> c51.py:120-160 on `Net(softmax=True, num_atoms=N,
+ * dueling_param=(Q, V))` whose stream layers are all NoisyLinear or all nn.Linear; the network of test/discrete/test_rainbow.py):
+ * ts_c51_mlp's tile with the noisy operand mu + sigma * (eps_q[c] * eps_p[k]) composed in registers, 0 or 1 hidden layer per stream
+ * and the dueling combination (Q_a - mean_a Q_a) + V over the atoms in two walks of the Q head (ts_rainbow_mlp.hip).  Two launches
+ * per update: step, apply.
+ * `desc` is a HOST array of TS_RAINBOW_MLP_DESC_LEN int64: {obs_dim, n_act, 1, trunk layers (1 .. 4), Q hidden layers (0 | 1),
+ * V hidden layers (0 | 1), trunk widths[4], Q hidden width, 0, V hidden width, 0, N, noisy (0 | 1)}, unused widths 0.  Envelope:
+ * ts_c51_mlp's, with four [32][N | 1] tables, the stream activations and the staged eps_p in the LDS carve of a tile.
+ * Flat vector: the trunk layers [K + 1, width] (row K the bias), then the Q stream (hidden layer, output layer [K + 1, n_act N],
+ * column a N + j), then the V stream (hidden layer, output layer [K + 1, N]); a stream layer of a noisy network is its mu block
+ * followed by its sigma block of the same shape.  Noise vector (DEVICE float32, one per network): per stream layer, in the same order,
+ * eps_p[K] then eps_q[width].  A plain network has no noise vector: the noise arguments are not read.
+ * ts_rainbow_mlp_layout's h_out (int64[12]): {parameter count, LDS bytes per tile, workspace bytes for B rows, offsets of the trunk
+ * layers[4], of the Q hidden layer, the Q output layer, the V hidden layer, the V output layer (-1: absent), noise count}. */
+#define TS_RAINBOW_MLP_DESC_LEN 16
+int ts_rainbow_mlp_layout(const int64_t* desc, int64_t B, int64_t* h_out);
+/* Net.forward + C51Policy.compute_q_value + the greedy action, as ts_c51_mlp_forward; noise NULL: eval mode (mu alone is read). */
+int ts_rainbow_mlp_forward(const float* params, const float* noise, const int64_t* desc, const float* support, const float* obs, int64_t B,
+                           float* dist_out, float* q_out, int64_t* act_out, ts_stream_t stream);
+/* C51._target_dist as ts_c51_mlp_target_dist: the online network selects under `noise`, the lagged network evaluates under
+ * `noise_old`; params_old NULL or == params: the online network under `noise`, read once. */
+int ts_rainbow_mlp_target_dist(const float* params, const float* noise, const float* params_old, const float* noise_old, const int64_t* desc,
+                               const float* support, float v_min, float v_max, float delta_z, const float* obs_next, const float* returns,
+                               int64_t B, float* out, ts_stream_t stream);
+/* RainbowDQN._update_with_batch once both networks' noise is drawn, as ts_c51_mlp_update.  sync_old != 0: the target is read from
+ * `params` under `noise` alone and params_old receives the parameters as they are BEFORE this step (the caller copies the noise). */
+int ts_rainbow_mlp_update(ts_workspace* ws, float* params, const float* noise, float* params_old, const float* noise_old, int sync_old,
+                          float* adam_m, float* adam_v, int64_t adam_step, const int64_t* desc, const float* support, float v_min,
+                          float v_max, float delta_z, const float* obs, const int64_t* act, const float* obs_next, const float* returns,
+                          const float* weight, int64_t B, const ts_dqn_hparams* hp, float* loss_out, float* prio_out, float* grad_out,
+                          float* target_out, ts_stream_t stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * TD3 / DDPG: ContinuousActorDeterministic (utils/net/continuous.py:26-85) + the SAC critics,

@@ -26,6 +26,7 @@ EXTRA_FLAGS: dict[str, list[str]] = {
     "ts_dqn_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "ts_qrdqn_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "ts_c51_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "ts_rainbow_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

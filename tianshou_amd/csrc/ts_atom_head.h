@@ -2,7 +2,7 @@
 // softmax) on the 32-row tile of ts_mlp_tile.h: the network description, the trunk, the A N wide head walked ACTION BY ACTION (action
 // a's N columns are ceil(N / 32) MFMA column blocks whose weight loads are masked past column N, so the LDS footprint does not depend
 // on A and N needs no alignment), its masked weight and input gradients, the eight-lane row sum and the launch helpers.  Moved here
-// from ts_qrdqn_mlp.hip as they were.  Flat parameter vector: per layer [K + 1, N] (row K = bias), trunk layers then the head
+// from ts_qrdqn_mlp.hip as they were; softmax_row from ts_c51_mlp.hip, for ts_rainbow_mlp.hip as well.  Flat parameter vector: per layer [K + 1, N] (row K = bias), trunk layers then the head
 // [top + 1, A N], column a N + j.  Include behind `#pragma clang fp contract(off)`.
 #pragma once
 
@@ -72,6 +72,29 @@ __device__ __forceinline__ float row_sum8(float s) {
     s += __shfl_xor(s, 2);
     s += __shfl_xor(s, 4);
     return s;
+}
+
+// softmax of a row of N logits in place, thread t of the row's eight on the atoms i = t (mod 8) -> the expected value sum_i p_i z_i
+__device__ __forceinline__ float softmax_row(float* mine, int N, int t, const float* __restrict__ z) {
+    float mx = -INFINITY;
+    for (int i = t; i < N; i += RPT) mx = fmaxf(mx, mine[i]);
+    mx = fmaxf(mx, __shfl_xor(mx, 1));
+    mx = fmaxf(mx, __shfl_xor(mx, 2));
+    mx = fmaxf(mx, __shfl_xor(mx, 4));
+    float s = 0.f;
+    for (int i = t; i < N; i += RPT) {
+        const float e = expf(mine[i] - mx);
+        mine[i] = e;                                     // only this thread reads atom i
+        s += e;
+    }
+    s = row_sum8(s);
+    float q = 0.f;
+    for (int i = t; i < N; i += RPT) {
+        const float p = mine[i] / s;
+        mine[i] = p;
+        q += p * z[i];
+    }
+    return row_sum8(q);
 }
 
 // the head's part of the slab: for action a the columns [aN, aN + N) of rows 0 .. K (row K = bias) = sum over the rows m with

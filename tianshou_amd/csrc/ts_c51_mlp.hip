@@ -42,29 +42,6 @@ struct C51Args {
     float* prio_out; float* slabs; float* partials;       // STEP
 };
 
-// softmax of a row of N logits in place, thread t of the row's eight on the atoms i = t (mod 8) -> the expected value sum_i p_i z_i
-__device__ __forceinline__ float softmax_row(float* mine, int N, int t, const float* __restrict__ z) {
-    float mx = -INFINITY;
-    for (int i = t; i < N; i += RPT) mx = fmaxf(mx, mine[i]);
-    mx = fmaxf(mx, __shfl_xor(mx, 1));
-    mx = fmaxf(mx, __shfl_xor(mx, 2));
-    mx = fmaxf(mx, __shfl_xor(mx, 4));
-    float s = 0.f;
-    for (int i = t; i < N; i += RPT) {
-        const float e = expf(mine[i] - mx);
-        mine[i] = e;                                     // only this thread reads atom i
-        s += e;
-    }
-    s = row_sum8(s);
-    float q = 0.f;
-    for (int i = t; i < N; i += RPT) {
-        const float p = mine[i] / s;
-        mine[i] = p;
-        q += p * z[i];
-    }
-    return row_sum8(q);
-}
-
 // The head, action by action, on the tile whose top activation is in LDS: softmax of every action's row, the running argmax of the
 // expected value -> returned (thread (row, t): its row's).  KEEP: the argmax's normalised row is left in `kept`.  INFER: the
 // probabilities and expected values of every action go to memory.  Ends behind a barrier.

@@ -2522,6 +2522,87 @@ def make_hip_rainbow(ref=None):
     return HipRainbow
 
 
+def make_hip_rainbow_mlp(ref=None):
+    """Returns HipRainbowMlp(RainbowDQN): HipC51Mlp's hooks on tianshou_amd.rainbow_mlp.RainbowMlpEngine for a
+    `Net(softmax=True, num_atoms=policy.num_atoms, dueling_param=(Q, V))` whose streams are NoisyLinear (test/discrete/test_rainbow.py)
+    or plain Linear layers, over a plain or prioritized buffer of vector observations.  As in HipRainbow the noise is drawn by the
+    torch modules themselves (`RainbowDQN._sample_noise`, so torch's generator advances as in the reference) and handed to the engine.
+    What is outside the envelope (rainbow_mlp.ENVELOPE) raises NotImplementedError in the constructor; nothing falls back to eager
+    PyTorch.  `policy.forward` and the collector's `add_exploration_noise` stay the reference's.
+    `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    RainbowDQN = _ref(ref, "tianshou.algorithm.modelfree.rainbow", "RainbowDQN")
+    LossSequenceTrainingStats = _ref(ref, "tianshou.algorithm.modelfree.reinforce", "LossSequenceTrainingStats")
+
+    from . import dqn as D
+    from . import rainbow_mlp as M
+
+    class HipRainbowMlp(_HipGlue, RainbowDQN):
+        def __init__(self, *args, device="cuda", **kwargs):
+            super().__init__(*args, **kwargs)
+            self._hip_device = torch.device(device)
+            self._hip_layers = M.describe_module(self.policy.model)
+            if self._hip_layers[5] != int(self.policy.num_atoms):
+                raise NotImplementedError(f"HipRainbowMlp: the Net has num_atoms = {self._hip_layers[5]}, the policy num_atoms = "
+                                          f"{self.policy.num_atoms}")
+            _adam_of(self.optim)
+            self._hip_engine = None
+            self._hip_glue_init()
+
+        def _noise_of(self, model):
+            sd = model.state_dict()
+            return M.noise_from_torch([sd[k] for k in M.noise_keys(self._hip_layers)], *self._hip_layers, self._hip_device)
+
+        def _hip_qstate(self):
+            layers = self._hip_layers             # what the engine was built with
+            return _QState(M.state_dict_keys(layers), M.flat_from_torch, M.flat_to_torch, lambda eng: layers)
+
+        def _engine(self):
+            if self._hip_engine is None:
+                layers = self._hip_layers
+                eng = M.RainbowMlpEngine(layers, _q_flat(self, layers), self._noise_of(self.policy.model), D.DQNConfig(**_q_config_fields(self)),
+                                         v_min=float(self.policy.v_min), v_max=float(self.policy.v_max))
+                self._hip_engine = _q_load(self, eng)
+            return self._hip_engine
+
+        def _preprocess_batch(self, batch, buffer, indices):
+            obs = np.asarray(buffer.obs)
+            if obs.ndim < 2 or int(np.prod(obs.shape[1:])) != self._hip_layers[0] or int(getattr(buffer, "stack_num", 1)) != 1:
+                raise NotImplementedError("HipRainbowMlp: the buffer must hold vector observations of the model's state_shape, stack_num 1")
+            m, idx = _q_begin(self, "HipRainbowMlp", batch, buffer, indices)
+            eng = self._engine()
+            rows = m.obs.reshape(m.obs.shape[0], -1)
+            nxt = m.obs_next.reshape(m.obs_next.shape[0], -1) if m.obs_next is not None else None
+            self._hip_obs, self._hip_obs_next, batch.returns = eng.preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt)
+            return batch
+
+        def _update_with_batch(self, batch):
+            self._hip_refresh_lr()
+            eng, m = self._hip_engine, self._hip_mirror
+            self._sample_noise(self.policy.model)                                 # rainbow.py:97-100
+            noise_old = None
+            if self.use_target_network:
+                self._sample_noise(self.model_old)
+                noise_old = self._noise_of(self.model_old)
+            eng.set_noise(self._noise_of(self.policy.model), noise_old)
+            weight = batch.pop("weight", None)
+            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device) if hasattr(batch, "act") else m.act[self._hip_idx]
+            loss, prio = eng.update_with_batch(self._hip_obs, act, self._hip_obs_next, batch.returns, weight)
+            self._iter = eng.iter
+            batch.weight = prio                                                   # prio-buffer, c51.py:157
+            self._hip_after_update()
+            return LossSequenceTrainingStats(loss=float(loss.item()))            # as c51.py:160
+
+        def _hip_write_back(self) -> None:
+            _q_write_back(self)
+            eng = self.__dict__.get("_hip_engine_obj")
+            if eng is not None and eng.noise_old is not None and (eng.iter - 1) % eng.cfg.target_update_freq == 0:
+                so, sn = self.model_old.state_dict(), self.policy.model.state_dict()      # the sync carried the noise along
+                with torch.no_grad():
+                    for k in M.noise_keys(self._hip_layers):
+                        so[k].copy_(sn[k])
+
+    return HipRainbowMlp
+
 
 # ---------------------------------------------------------------------------------------------------
 # SAC (sac.py:213-336) on the mujoco_sac.py networks
