@@ -1802,6 +1802,42 @@ int ts_rainbow_mlp_update(ts_workspace* ws, float* params, const float* noise, f
                           const float* weight, int64_t B, const ts_dqn_hparams* hp, float* loss_out, float* prio_out, float* grad_out,
                           float* target_out, ts_stream_t stream);
 
+/* ---- IQN on vector observations (modelfree/iqn.py:156-183 and qrdqn.py:94-106 on `ImplicitQuantileNetwork(preprocess_net=Net(...),
+ * hidden_sizes=H, num_cosines=C)`, utils/net/discrete.py:126-216; the network of test/discrete/test_iqn.py): ts_dqn_mlp's tile with
+ * the SAMPLE WALK (ts_iqn_mlp.hip): the trunk runs once per 32-row tile, then the N sampled fractions of its rows are taken one
+ * after the other (cosines, embedding, features (.) embedding, `last`, the final Linear as one masked 32-column block), so the LDS
+ * carve depends neither on N nor on A.  A target pass is one launch, an update two (step, apply).
+ * `desc` is a HOST array of TS_IQN_MLP_DESC_LEN int64: {obs_dim, n_act, trunk layers (1 .. 4), trunk widths[4], width F of the
+ * Net's linear output layer (0: none, the features are the last ReLU layer and F its width), num_cosines C, hidden layers of
+ * `last` (0 .. 2), their widths[2]}, unused widths 0.  Envelope (TS_ERR_UNSUPPORTED beyond it, before any HIP call): obs_dim in
+ * [1, 256], every width and F a multiple of 32 in [32, 256], ReLU, 1 <= C <= 64, 1 <= n_act <= 32, every sample count in [2, 64],
+ * 1 <= B <= 4096, and the LDS carve of one tile within 160 KB.  The fractions are inputs: DEVICE float32[B, N].
+ * Flat vector, per layer [K + 1, width] (row K the bias): trunk | the Net's output layer (if any) | [We; be] [C + 1, F] | `last`
+ * hidden layers | final Linear [top + 1, n_act].
+ * ts_iqn_mlp_layout: h_out int64[16] = {floats of the flat vector, LDS bytes of a tile, workspace bytes at this B, offsets of
+ * trunk[0..3], of the Net's output layer, of the embedding, of last_hidden[0..1] (-1: absent), of the final Linear, F}. */
+#define TS_IQN_MLP_DESC_LEN 12
+int ts_iqn_mlp_layout(const int64_t* desc, int64_t B, int64_t* h_out);
+/* ImplicitQuantileNetwork.forward on the given fractions + IQNPolicy.forward: logits_out float32[B, n_act, N], q_out
+ * float32[B, n_act] = the mean over the samples, act_out int64[B] = argmax q, first index on ties; each may be NULL, not all. */
+int ts_iqn_mlp_forward(const float* params, const int64_t* desc, const float* obs, int64_t B, const float* tau, int64_t N,
+                       float* logits_out, float* q_out, int64_t* act_out, ts_stream_t stream);
+/* QRDQN._target_q (qrdqn.py:94-106) in one launch: the online network on tau_online [B, N] selects, the lagged network on
+ * tau_target [B, N2] gives out float32[B, N2]; params_old NULL (or == params): the online network itself on tau_online, out
+ * float32[B, N] (tau_target and N2 are not read).  With the three outputs of ts_nstep_coefficients (all or none) out[b, j] is
+ * instead float(double(out[b, j] * mask[b]) * gpow[b] + mc[b]). */
+int ts_iqn_mlp_next_dist(const float* params, const float* params_old, const int64_t* desc, const float* obs_next, int64_t B,
+                         const float* tau_online, int64_t N, const float* tau_target, int64_t N2, const float* nstep_mask,
+                         const double* nstep_gpow, const double* nstep_mc, float* out, ts_stream_t stream);
+/* IQN._update_with_batch (iqn.py:156-183) in two launches.  tau float32[B, N]; returns float32[B, N2]; weight (nullable)
+ * float32[B].  loss_out float32[1] = mean_b(huber_b weight_b), prio_out float32[B] = the new priorities (iqn.py:180); sync_old,
+ * grad_out, hp->lr < 0 and hp->max_grad_norm as ts_dqn_mlp_update (hp->v_min / v_max are not read).  The slab blocks of the
+ * embedding and of `last` take the samples in ascending order, each block on one wave: bit-identical from run to run. */
+int ts_iqn_mlp_update(ts_workspace* ws, float* params, float* params_old, int sync_old, float* adam_m, float* adam_v, int64_t adam_step,
+                      const int64_t* desc, const float* obs, const int64_t* act, const float* tau, int64_t N, const float* returns,
+                      int64_t N2, const float* weight, int64_t B, const ts_distq_hparams* hp, float* loss_out, float* prio_out,
+                      float* grad_out, ts_stream_t stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * TD3 / DDPG: ContinuousActorDeterministic (utils/net/continuous.py:26-85) + the SAC critics,

@@ -151,6 +151,11 @@ def _bdqn_prototypes(lib) -> None:
         "ts_rainbow_mlp_forward": [p, p, p, p, p, i64_, p, p, p, p],
         "ts_rainbow_mlp_target_dist": [p, p, p, p, p, p, f32, f32, f32, p, p, i64_, p, p],
         "ts_rainbow_mlp_update": [p, p, p, p, p, i32, p, p, i64_, p, p, f32, f32, f32, p, p, p, p, p, i64_, p, p, p, p, p, p],
+        # ts_iqn_mlp_* (desc: a host int64[TS_IQN_MLP_DESC_LEN]; every fraction tensor with its sample count behind it)
+        "ts_iqn_mlp_layout": [p, i64_, p],
+        "ts_iqn_mlp_forward": [p, p, p, i64_, p, i64_, p, p, p, p],
+        "ts_iqn_mlp_next_dist": [p, p, p, p, i64_, p, i64_, p, i64_, p, p, p, p, p],
+        "ts_iqn_mlp_update": [p, p, p, i32, p, p, i64_, p, p, p, p, i64_, p, i64_, p, i64_, p, p, p, p, p],
     }
     for name, argtypes in protos.items():
         if hasattr(lib, name):                       # (a library built before these existed still serves every other engine)

@@ -27,6 +27,7 @@ EXTRA_FLAGS: dict[str, list[str]] = {
     "ts_qrdqn_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "ts_c51_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "ts_rainbow_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "ts_iqn_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -2159,6 +2159,90 @@ def make_hip_iqn(ref=None):
     return HipIQN
 
 
+# ---------------------------------------------------------------------------------------------------
+# IQN on the plain MLP Net over vector observations (test/discrete/test_iqn.py)
+# ---------------------------------------------------------------------------------------------------
+def make_hip_iqn_mlp(ref=None):
+    """Returns HipIQNMlp(IQN): the IQN hooks (qrdqn.py:94-106, iqn.py:156-183) on tianshou_amd.iqn_mlp.IQNMlpEngine for an
+    `ImplicitQuantileNetwork(preprocess_net=Net(...), hidden_sizes, num_cosines)` over a plain or prioritized buffer of vector
+    observations: `_target_q` + the n-step returns ([B, N']) are one launch, the update and the optimizer step two.  What is
+    outside the envelope (iqn_mlp.ENVELOPE) raises NotImplementedError in the constructor; nothing falls back to eager PyTorch.
+    `policy.forward` and the collector's `add_exploration_noise` stay the reference's.  `hip_taus` / `hip_seed` and the fraction
+    counter beside the checkpoint (`hip_extra_state()`) are HipIQN's; the fractions of the last update stay in the engine
+    (`last_tau_online`, `last_tau_target`, `last_tau`).
+    `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    IQN = _ref(ref, "tianshou.algorithm.modelfree.iqn", "IQN")
+    SimpleLossTrainingStats = _ref(ref, "tianshou.algorithm.modelfree.reinforce", "SimpleLossTrainingStats")
+    HipIQN = make_hip_iqn(ref)
+
+    from . import iqn as I
+    from . import iqn_mlp as M
+
+    class HipIQNMlp(_HipGlue, IQN):
+        def __init__(self, *args, device="cuda", hip_taus=None, hip_seed=0, **kwargs):
+            super().__init__(*args, **kwargs)
+            self._hip_device = torch.device(device)
+            self._hip_layers = M.describe_module(self.policy.model)
+            for name in ("online_sample_size", "target_sample_size"):
+                if not 2 <= int(getattr(self.policy, name)) <= M.MAX_SAMPLES:
+                    raise NotImplementedError(f"HipIQNMlp: policy.{name} = {getattr(self.policy, name)} is outside [2, {M.MAX_SAMPLES}]")
+            _adam_of(self.optim)
+            self._hip_taus = hip_taus
+            self._hip_seed = int(hip_seed)
+            self._hip_tau_counter = 0
+            self._hip_engine = None
+            self._hip_glue_init()
+
+        hip_extra_state, load_hip_extra_state, _hip_next_tau = HipIQN.hip_extra_state, HipIQN.load_hip_extra_state, HipIQN._hip_next_tau
+
+        def _hip_qstate(self):
+            layers = self._hip_layers             # what the engine was built with
+            return _QState(M.state_dict_keys(layers), M.flat_from_torch, M.flat_to_torch, lambda eng: layers)
+
+        def _engine(self):
+            if self._hip_engine is None:
+                layers = self._hip_layers
+                cfg = I.IQNConfig(n_cos=layers[3], sample_size=min(max(int(self.policy.sample_size), 2), M.MAX_SAMPLES),
+                                  online_sample_size=int(self.policy.online_sample_size),
+                                  target_sample_size=int(self.policy.target_sample_size), seed=self._hip_seed,
+                                  **_q_config_fields(self))
+                eng = M.IQNMlpEngine(layers, _q_flat(self, layers), cfg)
+                eng.tau_counter = self._hip_tau_counter
+                self._hip_engine = _q_load(self, eng)
+            return self._hip_engine
+
+        def _preprocess_batch(self, batch, buffer, indices):
+            obs = np.asarray(buffer.obs)
+            if obs.ndim < 2 or int(np.prod(obs.shape[1:])) != self._hip_layers[0] or int(getattr(buffer, "stack_num", 1)) != 1:
+                raise NotImplementedError("HipIQNMlp: the buffer must hold vector observations of the model's state_shape, stack_num 1")
+            m, idx = _q_begin(self, "HipIQNMlp", batch, buffer, indices)
+            eng = self._engine()
+            rows = m.obs.reshape(m.obs.shape[0], -1)
+            nxt = m.obs_next.reshape(m.obs_next.shape[0], -1) if m.obs_next is not None else None
+            tau_online = self._hip_next_tau()                                    # qrdqn.py:100 / :103
+            tau_target = self._hip_next_tau() if eng.params_old is not None else None      # qrdqn.py:101
+            self._hip_obs, batch.returns = eng.preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt, tau_online=tau_online,
+                                                                   tau_target=tau_target)
+            self._hip_tau_counter = eng.tau_counter
+            return batch
+
+        def _update_with_batch(self, batch):
+            self._hip_refresh_lr()
+            eng, m = self._hip_engine, self._hip_mirror
+            weight = batch.pop("weight", None)
+            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device) if hasattr(batch, "act") else m.act[self._hip_idx]
+            loss, prio = eng.update_with_batch(self._hip_obs, act, batch.returns, weight, tau=self._hip_next_tau())      # iqn.py:162
+            self._iter = eng.iter
+            self._hip_tau_counter = eng.tau_counter
+            batch.weight = prio                                                   # prio-buffer, iqn.py:180
+            self._hip_after_update()
+            return SimpleLossTrainingStats(loss=float(loss.item()))
+
+        _hip_write_back = _q_write_back
+
+    return HipIQNMlp
+
+
 def make_hip_discrete_bcq(ref=None):
     """Returns HipDiscreteBCQ(DiscreteBCQ): `_preprocess_batch` / `_update_with_batch` (imitation/discrete_bcq.py:213-261) on
     the engine (tianshou_amd/bcq.py).  Supported model: policy.model and policy.imitator = DiscreteActor(preprocess_net,
