@@ -526,7 +526,8 @@ class DeviceReplayBuffer:
 
         batch_size == 0 -> every valid index, sub-buffer-major and time-ordered.
         batch_size > 0  -> sub-buffer with probability proportional to its length, then uniform inside it, concatenated
-        in sub-buffer order (ts_sample_indices_random).  The reference draws from the buffers' own RandomStates
+        in sub-buffer order (ts_sample_indices_random); with every sub-buffer empty it raises ValueError, as the reference's
+        RandomState.choice does.  The reference draws from the buffers' own RandomStates
         (buffer_base.py:98); to reproduce a seeded reference run pass its draws: `u_buffer` float64[bs] (the uniforms
         `RandomState.choice(E, bs, p=...)` consumes) and `within` int64[bs] (the children's `choice(len_e, n_e)` values,
         concatenated in sub-buffer order).  Without them the draws come from torch's device generator (`generator`), or --
@@ -542,8 +543,9 @@ class DeviceReplayBuffer:
         if batch_size > 0:
             dev = self.device
             bs = int(batch_size)
-            if len(self) == 0:                               # buffer_base.py:512-513: an empty buffer yields no indices
-                return torch.empty(0, dtype=torch.int64, device=dev)
+            if len(self) == 0:
+                # manager.py:220-224 / buffer_base.py:516-517: RandomState.choice refuses p = lengths / 0 (and choice(0, bs))
+                raise ValueError("sample_indices: batch_size > 0 on an empty buffer (the reference's RandomState.choice raises)")
             if (u_buffer is None) != (within is None):
                 raise ValueError("pass both u_buffer and within (the reference's draws) or neither")
             if u_buffer is None and seed is not None:

@@ -647,9 +647,10 @@ using ts::philox_round;
 // prio.py:65, inside ts_dqn_learn_step)
 __global__ __launch_bounds__(256) void uniform_fill_f64_kernel(double* __restrict__ out, int64_t n, uint64_t seed, uint64_t counter,
                                                                const uint64_t* __restrict__ counter_dev) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (counter_dev) counter = *counter_dev;
-    if (i < n) out[i] = uniform53(seed, counter, i, 0);
+    // grid_for caps the grid at 4,096 workgroups: larger n go round again
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        out[i] = uniform53(seed, counter, i, 0);
 }
 
 // torch.rand's stand-in for the IQN fractions: 24 random bits -> float32 in [0, 1) (exact: k * 2^-24, k < 2^24)
@@ -662,13 +663,14 @@ __global__ __launch_bounds__(256) void uniform_fill_f32_kernel(float* __restrict
 }
 
 __global__ __launch_bounds__(256) void normal_fill_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t offset) {
-    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (4 * q >= n) return;
-    float z[4];
-    ts::normal4(q, seed, offset, z);
+    // grid_for caps the grid at 4,096 workgroups (2^22 outputs): larger n go round again
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; 4 * q < n; q += (int64_t)gridDim.x * 256) {
+        float z[4];
+        ts::normal4(q, seed, offset, z);
 #pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (4 * q + e < n) out[4 * q + e] = z[e];
+        for (int e = 0; e < 4; ++e)
+            if (4 * q + e < n) out[4 * q + e] = z[e];
+    }
 }
 
 inline int grid_for(int64_t n, int block) {
