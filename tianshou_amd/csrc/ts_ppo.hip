@@ -1217,6 +1217,21 @@ __global__ __launch_bounds__(STEP_THREADS, 2) void ppo_step1_kernel(StepArgs g, 
 // slab reduction: grad[col] = sum over all workgroup slabs (fixed order), plus the block's
 // partial sum of squares over the parameter columns (for the global gradient norm).
 constexpr int RED_THREADS = 1024;
+constexpr int RED_WAVES = RED_THREADS / 64;
+
+// One thread's NL slabs (every RED_WAVES-th one) with all NL loads issued before the first add: one memory round trip
+// whatever NL is.  The adds run in the order of the general loop in the kernel.  `base` (the wave's first slab) and
+// `stride` are uniform, `off` is the thread's column.
+template <int NL>
+__device__ __forceinline__ float slab_sum_inflight(const float* __restrict__ base, int64_t stride, unsigned off) {
+    float v[NL];
+#pragma unroll
+    for (int j = 0; j < NL; ++j) v[j] = (base + j * stride)[off];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) s += v[j];
+    return s;
+}
 
 __global__ __launch_bounds__(RED_THREADS) void ppo_reduce_slabs_kernel(const float* __restrict__ slabs,
                                                                        int n_slabs, int slab_w, Dims d, int kp, int k1q,
@@ -1229,22 +1244,56 @@ __global__ __launch_bounds__(RED_THREADS) void ppo_reduce_slabs_kernel(const flo
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = blockIdx.x * 64 + lane;
     const int n_params = d.p_total;
+    // Everything below that does not depend on the slabs is started here, in front of the slab loads, so that behind the
+    // barrier wave 0 (which every workgroup's end waits for) is left with register and LDS work only.
+    // Normal.entropy() = 0.5 + 0.5 log(2 pi) + log(sigma), summed over actions; identical for every sample, so its batch
+    // mean (ppo.py:210) is the value itself.  Read here, before the Adam kernel touches sigma_param: lane k of the LAST
+    // wave holds action k's term (that wave has nothing to do behind the barrier, so neither the arithmetic nor the
+    // completion of its stores delays wave 0).
+    const bool ent_wave = (losses || parts) && blockIdx.x == 0 && wave == RED_WAVES - 1;
+    float ent_t = 0.f;
+    if (ent_wave && lane < d.act) ent_t = params[d.a_sig + lane];      // (only the load: its use waits behind the slab loads)
+    // slab column -> flat parameter index (second-generation slabs keep W1 | b1 as one augmented matrix)
+    // (k1q > 0: the slabs come from ppo_stepq_kernel, transposed sections, see ts_ppo_q.h)
+    int pidx = -1;
+    if (wave == 0 && col < slab_w) pidx = k1q > 0 ? q4::slab3_col_to_param(col, d, k1q) : slab_col_to_param(col, d, kp);
     float s = 0.f;
     if (col < slab_w) {
+        const float* base = slabs + (int64_t)__builtin_amdgcn_readfirstlane(wave) * slab_w;
+        const int64_t stride = (int64_t)RED_WAVES * slab_w;
+        // n_slabs = 32 m <= 512 (the headline's 512, the feature-split kernels' 256): every thread has 2 m slabs
+        switch ((n_slabs & 31) == 0 && n_slabs <= 32 * RED_WAVES ? n_slabs >> 5 : 0) {
+#define TS_RED_CASE(M) case M: s = slab_sum_inflight<2 * M>(base, stride, col); break;
+            TS_RED_CASE(1) TS_RED_CASE(2) TS_RED_CASE(3) TS_RED_CASE(4) TS_RED_CASE(5) TS_RED_CASE(6) TS_RED_CASE(7)
+            TS_RED_CASE(8) TS_RED_CASE(9) TS_RED_CASE(10) TS_RED_CASE(11) TS_RED_CASE(12) TS_RED_CASE(13)
+            TS_RED_CASE(14) TS_RED_CASE(15) TS_RED_CASE(16)
+#undef TS_RED_CASE
+            default:
 #pragma unroll 16
-        for (int k = wave; k < n_slabs; k += RED_THREADS / 64) s += slabs[(int64_t)k * slab_w + col];
+                for (int k = wave; k < n_slabs; k += RED_WAVES) s += slabs[(int64_t)k * slab_w + col];
+        }
     }
     red[wave][lane] = s;
+    if (ent_wave) {
+        asm volatile("" : "+v"(ent_t));      // keeps the arithmetic (and the wait for the load) here, behind the slab loads
+        ent_t = 0.5f + 0.5f * 1.8378770664093453f + logf(expf(ent_t));
+        // the lanes' terms added in action order, as one thread would add them
+        float ent = 0.f;
+#pragma unroll
+        for (int k = 0; k < ACT_PAD; ++k) {
+            const float tk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ent_t), k));
+            if (k < d.act) ent += tk;
+        }
+        if (lane == 0 && losses) losses[3] = ent;
+        if (lane == 0 && parts) parts[3] = ent;
+    }
     __syncthreads();
     if (wave == 0) {
         float t = 0.f;
 #pragma unroll
-        for (int k = 0; k < RED_THREADS / 64; ++k) t += red[k][lane];
-        // slab column -> flat parameter index (second-generation slabs keep W1 | b1 as one augmented matrix)
-        // (k1q > 0: the slabs come from ppo_stepq_kernel, transposed sections, see ts_ppo_q.h)
-        const int pidx = col < slab_w ? (k1q > 0 ? q4::slab3_col_to_param(col, d, k1q) : slab_col_to_param(col, d, kp)) : -1;
+        for (int k = 0; k < RED_WAVES; ++k) t += red[k][lane];
         // data-parallel path (parts != NULL): grad holds only the n_params gradient columns, the two loss sums go
-        // to parts[1] (clip) and parts[2] (vf); parts[3] = entropy below, parts[0] is composed by the caller
+        // to parts[1] (clip) and parts[2] (vf); parts[3] = entropy above, parts[0] is composed by the caller
         if (pidx >= 0 && pidx < (parts ? n_params : n_params + N_EXTRA)) grad[pidx] = t;
         if (parts && pidx == n_params) parts[1] = t;
         if (parts && pidx == n_params + 1) parts[2] = t;
@@ -1253,16 +1302,6 @@ __global__ __launch_bounds__(RED_THREADS) void ppo_reduce_slabs_kernel(const flo
         for (int off = 32; off > 0; off >>= 1) q += __shfl_down(q, off, 64);
         if (lane == 0) sumsq_part[blockIdx.x] = q;
         if (parts && blockIdx.x == 0 && lane == 0) parts[0] = 0.f;
-        if ((losses || parts) && blockIdx.x == 0 && lane == 0) {
-            // Normal.entropy() = 0.5 + 0.5 log(2 pi) + log(sigma), summed over actions; identical
-            // for every sample, so its batch mean (ppo.py:210) is the value itself.  Computed here,
-            // before the Adam kernel touches sigma_param.
-            float ent = 0.f;
-            for (int k = 0; k < d.act; ++k)
-                ent += 0.5f + 0.5f * 1.8378770664093453f + logf(expf(params[d.a_sig + k]));
-            if (losses) losses[3] = ent;
-            if (parts) parts[3] = ent;
-        }
     }
 }
 
