@@ -1838,6 +1838,46 @@ int ts_iqn_mlp_update(ts_workspace* ws, float* params, float* params_old, int sy
                       int64_t N2, const float* weight, int64_t B, const ts_distq_hparams* hp, float* loss_out, float* prio_out,
                       float* grad_out, ts_stream_t stream);
 
+/* ---- FQF on vector observations (modelfree/fqf.py:66-106, 178-256 on `FullQuantileFunction(preprocess_net=Net(...), hidden_sizes=H,
+ * num_cosines=C)` + `FractionProposalNetwork(N, F)`, utils/net/discrete.py:219-314; the networks of test/discrete/test_fqf.py):
+ * ts_iqn_mlp's tile and sample walk (ts_fqf_mlp.hip), but the fractions are PROPOSED by the tile from its own detached features
+ * (Categorical(logits = f Wp + bp): probabilities, float32 ascending cumsum -> taus [N + 1], tau_hats [N], entropy), kept in LDS
+ * and walked over there.  A target pass is one launch, an update three (step, apply, the fraction optimizer's step).
+ * `desc` is a HOST array of TS_FQF_MLP_DESC_LEN int64: the first ten entries of ts_iqn_mlp's, then the widths of `last`'s hidden
+ * layers[3] (0 .. 3 layers) and num_fractions N in [2, 64].  Envelope otherwise as ts_iqn_mlp's; the LDS carve of a tile holds
+ * five more [32][65] tables and 512 bytes of staged description.  Two flat vectors: the model's as ts_iqn_mlp's, the fraction
+ * network's [F + 1, N] (row F the bias).
+ * ts_fqf_mlp_layout: h_out int64[16] = {floats of the model's vector, floats of the fraction network's, LDS bytes of a tile,
+ * workspace bytes at this B, F}. */
+#define TS_FQF_MLP_DESC_LEN 14
+int ts_fqf_mlp_layout(const int64_t* desc, int64_t B, int64_t* h_out);
+/* FullQuantileFunction.forward + FQFPolicy.forward (fqf.py:66-106): logits_out float32[B, n_act, N] at tau_hats, q_out float32[B,
+ * n_act] = sum_j (taus[j + 1] - taus[j]) logits[.., j], act_out int64[B] = argmax q (first index on ties), taus_out float32[B, N +
+ * 1], tau_hats_out float32[B, N], entropies_out float32[B], quantiles_tau_out float32[B, n_act, N - 1] at taus[:, 1:-1]; each
+ * nullable.  taus_in / tau_hats_in (both or neither): the reference's `fractions=`; the proposal is skipped, fparams may be NULL
+ * and entropies_out is not written. */
+int ts_fqf_mlp_forward(const float* params, const float* fparams, const int64_t* desc, const float* obs, int64_t B, const float* taus_in,
+                       const float* tau_hats_in, float* logits_out, float* q_out, int64_t* act_out, float* taus_out, float* tau_hats_out,
+                       float* entropies_out, float* quantiles_tau_out, ts_stream_t stream);
+/* FQF._target_q (fqf.py:178-193) in one launch: the online network proposes the fractions and selects by the weighted q; the
+ * lagged network (params_old; NULL or == params: the online one) on the same tau_hats gives out float32[B, N].  The n-step
+ * arrays as ts_iqn_mlp_next_dist.  taus_out / tau_hats_out (nullable): the fractions used. */
+int ts_fqf_mlp_next_dist(const float* params, const float* params_old, const float* fparams, const int64_t* desc, const float* obs_next,
+                         int64_t B, const float* nstep_mask, const double* nstep_gpow, const double* nstep_mc, float* out, float* taus_out,
+                         float* tau_hats_out, ts_stream_t stream);
+/* FQF._update_with_batch (fqf.py:195-256).  returns float32[B, N]; weight (nullable) float32[B].  losses_out float32[3] =
+ * {quantile_loss, fraction_loss, entropy_loss}; prio_out float32[B] (fqf.py:220); grad_out [P] / fgrad_out [P2] (nullable): the
+ * two gradients (fgrad = d(fraction_loss - ent_coef entropy_loss)); sync_old, adam_step and hp->lr < 0 (both gradients only, no
+ * optimizer step on either network) as ts_iqn_mlp_update; `hp`: the model's Adam and max_grad_norm.  `fhp`: the fraction optimizer,
+ * which has no max_grad_norm (fqf.py:170) -- of ts_ppo_hparams it reads lr, beta1, beta2, adam_eps, optimizer (TS_OPT_ADAM /
+ * TS_OPT_RMSPROP; test_fqf.py: RMSprop), rms_centered, weight_decay, rms_alpha, rms_momentum, and ent_coef (the fraction optimizer
+ * minimises fraction_loss - ent_coef * entropy_loss, fqf.py:247).  f_m / f_v / f_step: its state vectors (ts_optim_step's
+ * mapping) and its 1-based step.  Slabs and loss partials are summed in tile order: a repeated update is bit-identical. */
+int ts_fqf_mlp_update(ts_workspace* ws, float* params, float* params_old, int sync_old, float* adam_m, float* adam_v, int64_t adam_step,
+                      float* fparams, float* f_m, float* f_v, int64_t f_step, const int64_t* desc, const float* obs, const int64_t* act,
+                      const float* returns, const float* weight, int64_t B, const ts_distq_hparams* hp, const ts_ppo_hparams* fhp,
+                      float* losses_out, float* prio_out, float* grad_out, float* fgrad_out, float* taus_out, float* tau_hats_out, ts_stream_t stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * TD3 / DDPG: ContinuousActorDeterministic (utils/net/continuous.py:26-85) + the SAC critics,

@@ -156,6 +156,11 @@ def _bdqn_prototypes(lib) -> None:
         "ts_iqn_mlp_forward": [p, p, p, i64_, p, i64_, p, p, p, p],
         "ts_iqn_mlp_next_dist": [p, p, p, p, i64_, p, i64_, p, i64_, p, p, p, p, p],
         "ts_iqn_mlp_update": [p, p, p, i32, p, p, i64_, p, p, p, p, i64_, p, i64_, p, i64_, p, p, p, p, p],
+        # ts_fqf_mlp_* (desc: a host int64[TS_FQF_MLP_DESC_LEN]; the fraction network's flat vector behind the model's)
+        "ts_fqf_mlp_layout": [p, i64_, p],
+        "ts_fqf_mlp_forward": [p, p, p, p, i64_, p, p, p, p, p, p, p, p, p, p],
+        "ts_fqf_mlp_next_dist": [p, p, p, p, p, i64_, p, p, p, p, p, p, p],
+        "ts_fqf_mlp_update": [p, p, p, i32, p, p, i64_, p, p, p, i64_, p, p, p, p, p, i64_, p, p, p, p, p, p, p, p, p],
     }
     for name, argtypes in protos.items():
         if hasattr(lib, name):                       # (a library built before these existed still serves every other engine)

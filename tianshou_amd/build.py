@@ -28,6 +28,7 @@ EXTRA_FLAGS: dict[str, list[str]] = {
     "ts_c51_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "ts_rainbow_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "ts_iqn_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "ts_fqf_mlp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     # likewise for the Box-Muller products of ts_normal_fill (ts::normal4) and the float32 uniform fill
     "ts_index.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }

@@ -30,110 +30,11 @@
 #pragma clang fp contract(off)
 #include <algorithm>
 
-#include "ts_atom_head.h"     // RPT, row_sum8, tiles_of, check_batch (and ts_mlp_tile.h)
-#include "ts_qr_terms.h"
+#include "ts_iqn_walk.h"      // the network, the sample walk forward and backward, the pair loss (shared with ts_fqf_mlp.hip)
 
 namespace {
 
-constexpr int MAX_LAST = 2, MAX_COS = 64, MAX_SAMPLES = 64;
-constexpr int TP = MAX_SAMPLES | 1;         // pitch of the per-row sample tables
-constexpr int OP = TILE + 1;                // pitch of the head's output block
-
-struct INet {
-    int obs_dim, n_act, nt, nh, n_cos, feat_lin, F;
-    Lay t[MAX_TRUNK], fo, emb, h[MAX_LAST], head;
-    int x_at, t_at[MAX_TRUNK], f_at, cs_at, pc, phi_at, h_at[MAX_LAST], df_at, ob_at, th_at, tg_at, row_at;
-    int P, lds_floats;
-};
-
-// Y[32][N] = act((X (.) X2) W + b); PROD false: X alone.  The lane mapping of dense_relu; K is a hidden width (even).
-template <bool PROD, bool RELU>
-__device__ void dense(const float* __restrict__ w, int K, int N, const float* X, const float* X2, int px, float* Y, int py) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
-    for (int nb = wave; nb < N / 32; nb += 4) {
-        const int n = nb * 32 + i;
-        const float* wp = w + n;
-        const float* xp = X + i * px + h;
-        const float* x2p = X2 + i * px + h;
-        f32x16 acc = {};
-#pragma unroll 8
-        for (int k = 0; k < K; k += 2) acc = mfma32(PROD ? xp[k] * x2p[k] : xp[k], wp[(size_t)(k + h) * N], acc);
-        const float bias = wp[(size_t)K * N];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) Y[featF(r, h) * py + n] = RELU ? fmaxf(acc[r] + bias, 0.f) : acc[r] + bias;
-    }
-}
-
-// the final Linear: ob[32][A] = (X (.) X2) W + b as one 32-column block on wave 0, the weight loads masked past column A
-template <bool PROD>
-__device__ void head_block(const float* __restrict__ w, int K, int A, const float* X, const float* X2, int px, float* ob) {
-    if (threadIdx.x >= 64) return;
-    const int i = threadIdx.x & 31, h = threadIdx.x >> 5;
-    const bool live = i < A;
-    const float* wp = w + (live ? i : 0);                      // past column A: column 0 is read, 0 is used
-    const float* xp = X + i * px + h;
-    const float* x2p = X2 + i * px + h;
-    f32x16 acc = {};
-#pragma unroll 8
-    for (int k = 0; k < K; k += 2) {
-        const float b = wp[(size_t)(k + h) * A];
-        acc = mfma32(PROD ? xp[k] * x2p[k] : xp[k], live ? b : 0.f, acc);
-    }
-    const float bias = wp[(size_t)K * A];
-    if (live) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ob[featF(r, h) * OP + i] = acc[r] + bias;
-    }
-}
-
-// the trunk (and the Net's linear output layer) on the tile whose observations are in LDS -> the features.  Ends behind a barrier.
-__device__ const float* features(const INet& net, const float* __restrict__ p, float* sm) {
-    const float* x = sm + net.x_at;
-    int px = net.obs_dim + 1;
-    for (int l = 0; l < net.nt; ++l) {
-        float* y = sm + net.t_at[l];
-        dense_relu(p + net.t[l].off, net.t[l].K, net.t[l].N, x, px, y, net.t[l].N + 1);
-        __syncthreads();
-        x = y; px = net.t[l].N + 1;
-    }
-    if (!net.feat_lin) return x;
-    dense<false, false>(p + net.fo.off, net.fo.K, net.F, x, x, px, sm + net.f_at, net.F + 1);
-    __syncthreads();
-    return sm + net.f_at;
-}
-
-// sample j up to the top of `last`'s hidden layers: cs, phi, h[0], h[1].  Ends behind a barrier.
-__device__ void sample_hidden(const INet& net, const float* __restrict__ p, const float* fa, float* sm, const float* __restrict__ tau, int N,
-                              int j, int64_t row0, int64_t B) {
-    float* cs = sm + net.cs_at;
-    float* phi = sm + net.phi_at;
-    const int C = net.n_cos, pc = net.pc, pf = net.F + 1;
-    for (int e = threadIdx.x; e < TILE * C; e += THREADS) {                  // one cosine per (row, k)
-        const int i = e / C, k = e - i * C;
-        const float t = row0 + i < B ? tau[(row0 + i) * N + j] : 0.f;
-        const float ipi = 3.14159274101257324f * (float)(k + 1);
-        cs[i * pc + k] = cosf(t * ipi);
-    }
-    __syncthreads();
-    dense_relu(p + net.emb.off, C, net.F, cs, pc, phi, pf);
-    __syncthreads();
-    if (net.nh >= 1) {
-        dense<true, true>(p + net.h[0].off, net.F, net.h[0].N, fa, phi, pf, sm + net.h_at[0], net.h[0].N + 1);
-        __syncthreads();
-    }
-    if (net.nh == 2) {
-        dense_relu(p + net.h[1].off, net.h[1].K, net.h[1].N, sm + net.h_at[0], net.h[0].N + 1, sm + net.h_at[1], net.h[1].N + 1);
-        __syncthreads();
-    }
-}
-
-// the final Linear of the sample whose hidden activations are in LDS -> ob.  Ends behind a barrier.
-__device__ void sample_head(const INet& net, const float* __restrict__ p, const float* fa, float* sm) {
-    float* ob = sm + net.ob_at;
-    if (net.nh == 0) head_block<true>(p + net.head.off, net.F, net.n_act, fa, sm + net.phi_at, net.F + 1, ob);
-    else head_block<false>(p + net.head.off, net.head.K, net.n_act, sm + net.h_at[net.nh - 1], sm + net.h_at[net.nh - 1], net.head.K + 1, ob);
-    __syncthreads();
-}
+constexpr int MAX_LAST = 2;                 // this file's envelope of `last` (the walk itself takes MAX_LAST_H)
 
 // ---- INFER: ImplicitQuantileNetwork.forward + the mean over the samples + the greedy action; TARGET: QRDQN._target_q -------------
 struct WalkArgs {
@@ -160,7 +61,7 @@ __global__ __launch_bounds__(THREADS) void iqnm_walk_kernel(WalkArgs a) {
     int* sel = reinterpret_cast<int*>(sm + net.row_at);
     float qa[4] = {0.f, 0.f, 0.f, 0.f};                 // thread (row, t): the sample sums of the actions t, t + 8, t + 16, t + 24
     for (int j = 0; j < a.N; ++j) {
-        sample_hidden(net, a.params, fa, sm, a.tau, a.N, j, row0, a.B);
+        sample_hidden(net, a.params, fa, sm, TauSrc{a.tau, a.N, row0, a.B}, j);
         sample_head(net, a.params, fa, sm);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -200,7 +101,7 @@ __global__ __launch_bounds__(THREADS) void iqnm_walk_kernel(WalkArgs a) {
     float* kept = sm + net.th_at;
     const int s = sel[row];
     for (int j = 0; j < a.N2; ++j) {
-        sample_hidden(net, pe, fa, sm, a.tau2, a.N2, j, row0, a.B);
+        sample_hidden(net, pe, fa, sm, TauSrc{a.tau2, a.N2, row0, a.B}, j);
         sample_head(net, pe, fa, sm);
         if ((s & 7) == t) kept[row * TP + j] = ob[row * OP + s];
     }
@@ -216,83 +117,6 @@ __global__ __launch_bounds__(THREADS) void iqnm_walk_kernel(WalkArgs a) {
 }
 
 // ---- STEP: forward walk, pair loss, backward walk, trunk backward, the tile's slab -------------------------------------------------
-
-// slab[k N + n] (+)= sum_m (Hin (.) Hin2)[m][k] dZ[m][n], slab[K N + n] (+)= sum_m dZ[m][n]: wgrad's blocks (32 x 32, round-robin over
-// the waves, so a block has one owner wave and an element one owner lane for the whole walk), K and N of any size (masked loads).
-// `first`: the sample that writes instead of adding.
-template <bool PROD>
-__device__ void wgrad_acc(float* __restrict__ slab, bool first, const float* Hin, const float* Hin2, int pin, int K, const float* dZ, int pz, int N) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
-    const int nbs = (N + 31) / 32, kbs = (K + 31) / 32;
-    for (int blk = wave; blk < kbs * nbs; blk += 4) {
-        const int kb = blk / nbs, nb = blk - kb * nbs;
-        const int kc = kb * 32 + i, n = nb * 32 + i;
-        const bool klive = kc < K, nlive = n < N;
-        const int kk = klive ? kc : 0, nn = nlive ? n : 0;
-        f32x16 acc = {};
-#pragma unroll
-        for (int m = 0; m < TILE; m += 2) {
-            float hv = Hin[(m + h) * pin + kk];
-            if (PROD) hv *= Hin2[(m + h) * pin + kk];
-            const float z = dZ[(m + h) * pz + nn];
-            acc = mfma32(klive ? hv : 0.f, nlive ? z : 0.f, acc);
-        }
-        if (nlive) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int k = kb * 32 + featF(r, h);
-                if (k < K) {
-                    float* s = slab + (size_t)k * N + n;
-                    *s = first ? acc[r] : *s + acc[r];
-                }
-            }
-        }
-    }
-    for (int n = threadIdx.x; n < N; n += THREADS) {
-        float s = 0.f;
-        for (int m = 0; m < TILE; ++m) s += dZ[m * pz + n];
-        float* q = slab + (size_t)K * N + n;
-        *q = first ? s : *q + s;
-    }
-}
-
-// dx[32][F] = dZ W^T from one source (a hidden layer above: dgrad's MFMA pass; or the final Linear: dgrad's head pass), not stored:
-// the lane that owns element (m, k) adds dx phi to df and replaces phi by d phi = dx f (phi > 0)
-__device__ void dgrad_embed(float* phi, float* df, const float* fa, int pf, int F, MSrc ms, HSrc hd) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
-    for (int kb = wave; kb < F / 32; kb += 4) {
-        const int kc = kb * 32 + i;
-        f32x16 acc = {};
-        if (ms.dz) {
-            const int N = ms.N;
-            const float* wrow = ms.w + (size_t)kc * N + 4 * h;
-            const float* zp = ms.dz + i * ms.pz + 4 * h;
-#pragma unroll 2
-            for (int n = 0; n < N; n += 8) {
-                const f32x4 w4 = *reinterpret_cast<const f32x4*>(wrow + n);
-                acc = mfma32(zp[n], w4[0], acc);
-                acc = mfma32(zp[n + 1], w4[1], acc);
-                acc = mfma32(zp[n + 2], w4[2], acc);
-                acc = mfma32(zp[n + 3], w4[3], acc);
-            }
-        } else {
-            const int A = hd.A;
-            const float* wrow = hd.w + (size_t)kc * A;
-            for (int a = 0; a < A; ++a) {
-                const float w = wrow[a];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] += hd.dq[featF(r, h) * hd.pq + a] * w;
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int idx = featF(r, h) * pf + kc;
-            const float dx = acc[r], ph = phi[idx];
-            df[idx] += dx * ph;
-            phi[idx] = ph > 0.f ? dx * fa[idx] : 0.f;
-        }
-    }
-}
 
 struct StepArgs {
     INet net;
@@ -310,12 +134,11 @@ __global__ __launch_bounds__(THREADS) void iqnm_step_kernel(StepArgs a) {
     float* slab = a.slabs + (size_t)blockIdx.x * net.P;
     float* th = sm + net.th_at;                              // theta of the taken action per sample, then d loss / d theta
     float* tg = sm + net.tg_at;                              // the targets T
-    float* ob = sm + net.ob_at;                              // the head's output block, then its gradient
-    float* phi = sm + net.phi_at;
+    float* ob = sm + net.ob_at;                              // the head's output block (its gradient in the backward walk)
     float* df = sm + net.df_at;
     float* term = sm + net.row_at + TILE;
     int* sel = reinterpret_cast<int*>(sm + net.row_at);
-    const int N = a.N, N2 = a.N2, A = net.n_act, F = net.F, pf = F + 1, nh = net.nh;
+    const int N = a.N, N2 = a.N2, A = net.n_act, pf = net.F + 1;
     const int row = threadIdx.x >> 3, t = threadIdx.x & 7;
     if (threadIdx.x < TILE) {                                // rows beyond B select nothing: exactly zero in the loss and in every slab
         const int64_t b = row0 + threadIdx.x;
@@ -336,34 +159,15 @@ __global__ __launch_bounds__(THREADS) void iqnm_step_kernel(StepArgs a) {
     const float* fa = features(net, p, sm);
     const int s = sel[row];
     for (int j = 0; j < N; ++j) {                            // the forward walk
-        sample_hidden(net, p, fa, sm, a.tau, N, j, row0, a.B);
+        sample_hidden(net, p, fa, sm, TauSrc{a.tau, N, row0, a.B}, j);
         sample_head(net, p, fa, sm);
         if (s >= 0 && (s & 7) == t) th[row * TP + j] = ob[row * OP + s];
     }
     __syncthreads();
-    {   // the pair loss of row (tid >> 3): thread t takes theta_i, i = t (mod 8), against the row's N' targets
+    {   // the pair loss of row (tid >> 3) against the row's N' targets
         const int64_t b = row0 + row;
-        const bool live = b < a.B;
-        const float wb = live ? (a.weight ? a.weight[b] : 1.f) : 0.f;
-        const float scale = wb / ((float)a.B * (float)N);
-        float wl = 0.f, sl = 0.f;
-        if (live) {
-            float* mine = th + row * TP;
-            for (int i = t; i < N; i += RPT) {
-                float li, ai, g;
-                qr_terms(tg + row * TP, N2, mine[i], a.tau[b * N + i], li, ai, g);
-                mine[i] = -g * scale;                        // only this thread reads theta_i
-                wl += li;
-                sl += ai;
-            }
-        }
-        wl = row_sum8(wl);
-        sl = row_sum8(sl);
-        if (t == 0) {
-            const float huber = wl / (float)N;
-            if (live) a.prio_out[b] = sl / (float)N;
-            term[row] = live ? huber * wb / (float)a.B : 0.f;
-        }
+        const float v = pair_loss_row(th, tg, a.tau, b * N, N, N2, a.weight, b, a.B, a.prio_out);
+        if (t == 0) term[row] = v;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -371,66 +175,11 @@ __global__ __launch_bounds__(THREADS) void iqnm_step_kernel(StepArgs a) {
         for (int m = 0; m < TILE; ++m) sum += term[m];
         a.partials[blockIdx.x] = sum;
     }
-    float* h0 = sm + net.h_at[0];
-    float* h1 = sm + net.h_at[1];
-    const int p0 = net.h[0].N + 1, p1 = net.h[1].N + 1;
     for (int j = 0; j < N; ++j) {                            // the backward walk: the slab blocks take sample j, j ascending
-        const bool first = j == 0;
-        sample_hidden(net, p, fa, sm, a.tau, N, j, row0, a.B);
-        for (int idx = threadIdx.x; idx < TILE * TILE; idx += THREADS) {
-            const int m = idx >> 5, c = idx & 31;
-            ob[m * OP + c] = c == sel[m] ? th[m * TP + j] : 0.f;
-        }
-        __syncthreads();
-        const HSrc hs{ob, OP, p + net.head.off, A};
-        if (nh == 0) {
-            wgrad_acc<true>(slab + net.head.off, first, fa, phi, pf, F, ob, OP, A);
-            __syncthreads();
-            dgrad_embed(phi, df, fa, pf, F, MSrc{}, hs);
-        } else {
-            float* top = nh == 2 ? h1 : h0;
-            const int ptop = nh == 2 ? p1 : p0;
-            wgrad_acc<false>(slab + net.head.off, first, top, top, ptop, net.head.K, ob, OP, A);
-            __syncthreads();
-            dgrad(top, ptop, net.head.K, MSrc{}, MSrc{}, hs, HSrc{});
-            __syncthreads();
-            if (nh == 2) {
-                wgrad_acc<false>(slab + net.h[1].off, first, h0, h0, p0, net.h[1].K, h1, p1, net.h[1].N);
-                __syncthreads();
-                dgrad(h0, p0, net.h[0].N, MSrc{h1, p1, p + net.h[1].off, net.h[1].N}, MSrc{}, HSrc{}, HSrc{});
-                __syncthreads();
-            }
-            wgrad_acc<true>(slab + net.h[0].off, first, fa, phi, pf, F, h0, p0, net.h[0].N);
-            __syncthreads();
-            dgrad_embed(phi, df, fa, pf, F, MSrc{h0, p0, p + net.h[0].off, net.h[0].N}, HSrc{});
-        }
-        __syncthreads();
-        wgrad_acc<false>(slab + net.emb.off, first, sm + net.cs_at, sm + net.cs_at, net.pc, net.n_cos, phi, pf, F);
-        __syncthreads();                                     // the next sample overwrites cs and phi
+        sample_hidden(net, p, fa, sm, TauSrc{a.tau, N, row0, a.B}, j);
+        sample_backward(net, p, fa, sm, slab, th, sel, j, j == 0);
     }
-    // the trunk backward on df
-    float* top = sm + net.t_at[net.nt - 1];
-    const int ptop = net.t[net.nt - 1].N + 1;
-    if (net.feat_lin) {
-        wgrad(slab + net.fo.off, top, ptop, net.fo.K, df, pf, F);
-        __syncthreads();
-        dgrad(top, ptop, net.fo.K, MSrc{df, pf, p + net.fo.off, F}, MSrc{}, HSrc{}, HSrc{});
-    } else {                                                 // the features are the top ReLU layer itself (pitch pf)
-        for (int idx = threadIdx.x; idx < TILE * F; idx += THREADS) {
-            const int r = idx / F, o = r * pf + idx - r * F;
-            top[o] = top[o] > 0.f ? df[o] : 0.f;
-        }
-    }
-    __syncthreads();
-    for (int l = net.nt - 1; l >= 0; --l) {
-        const float* in = l > 0 ? sm + net.t_at[l - 1] : sm + net.x_at;
-        wgrad(slab + net.t[l].off, in, l > 0 ? net.t[l - 1].N + 1 : net.obs_dim + 1, net.t[l].K, sm + net.t_at[l], net.t[l].N + 1, net.t[l].N);
-        if (l == 0) break;
-        __syncthreads();
-        MSrc ms{sm + net.t_at[l], net.t[l].N + 1, p + net.t[l].off, net.t[l].N};
-        dgrad(sm + net.t_at[l - 1], net.t[l - 1].N + 1, net.t[l - 1].N, ms, MSrc{}, HSrc{}, HSrc{});
-        __syncthreads();
-    }
+    trunk_backward(net, p, sm, slab);
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
@@ -445,63 +194,10 @@ __global__ __launch_bounds__(THREADS) void iqnm_step_kernel(StepArgs a) {
 //                                                              = 28,352 floats = 113,664 B
 //   (refused)     obs 8, [256, 256] -> 256, C 64, H (256,):    6 x 8,224 floats alone = 197,376 B > 163,840 B
 int make_net(const int64_t* d, const char* who, INet* out) {
-    TS_REQUIRE(d != nullptr, TS_ERR_INVALID_ARG, "%s: NULL network description", who);
-    INet n{};
-    const int64_t obs_dim = d[0], n_act = d[1], nt = d[2], fl = d[7], n_cos = d[8], nh = d[9];
-    TS_REQUIRE(obs_dim >= 1 && obs_dim <= 256, TS_ERR_UNSUPPORTED, "%s: obs_dim %lld outside [1, 256]", who, (long long)obs_dim);
-    TS_REQUIRE(n_act >= 1 && n_act <= MAX_ACT, TS_ERR_UNSUPPORTED, "%s: %lld actions outside [1, 32]", who, (long long)n_act);
-    TS_REQUIRE(nt >= 1 && nt <= MAX_TRUNK, TS_ERR_UNSUPPORTED, "%s: %lld trunk hidden layers outside [1, 4]", who, (long long)nt);
-    TS_REQUIRE(nh >= 0 && nh <= MAX_LAST, TS_ERR_UNSUPPORTED, "%s: %lld hidden layers in `last` outside [0, 2]", who, (long long)nh);
-    TS_REQUIRE(n_cos >= 1 && n_cos <= MAX_COS, TS_ERR_UNSUPPORTED, "%s: num_cosines %lld outside [1, 64]", who, (long long)n_cos);
-    auto width_ok = [](int64_t w) { return w >= 32 && w <= 256 && w % 32 == 0; };
-    TS_REQUIRE(fl == 0 || width_ok(fl), TS_ERR_UNSUPPORTED, "%s: feature width %lld is no multiple of 32 in [32, 256]", who, (long long)fl);
-    n.obs_dim = (int)obs_dim; n.n_act = (int)n_act; n.nt = (int)nt; n.nh = (int)nh; n.n_cos = (int)n_cos; n.feat_lin = fl != 0;
-    int off = 0, at = 0;
-    auto add = [&](Lay* l, int K, int N) { l->K = K; l->N = N; l->off = off; off += (K + 1) * N; };
-    auto carve = [&](int floats) { const int o = at; at += floats; return o; };
-    n.x_at = carve(TILE * (n.obs_dim + 1));
-    int k = n.obs_dim;
-    for (int i = 0; i < n.nt; ++i) {
-        const int64_t w = d[3 + i];
-        TS_REQUIRE(width_ok(w), TS_ERR_UNSUPPORTED, "%s: hidden width %lld is no multiple of 32 in [32, 256]", who, (long long)w);
-        add(&n.t[i], k, (int)w);
-        n.t_at[i] = carve(TILE * (n.t[i].N + 1));
-        k = n.t[i].N;
-    }
-    if (n.feat_lin) {
-        add(&n.fo, k, (int)fl);
-        n.f_at = carve(TILE * ((int)fl + 1));
-        k = (int)fl;
-    }
-    n.F = k;
-    add(&n.emb, n.n_cos, n.F);
-    n.pc = n.n_cos | 1;
-    n.cs_at = carve(TILE * n.pc);
-    n.phi_at = carve(TILE * (n.F + 1));
-    for (int i = 0; i < n.nh; ++i) {
-        const int64_t w = d[10 + i];
-        TS_REQUIRE(width_ok(w), TS_ERR_UNSUPPORTED, "%s: hidden width %lld is no multiple of 32 in [32, 256]", who, (long long)w);
-        add(&n.h[i], k, (int)w);
-        n.h_at[i] = carve(TILE * (n.h[i].N + 1));
-        k = n.h[i].N;
-    }
-    add(&n.head, k, n.n_act);
-    n.df_at = carve(TILE * (n.F + 1));
-    n.ob_at = carve(TILE * OP);
-    n.th_at = carve(TILE * TP);
-    n.tg_at = carve(TILE * TP);
-    n.row_at = carve(4 * TILE);
-    n.P = off;
-    n.lds_floats = at;
-    TS_REQUIRE((size_t)at * 4 + 256 <= (size_t)LDS_LIMIT, TS_ERR_UNSUPPORTED,
+    if (int rc = make_inet(d, who, MAX_LAST, out)) return rc;
+    TS_REQUIRE((size_t)out->lds_floats * 4 + 256 <= (size_t)LDS_LIMIT, TS_ERR_UNSUPPORTED,
                "%s: the activations and sample tables of one 32-row tile need %zu bytes of LDS, the workgroup limit is %d", who,
-               (size_t)at * 4 + 256, LDS_LIMIT);
-    *out = n;
-    return TS_OK;
-}
-
-int check_samples(int64_t N, const char* what, const char* who) {
-    TS_REQUIRE(N >= 2 && N <= MAX_SAMPLES, TS_ERR_UNSUPPORTED, "%s: %s = %lld outside [2, 64]", who, what, (long long)N);
+               (size_t)out->lds_floats * 4 + 256, LDS_LIMIT);
     return TS_OK;
 }
 

@@ -1258,6 +1258,17 @@ class _QState(NamedTuple):
     from_torch: Callable  # the engine module's flat_from_torch(tensors, *dims, device)
     to_torch: Callable    # the engine module's flat_to_torch(flat, *dims)
     dims: Callable        # engine -> the dims tuple of the two converters
+    second: "_QSecond | None" = None      # a second module with its own optimizer beside the Q network (HipFQFMlp)
+
+
+class _QSecond(NamedTuple):
+    """The second module of a Q-learning class (FQF's fraction network): it has no lagged copy; its state is the engine's `fparams`,
+    `f_m` / `f_v` (checkpoint.adam_state's pair of its optimizer) and `f_step`."""
+    module: object        # the torch module
+    optim: object         # its Algorithm.Optimizer wrapper
+    keys: list
+    from_torch: Callable  # tensors in `keys` order -> flat (on the device)
+    to_torch: Callable    # flat -> tensors in `keys` order
 
 
 def _q_layout(buffer, who: str):
@@ -1312,6 +1323,9 @@ def _q_load(algo, eng):
     eng.adam_m, eng.adam_v = st.from_torch(ms, *dims, dev), st.from_torch(vs, *dims, dev)
     if eng.params_old is not None:
         eng.params_old = st.from_torch([p.detach() for p in _q_old_params(algo, st)], *dims, dev)
+    if st.second is not None:
+        ms, vs, eng.f_step = adam_state(st.second.optim._optim, params_by_keys(st.second.module, st.second.keys))
+        eng.f_m, eng.f_v = st.second.from_torch(ms), st.second.from_torch(vs)
     return eng
 
 
@@ -1331,6 +1345,13 @@ def _q_write_back(algo) -> None:
             for p, t in zip(_q_old_params(algo, st), st.to_torch(eng.params_old, *dims)):
                 algo._hip_put(p, t)
     store_adam_state(algo.optim._optim, params, st.to_torch(eng.adam_m, *dims), st.to_torch(eng.adam_v, *dims), eng.adam_step)
+    if st.second is not None:
+        sec = st.second
+        params = params_by_keys(sec.module, sec.keys)
+        with torch.no_grad():
+            for p, t in zip(params, sec.to_torch(eng.fparams)):
+                algo._hip_put(p, t)
+        store_adam_state(sec.optim._optim, params, sec.to_torch(eng.f_m), sec.to_torch(eng.f_v), eng.f_step)
 
 
 # -- what the off-policy actor-critic classes (HipSAC, HipREDQ, HipDiscreteSAC, HipTD3 / HipDDPG / HipTD3BC) share: the same two
@@ -2241,6 +2262,84 @@ def make_hip_iqn_mlp(ref=None):
         _hip_write_back = _q_write_back
 
     return HipIQNMlp
+
+
+# ---------------------------------------------------------------------------------------------------
+# FQF on the plain MLP Net over vector observations (test/discrete/test_fqf.py)
+# ---------------------------------------------------------------------------------------------------
+def make_hip_fqf_mlp(ref=None):
+    """Returns HipFQFMlp(FQF): the FQF hooks (fqf.py:178-256) on tianshou_amd.fqf_mlp.FQFMlpEngine for a `FullQuantileFunction(
+    preprocess_net=Net(...), hidden_sizes, num_cosines)` with its `FractionProposalNetwork` over a plain or prioritized buffer of
+    vector observations: `_target_q` + the n-step returns ([B, N]) are one launch, the update and the two optimizer steps three.
+    Adam on the model, Adam or RMSprop on the fraction network (`optimizer_fields`).  What is outside the envelope
+    (fqf_mlp.ENVELOPE) raises NotImplementedError in the constructor; nothing falls back to eager PyTorch.  `policy.forward` and
+    the collector's `add_exploration_noise` stay the reference's.  The fractions of the last update stay in the engine
+    (`last_taus`, `last_tau_hats`, `last_target_taus`, `last_target_tau_hats`).
+    `ref`: optional namespace replacing the tianshou imports (see `_ref`)."""
+    FQF = _ref(ref, "tianshou.algorithm.modelfree.fqf", "FQF")
+    FQFTrainingStats = _ref(ref, "tianshou.algorithm.modelfree.fqf", "FQFTrainingStats")
+
+    from . import fqf_mlp as M
+
+    def _fraction_fields(opt) -> dict:
+        of = optimizer_fields(opt)
+        return dict(f_optimizer=of["optimizer"], f_lr=of["lr"], f_betas=of.get("betas", (0.9, 0.999)), f_adam_eps=of["adam_eps"],
+                    f_weight_decay=of["weight_decay"], f_rms_alpha=of.get("rms_alpha", 0.99), f_rms_momentum=of.get("rms_momentum", 0.0),
+                    f_rms_centered=of.get("rms_centered", False))
+
+    class HipFQFMlp(_HipGlue, FQF):
+        _HIP_LR = (("lr", "optim"), ("f_lr", "fraction_optim"))
+
+        def __init__(self, *args, device="cuda", **kwargs):
+            super().__init__(*args, **kwargs)
+            self._hip_device = torch.device(device)
+            self._hip_layers, self._hip_fractions = M.describe_module(self.policy.model, self.policy.fraction_model)
+            _adam_of(self.optim)
+            _fraction_fields(self.fraction_optim._optim)
+            self._hip_engine = None
+            self._hip_glue_init()
+
+        def _hip_qstate(self):
+            layers, n = self._hip_layers, self._hip_fractions             # what the engine was built with
+            feat, dev = M.layout(layers, n)["F"], self._hip_device
+            second = _QSecond(self.policy.fraction_model, self.fraction_optim, M.FRACTION_KEYS,
+                              lambda t: M.fraction_from_torch(t, feat, n, dev), lambda f: M.fraction_to_torch(f, feat, n))
+            return _QState(M.state_dict_keys(layers), M.flat_from_torch, M.flat_to_torch, lambda eng: layers, second)
+
+        def _engine(self):
+            if self._hip_engine is None:
+                st = self._hip_qstate()
+                cfg = M.FQFConfig(ent_coef=float(self.ent_coef), **_q_config_fields(self), **_fraction_fields(self.fraction_optim._optim))
+                fflat = st.second.from_torch([p.detach() for p in params_by_keys(st.second.module, st.second.keys)])
+                self._hip_engine = _q_load(self, M.FQFMlpEngine(self._hip_layers, self._hip_fractions, _q_flat(self, self._hip_layers), fflat, cfg))
+            return self._hip_engine
+
+        def _preprocess_batch(self, batch, buffer, indices):
+            obs = np.asarray(buffer.obs)
+            if obs.ndim < 2 or int(np.prod(obs.shape[1:])) != self._hip_layers[0] or int(getattr(buffer, "stack_num", 1)) != 1:
+                raise NotImplementedError("HipFQFMlp: the buffer must hold vector observations of the model's state_shape, stack_num 1")
+            m, idx = _q_begin(self, "HipFQFMlp", batch, buffer, indices)
+            rows = m.obs.reshape(m.obs.shape[0], -1)
+            nxt = m.obs_next.reshape(m.obs_next.shape[0], -1) if m.obs_next is not None else None
+            self._hip_obs, batch.returns = self._engine().preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt)
+            return batch
+
+        def _update_with_batch(self, batch):
+            self._hip_refresh_lr()
+            eng, m = self._hip_engine, self._hip_mirror
+            eng.cfg.ent_coef = float(self.ent_coef)
+            weight = batch.pop("weight", None)
+            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device) if hasattr(batch, "act") else m.act[self._hip_idx]
+            losses, prio = eng.update_with_batch(self._hip_obs, act, batch.returns, weight)
+            self._iter = eng.iter
+            batch.weight = prio                                                   # prio-buffer, fqf.py:220
+            self._hip_after_update()
+            ql, fl, el = (float(x) for x in losses.tolist())                      # one synchronisation for the three
+            return FQFTrainingStats(loss=ql + (fl - eng.cfg.ent_coef * el), quantile_loss=ql, fraction_loss=fl, entropy_loss=el)
+
+        _hip_write_back = _q_write_back
+
+    return HipFQFMlp
 
 
 def make_hip_discrete_bcq(ref=None):
