@@ -10,7 +10,7 @@ Setup: test/discrete/test_c51.py.  `update_with_batch` is two launches (ts_c51_m
 step kernel.  There is no CPU path: every function calls libtsengine.so.
 
 `layers` = (obs_dim, trunk widths, n_act, n_atoms) and the flat layout are qrdqn_mlp's (a plain Net whose last Linear has
-n_act * n_atoms outputs), so its converters serve here.
+n_act * n_atoms outputs), so its converters, envelope checks and module walk serve here.
 """
 from __future__ import annotations
 
@@ -19,17 +19,17 @@ import ctypes as C
 import torch
 
 from . import _lib
-from . import dqn_mlp as M
 from . import qrdqn_mlp as Q
-from .buffer import DeviceReplayBuffer, _i64_dev, gather_rows
+from . import vecq as V
+from .buffer import DeviceReplayBuffer
 from .dqn import DQNConfig
-from .drqn import gather_stacked_obs_pair
 from .returns import nstep_coefficients
 
 MAX_ATOMS = Q.MAX_ATOMS
 ENVELOPE = (f"Net on vector observations of 1 .. {Q.MAX_OBS} entries, 1 .. {Q.MAX_TRUNK} hidden layers, widths multiples of 32 in "
             f"[32, {Q.MAX_WIDTH}], ReLU, no norm_layer, no dueling_param, softmax=True, concat=False, 1 .. {Q.MAX_ACTIONS} actions, "
             f"num_atoms 2 .. {MAX_ATOMS}, the activations and the three atom tables of a 32-row tile within 160 KB of LDS")
+_F = V.Family("C51 MLP", ENVELOPE)
 
 _desc = Q._desc
 state_dict_keys, flat_from_torch, flat_to_torch = Q.state_dict_keys, Q.flat_from_torch, Q.flat_to_torch
@@ -37,33 +37,12 @@ state_dict_keys, flat_from_torch, flat_to_torch = Q.state_dict_keys, Q.flat_from
 
 def layout(layers, batch: int = 1) -> dict:
     """ts_c51_mlp_layout -> {count, lds_bytes, workspace_bytes}; NotImplementedError when the tile does not fit the LDS."""
-    out = (C.c_int64 * 16)()
-    try:
-        _lib.check(_lib.load().ts_c51_mlp_layout(_desc(layers), _lib.i64(batch), out))
-    except _lib.EngineError as e:
-        if e.code != _lib.TS_ERR_UNSUPPORTED:
-            raise
-        raise NotImplementedError(f"C51 MLP: {e}; supported: {ENVELOPE}") from None
-    return {"count": int(out[0]), "lds_bytes": int(out[1]), "workspace_bytes": int(out[2])}
+    return _F.layout("ts_c51_mlp_layout", _desc(layers), batch)
 
 
 def make_layers(obs_dim, trunk, n_act, n_atoms) -> tuple:
     """The model description every function here takes; raises NotImplementedError, naming the reason, outside the envelope."""
-    obs_dim, trunk, n_act, n_atoms = int(obs_dim), tuple(int(w) for w in trunk), int(n_act), int(n_atoms)
-    if not 1 <= obs_dim <= Q.MAX_OBS:
-        raise NotImplementedError(f"C51 MLP: obs_dim = {obs_dim} is outside [1, {Q.MAX_OBS}]; supported: {ENVELOPE}")
-    if not 1 <= len(trunk) <= Q.MAX_TRUNK:
-        raise NotImplementedError(f"C51 MLP: {len(trunk)} hidden layers (1 .. {Q.MAX_TRUNK}); supported: {ENVELOPE}")
-    bad = [w for w in trunk if w % 32 or not 32 <= w <= Q.MAX_WIDTH]
-    if bad:
-        raise NotImplementedError(f"C51 MLP: hidden width {bad[0]} is no multiple of 32 in [32, {Q.MAX_WIDTH}]; supported: {ENVELOPE}")
-    if not 1 <= n_act <= Q.MAX_ACTIONS:
-        raise NotImplementedError(f"C51 MLP: {n_act} actions (1 .. {Q.MAX_ACTIONS}); supported: {ENVELOPE}")
-    if not 2 <= n_atoms <= MAX_ATOMS:
-        raise NotImplementedError(f"C51 MLP: num_atoms = {n_atoms} is outside [2, {MAX_ATOMS}]; supported: {ENVELOPE}")
-    layers = (obs_dim, trunk, n_act, n_atoms)
-    layout(layers)                                     # the LDS carve of a tile (three tables) is the library's arithmetic
-    return layers
+    return Q._make_layers(_F, layout, obs_dim, trunk, n_act, n_atoms)      # (`layout`: the carve with three tables)
 
 
 def support(v_min: float, v_max: float, n_atoms: int, device) -> torch.Tensor:
@@ -74,65 +53,39 @@ def support(v_min: float, v_max: float, n_atoms: int, device) -> torch.Tensor:
 def describe_module(net) -> tuple:
     """-> `layers` of a Net-shaped module with `softmax=True` (common.py:286-341), or raises NotImplementedError naming what is
     not supported."""
-    for name in ("model", "use_dueling", "softmax", "num_atoms"):
-        if not hasattr(net, name):
-            raise NotImplementedError(f"C51 MLP: a Net is needed (found {type(net).__name__} without `{name}`); supported: {ENVELOPE}")
+    _F.require_net(net)
     if not net.softmax:
-        raise NotImplementedError(f"C51 MLP: softmax=True is needed (QRDQN on a Net is qrdqn_mlp's); supported: {ENVELOPE}")
+        raise _F.refuse("softmax=True is needed (QRDQN on a Net is qrdqn_mlp's)")
     if net.use_dueling:
-        raise NotImplementedError(f"C51 MLP: dueling_param with atoms is not supported; supported: {ENVELOPE}")
+        raise _F.refuse("dueling_param with atoms is not supported")
     n_atoms = int(net.num_atoms)
-    if not 2 <= n_atoms <= MAX_ATOMS:
-        raise NotImplementedError(f"C51 MLP: num_atoms = {n_atoms} is outside [2, {MAX_ATOMS}]; supported: {ENVELOPE}")
-    mods = list(net.model.model.children())
-    for j, m in enumerate(mods):
-        if j % 2 == 0 and (not isinstance(m, torch.nn.Linear) or m.bias is None):
-            raise NotImplementedError(f"C51 MLP: Linear layers with bias followed by ReLU only, no norm_layer (found {type(m).__name__}); "
-                                      f"supported: {ENVELOPE}")
-        if j % 2 == 1 and not isinstance(m, torch.nn.ReLU):
-            raise NotImplementedError(f"C51 MLP: the activation must be ReLU (found {type(m).__name__}); supported: {ENVELOPE}")
-    if len(mods) % 2 == 0 or len(mods) < 3:
-        raise NotImplementedError(f"C51 MLP: at least one hidden layer and a last Linear onto the outputs are needed (concat=True is "
-                                  f"not supported); supported: {ENVELOPE}")
-    lin = mods[0::2]
-    if lin[-1].out_features % n_atoms:
-        raise NotImplementedError(f"C51 MLP: {lin[-1].out_features} outputs are no multiple of num_atoms = {n_atoms}; supported: {ENVELOPE}")
-    layers = make_layers(lin[0].in_features, [l.out_features for l in lin[:-1]], lin[-1].out_features // n_atoms, n_atoms)
-    have = [k for k, _ in net.named_parameters()]
-    if have != state_dict_keys(layers):
-        raise NotImplementedError(f"C51 MLP: the model's parameters {have} are not a Net's {state_dict_keys(layers)}; supported: {ENVELOPE}")
-    return layers
+    _F.in_range("num_atoms", n_atoms, 2, MAX_ATOMS)
+    return Q._describe_plain(_F, make_layers, net, n_atoms)
 
 
-class C51MlpEngine:
+class C51MlpEngine(V.VecQEngine):
     """State of one C51 learner on one GPU: flat parameters, lagged copy, Adam moments, counters, the support.  `cfg` is a DQNConfig
     (`is_double` and `huber_delta` are not read: the online network always selects, c51.py:124-131, and the loss is a cross-entropy)."""
 
+    FAMILY = _F
+
     def __init__(self, layers, flat_params: torch.Tensor, cfg: DQNConfig, v_min: float = -10.0, v_max: float = 10.0):
-        if not flat_params.is_cuda:
-            raise RuntimeError("C51MlpEngine needs parameters on an MI355X (no CPU fallback)")
+        self._require_device(flat_params)
+        self._check_support(v_min, v_max)
+        layers = make_layers(*layers)
+        super().__init__(layers, _desc(layers), layout(layers)["count"], flat_params, cfg)
+        _, _, self.n_act, self.n_atoms = layers
+        self._set_support(v_min, v_max)
+
+    @staticmethod
+    def _check_support(v_min, v_max) -> None:
         if not v_min < v_max:
             raise ValueError(f"v_max must be larger than v_min, got {v_min=} and {v_max=}")
-        self.layers = make_layers(*layers)
-        self.obs_dim, _, self.n_act, self.n_atoms = self.layers
-        self.cfg = cfg
-        self._d = _desc(self.layers)
-        self.P = layout(self.layers)["count"]
-        if flat_params.numel() != self.P:
-            raise ValueError(f"expected {self.P} parameters, got {flat_params.numel()}")
-        self.device = flat_params.device
-        self.params = flat_params.detach().float().contiguous().clone()
-        self.params_old = self.params.clone() if cfg.target_update_freq > 0 else None    # dqn.py:240-246
-        self.adam_m, self.adam_v = torch.zeros_like(self.params), torch.zeros_like(self.params)
-        self.adam_step = 0
-        self.iter = 0
+
+    def _set_support(self, v_min, v_max) -> None:
         self.v_min, self.v_max = float(v_min), float(v_max)
         self.delta_z = (self.v_max - self.v_min) / (self.n_atoms - 1)                      # c51.py:118
         self.support = support(self.v_min, self.v_max, self.n_atoms, self.device)
-        self._ws = _lib.default_workspace(self.device.index or 0)
-
-    _obs = M.DQNMlpEngine._obs
-    apply_gradient = M.DQNMlpEngine.apply_gradient
 
     def _z(self):
         return _lib.ptr(self.support), self.v_min, self.v_max, self.delta_z
@@ -162,13 +115,7 @@ class C51MlpEngine:
                             obs_next_rows: torch.Tensor | None = None, coef=None):
         """-> (batch.obs float32[I, obs_dim], batch.obs_next float32[I, obs_dim], returns float32[I, N]).  obs_next is the ONE-step
         batch.obs_next (buffer_base.py:624-626): `_target_dist` reads it inside the update."""
-        if stack_num != 1:
-            raise NotImplementedError("C51 MLP: frame stacking is not supported (stack_num must be 1)")
-        pair = gather_stacked_obs_pair(obs_rows, buffer, indices, 1, 1, obs_next_rows)
-        if pair is None:
-            idx = _i64_dev(indices, buffer.device).reshape(-1)
-            nxt = gather_rows(obs_rows, buffer.next(idx)) if obs_next_rows is None else gather_rows(obs_next_rows, idx)
-            pair = (gather_rows(obs_rows, idx), nxt)
+        pair = self._obs_pair(buffer, obs_rows, indices, 1, obs_next_rows, None, stack_num)
         return self._obs(pair[0]), self._obs(pair[1]), self.support_returns(buffer, indices, coef)
 
     def _returns(self, returns, b):
@@ -180,8 +127,20 @@ class C51MlpEngine:
     def _lagged(self):
         """The network `_target_dist` evaluates at this call: the sync comes first (c51.py:147-149), so on a sync iteration it is
         the online one."""
-        sync = self.params_old is not None and self.iter % self.cfg.target_update_freq == 0    # dqn.py:283-285
-        return sync, (None if sync else self.params_old)
+        return None if self._sync_now() else self.params_old
+
+    def _update_args(self, obs, act, obs_next, returns, weight, grad_out, target_out):
+        """The argument checks of `update_with_batch` (RainbowMlpEngine's too) -> the converted (obs, act, obs_next, returns, weight)."""
+        obs, obs_next = self._obs(obs), self._obs(obs_next)
+        b = obs.shape[0]
+        returns = self._returns(returns, b)
+        if obs_next.shape[0] != b:
+            raise ValueError(f"act and obs_next must hold {b} rows")
+        act, weight = self._batch_args(b, act, weight, grad_out)
+        if target_out is not None and (tuple(target_out.shape) != (b, self.n_atoms) or target_out.dtype != torch.float32
+                                       or not target_out.is_contiguous()):
+            raise ValueError(f"target_out must be a contiguous float32 [{b}, {self.n_atoms}]")
+        return obs, act, obs_next, returns, weight
 
     # -- C51._target_dist ----------------------------------------------------------------------------------------------------------
     def target_dist(self, obs_next, returns) -> torch.Tensor:
@@ -191,7 +150,7 @@ class C51MlpEngine:
         returns = self._returns(returns, b)
         out = torch.empty((b, self.n_atoms), dtype=torch.float32, device=self.device)
         z, v_min, v_max, dz = self._z()
-        _lib.check(_lib.load().ts_c51_mlp_target_dist(_lib.ptr(self.params), _lib.ptr(self._lagged()[1]), self._d, z, v_min, v_max, dz,
+        _lib.check(_lib.load().ts_c51_mlp_target_dist(_lib.ptr(self.params), _lib.ptr(self._lagged()), self._d, z, v_min, v_max, dz,
                                                       _lib.ptr(obs_next), _lib.ptr(returns), _lib.i64(b), _lib.ptr(out),
                                                       _lib.current_stream(self.device)))
         return out
@@ -207,32 +166,16 @@ class C51MlpEngine:
         """-> (loss float32[1] device tensor, prio float32[B]); prio is the new batch.weight (c51.py:157).  On every
         target_update_freq-th call, the first included, the target is read from the current parameters and the lagged network takes
         the pre-step parameters inside the call.  A refused argument leaves the lagged network and both counters alone."""
-        obs, obs_next = self._obs(obs), self._obs(obs_next)
+        obs, act, obs_next, returns, weight = self._update_args(obs, act, obs_next, returns, weight, grad_out, target_out)
         b = obs.shape[0]
-        act = _i64_dev(act, self.device).reshape(-1)
-        returns = self._returns(returns, b)
-        if act.numel() != b or obs_next.shape[0] != b:
-            raise ValueError(f"act and obs_next must hold {b} rows")
-        if weight is not None:
-            weight = torch.as_tensor(weight, device=self.device).to(torch.float32).reshape(-1).contiguous()
-            if weight.numel() != b:
-                raise ValueError("weight length mismatch")
-        if grad_out is not None and (grad_out.numel() != self.P or grad_out.dtype != torch.float32):
-            raise ValueError("grad_out must be a float32 vector of the model's size")
-        if target_out is not None and (tuple(target_out.shape) != (b, self.n_atoms) or target_out.dtype != torch.float32
-                                       or not target_out.is_contiguous()):
-            raise ValueError(f"target_out must be a contiguous float32 [{b}, {self.n_atoms}]")
-        sync, _ = self._lagged()
         prio = torch.empty(b, dtype=torch.float32, device=self.device)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
         hp = self.cfg.to_c(grad_only=not apply)
         z, v_min, v_max, dz = self._z()
         _lib.check(_lib.load().ts_c51_mlp_update(
-            self._ws.handle, _lib.ptr(self.params), _lib.ptr(self.params_old), C.c_int32(int(sync)), _lib.ptr(self.adam_m),
-            _lib.ptr(self.adam_v), _lib.i64(self.adam_step + 1 if apply else max(self.adam_step, 1)), self._d, z, v_min, v_max, dz,
-            _lib.ptr(obs), _lib.ptr(act), _lib.ptr(obs_next), _lib.ptr(returns), _lib.ptr(weight), _lib.i64(b), C.byref(hp),
-            _lib.ptr(loss), _lib.ptr(prio), _lib.ptr(grad_out), _lib.ptr(target_out), _lib.current_stream(self.device)))
-        self.iter += 1
-        if apply:
-            self.adam_step += 1
+            self._ws.handle, _lib.ptr(self.params), _lib.ptr(self.params_old), C.c_int32(int(self._sync_now())), _lib.ptr(self.adam_m),
+            _lib.ptr(self.adam_v), self._adam_arg(apply), self._d, z, v_min, v_max, dz, _lib.ptr(obs), _lib.ptr(act), _lib.ptr(obs_next),
+            _lib.ptr(returns), _lib.ptr(weight), _lib.i64(b), C.byref(hp), _lib.ptr(loss), _lib.ptr(prio), _lib.ptr(grad_out),
+            _lib.ptr(target_out), _lib.current_stream(self.device)))
+        self._stepped(apply)
         return loss, prio

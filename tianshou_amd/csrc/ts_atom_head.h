@@ -7,6 +7,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cstring>
 
 #include "ts_mlp_tile.h"
 
@@ -170,7 +171,47 @@ __device__ void head_dgrad(const QNet& net, const float* __restrict__ p, float* 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 
 inline int64_t tiles_of(int64_t B) { return ts::ceil_div(B, TILE); }
-inline size_t ws_bytes(const QNet& n, int64_t B) { return ((size_t)tiles_of(B) * n.P + (size_t)tiles_of(B) + (size_t)n.P) * 4 + 4096 + 1024; }
+inline size_t ws_bytes(const QNet& n, int64_t B) { return update_scratch(nullptr, tiles_of(B), n.P).bytes; }
+
+// The QNet of a plain Net whose last Linear has n_act * N outputs, from ts_dqn_mlp's 14 desc entries and N in entry 14, with the LDS
+// carve of one tile: obs | hidden activations | n_tables (2 or 3) [32][N | 1] tables in the order ta, tb, [the third one, its offset
+// in *third_table_at] | 4 x 32 per-row scalars.  `noun`: what the N outputs of an action are ("quantiles", "atoms").
+int make_qnet(const int64_t* d, const char* who, const char* noun, int n_tables, QNet* out, int* third_table_at) {
+    TS_REQUIRE(d != nullptr, TS_ERR_INVALID_ARG, "%s: NULL network description", who);
+    QNet n{};
+    const int64_t obs_dim = d[0], n_act = d[1], nt = d[3], n_atoms = d[14];
+    TS_REQUIRE(obs_dim >= 1 && obs_dim <= 256, TS_ERR_UNSUPPORTED, "%s: obs_dim %lld outside [1, 256]", who, (long long)obs_dim);
+    TS_REQUIRE(n_act >= 1 && n_act <= MAX_ACT, TS_ERR_UNSUPPORTED, "%s: %lld actions outside [1, 32]", who, (long long)n_act);
+    TS_REQUIRE(n_atoms >= 2 && n_atoms <= MAX_ATOMS, TS_ERR_UNSUPPORTED, "%s: %lld %s outside [2, 256]", who, (long long)n_atoms, noun);
+    TS_REQUIRE(nt >= 1 && nt <= MAX_TRUNK, TS_ERR_UNSUPPORTED, "%s: %lld trunk hidden layers outside [1, 4]", who, (long long)nt);
+    TS_REQUIRE(d[2] == 0 && d[4] == 0 && d[5] == 0, TS_ERR_UNSUPPORTED, "%s: a dueling head with %s is not supported", who, noun);
+    n.obs_dim = (int)obs_dim; n.n_act = (int)n_act; n.n_atoms = (int)n_atoms; n.nt = (int)nt;
+    int off = 0, at = 0;
+    auto add = [&](Lay* l, int K, int N) { l->K = K; l->N = N; l->off = off; off += (K + 1) * N; };
+    auto carve = [&](int floats) { const int o = at; at += floats; return o; };
+    n.x_at = carve(TILE * (n.obs_dim + 1));
+    int k = n.obs_dim;
+    for (int i = 0; i < n.nt; ++i) {
+        const int64_t w = d[6 + i];
+        TS_REQUIRE(w >= 32 && w <= 256 && w % 32 == 0, TS_ERR_UNSUPPORTED, "%s: hidden width %lld is no multiple of 32 in [32, 256]", who, (long long)w);
+        add(&n.t[i], k, (int)w);
+        n.t_at[i] = carve(TILE * (n.t[i].N + 1));
+        k = n.t[i].N;
+    }
+    add(&n.head, k, n.n_act * n.n_atoms);
+    n.pitch = n.n_atoms | 1;
+    n.ta_at = carve(TILE * n.pitch);
+    n.tb_at = carve(TILE * n.pitch);
+    if (n_tables > 2) *third_table_at = carve(TILE * n.pitch);
+    n.row_at = carve(4 * TILE);
+    n.P = off;
+    n.lds_floats = at;
+    TS_REQUIRE((size_t)at * 4 + 256 <= (size_t)LDS_LIMIT, TS_ERR_UNSUPPORTED,       // ("quantile tables": the noun without its s)
+               "%s: the activations and %.*s tables of one 32-row tile need %zu bytes of LDS, the workgroup limit is %d", who,
+               (int)strlen(noun) - 1, noun, (size_t)at * 4 + 256, LDS_LIMIT);
+    *out = n;
+    return TS_OK;
+}
 
 template <typename Kern>
 int allow_lds(ts::DynLds& slot, Kern kern, const QNet& n) {

@@ -211,43 +211,7 @@ __global__ __launch_bounds__(THREADS) void c51m_kernel(C51Args a) {
 //   test_c51.py     obs 4, [128] x 4, A = 2, N = 51: 160 + 4 x 4,128 + 3 x 1,632 + 128 = 21,696 floats = 86,784 B
 //   LunarLander     obs 8, [128] x 4, A = 4, N = 51: 288 + 4 x 4,128 + 3 x 1,632 + 128 = 21,824 floats = 87,296 B
 //   (refused) [256] x 4, N = 256: 160 + 4 x 8,224 + 3 x 8,224 + 128 = 57,856 floats = 231,424 B > 163,840 B
-int make_net(const int64_t* d, const char* who, CNet* out) {
-    TS_REQUIRE(d != nullptr, TS_ERR_INVALID_ARG, "%s: NULL network description", who);
-    CNet cn{};
-    QNet& n = cn.q;
-    const int64_t obs_dim = d[0], n_act = d[1], nt = d[3], n_atoms = d[14];
-    TS_REQUIRE(obs_dim >= 1 && obs_dim <= 256, TS_ERR_UNSUPPORTED, "%s: obs_dim %lld outside [1, 256]", who, (long long)obs_dim);
-    TS_REQUIRE(n_act >= 1 && n_act <= MAX_ACT, TS_ERR_UNSUPPORTED, "%s: %lld actions outside [1, 32]", who, (long long)n_act);
-    TS_REQUIRE(n_atoms >= 2 && n_atoms <= MAX_ATOMS, TS_ERR_UNSUPPORTED, "%s: %lld atoms outside [2, 256]", who, (long long)n_atoms);
-    TS_REQUIRE(nt >= 1 && nt <= MAX_TRUNK, TS_ERR_UNSUPPORTED, "%s: %lld trunk hidden layers outside [1, 4]", who, (long long)nt);
-    TS_REQUIRE(d[2] == 0 && d[4] == 0 && d[5] == 0, TS_ERR_UNSUPPORTED, "%s: a dueling head with atoms is not supported", who);
-    n.obs_dim = (int)obs_dim; n.n_act = (int)n_act; n.n_atoms = (int)n_atoms; n.nt = (int)nt;
-    int off = 0, at = 0;
-    auto add = [&](Lay* l, int K, int N) { l->K = K; l->N = N; l->off = off; off += (K + 1) * N; };
-    auto carve = [&](int floats) { const int o = at; at += floats; return o; };
-    n.x_at = carve(TILE * (n.obs_dim + 1));
-    int k = n.obs_dim;
-    for (int i = 0; i < n.nt; ++i) {
-        const int64_t w = d[6 + i];
-        TS_REQUIRE(w >= 32 && w <= 256 && w % 32 == 0, TS_ERR_UNSUPPORTED, "%s: hidden width %lld is no multiple of 32 in [32, 256]", who, (long long)w);
-        add(&n.t[i], k, (int)w);
-        n.t_at[i] = carve(TILE * (n.t[i].N + 1));
-        k = n.t[i].N;
-    }
-    add(&n.head, k, n.n_act * n.n_atoms);
-    n.pitch = n.n_atoms | 1;
-    n.ta_at = carve(TILE * n.pitch);
-    n.tb_at = carve(TILE * n.pitch);
-    cn.tc_at = carve(TILE * n.pitch);
-    n.row_at = carve(4 * TILE);
-    n.P = off;
-    n.lds_floats = at;
-    TS_REQUIRE((size_t)at * 4 + 256 <= (size_t)LDS_LIMIT, TS_ERR_UNSUPPORTED,
-               "%s: the activations and atom tables of one 32-row tile need %zu bytes of LDS, the workgroup limit is %d", who,
-               (size_t)at * 4 + 256, LDS_LIMIT);
-    *out = cn;
-    return TS_OK;
-}
+int make_net(const int64_t* d, const char* who, CNet* out) { return make_qnet(d, who, "atoms", 3, &out->q, &out->tc_at); }
 
 template <int MODE>
 int launch(const CNet& cn, const C51Args& a, hipStream_t s) {
@@ -326,35 +290,16 @@ int ts_c51_mlp_update(ts_workspace* ws, float* params, float* params_old, int sy
     if (int rc = ts::ws_reserve(ws, ws_bytes(n, B))) return rc;
     hipStream_t s = ts::as_stream(stream);
     const int tiles = (int)tiles_of(B);
-    float* slabs = static_cast<float*>(ws->base);
-    float* partials = slabs + (size_t)tiles * n.P;
-    float* grad_ws = partials + ((tiles + 63) / 64) * 64;
-    float* norm_part = grad_ws + ((n.P + 63) / 64) * 64;            // 1024 floats behind it (ws_bytes' tail)
+    const UpdateScratch u = update_scratch(ws->base, tiles, n.P);
     C51Args a{};
     a.net = cn; a.params = params;
     // the sync comes before the target (c51.py:147-149): on a sync iteration the lagged network IS the online one, read once
     a.params_old = sync_old || params_old == params ? nullptr : params_old;
     a.support = support; a.v_min = v_min; a.v_max = v_max; a.delta_z = delta_z;
     a.obs = obs; a.obs_next = obs_next; a.returns = returns; a.act = act; a.weight = weight; a.B = B;
-    a.target_out = target_out; a.prio_out = prio_out; a.slabs = slabs; a.partials = partials;
+    a.target_out = target_out; a.prio_out = prio_out; a.slabs = u.slabs; a.partials = u.partials;
     if (int rc = launch<C51_STEP>(cn, a, s)) return rc;
-    const bool step = hp->lr >= 0.0, clip = step && hp->max_grad_norm > 0.0;
-    ApplyArgs aa{};
-    aa.p = params; aa.m = adam_m; aa.v = adam_v; aa.p_old = sync_old ? params_old : nullptr;
-    aa.slabs = slabs; aa.partials = partials; aa.tiles = tiles; aa.P = n.P;
-    aa.grad_out = grad_out ? grad_out : (clip ? grad_ws : nullptr);
-    aa.loss_out = loss_out;
-    aa.adam = step && !clip;               // clip_grad_norm_ needs the whole gradient first: the sum here, then ts_adam_step's kernels
-    float sc[2];
-    ts::adam_step_scalars(adam_step, hp->lr, hp->beta1, hp->beta2, sc);
-    aa.lr_step = sc[0]; aa.bc2_sqrt = sc[1];
-    aa.beta2 = (float)hp->beta2; aa.eps = (float)hp->adam_eps;
-    aa.omb1 = (float)(1.0 - hp->beta1); aa.omb2 = (float)(1.0 - hp->beta2);
-    hipLaunchKernelGGL(dqnm_apply_kernel, dim3((unsigned)ts::ceil_div(n.P, THREADS)), dim3(THREADS), 0, s, aa);
-    TS_LAUNCH_CHECK();
-    if (!clip) return TS_OK;
-    return ts::optim_step(s, ts::OptimDesc{}, params, adam_m, adam_v, aa.grad_out, n.P, adam_step, hp->lr, hp->beta1, hp->beta2,
-                          hp->adam_eps, hp->max_grad_norm, norm_part);
+    return apply_tiles(s, u, tiles, n.P, params, sync_old ? params_old : nullptr, adam_m, adam_v, adam_step, hp, grad_out, loss_out);
 }
 
 }  // extern "C"

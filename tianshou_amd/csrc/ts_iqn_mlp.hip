@@ -201,7 +201,7 @@ int make_net(const int64_t* d, const char* who, INet* out) {
     return TS_OK;
 }
 
-inline size_t iqnm_ws_bytes(const INet& n, int64_t B) { return ((size_t)tiles_of(B) * n.P + (size_t)tiles_of(B) + (size_t)n.P) * 4 + 4096 + 1024; }
+inline size_t iqnm_ws_bytes(const INet& n, int64_t B) { return update_scratch(nullptr, tiles_of(B), n.P).bytes; }
 
 template <typename Kern>
 int allow_lds(ts::DynLds& slot, Kern kern, const INet& n) {
@@ -285,32 +285,13 @@ int ts_iqn_mlp_update(ts_workspace* ws, float* params, float* params_old, int sy
     if (int rc = ts::ws_reserve(ws, iqnm_ws_bytes(n, B))) return rc;
     hipStream_t s = ts::as_stream(stream);
     const int tiles = (int)tiles_of(B);
-    float* slabs = static_cast<float*>(ws->base);
-    float* partials = slabs + (size_t)tiles * n.P;
-    float* grad_ws = partials + ((tiles + 63) / 64) * 64;
-    float* norm_part = grad_ws + ((n.P + 63) / 64) * 64;            // 1024 floats behind it (iqnm_ws_bytes' tail)
+    const UpdateScratch u = update_scratch(ws->base, tiles, n.P);
     static ts::DynLds lds;
     if (int rc = allow_lds(lds, iqnm_step_kernel, n)) return rc;
-    StepArgs sa{n, params, obs, act, tau, (int)N, returns, (int)N2, weight, B, prio_out, slabs, partials};
+    StepArgs sa{n, params, obs, act, tau, (int)N, returns, (int)N2, weight, B, prio_out, u.slabs, u.partials};
     hipLaunchKernelGGL(iqnm_step_kernel, dim3((unsigned)tiles), dim3(THREADS), (size_t)n.lds_floats * 4, s, sa);
     TS_LAUNCH_CHECK();
-    const bool step = hp->lr >= 0.0, clip = step && hp->max_grad_norm > 0.0;
-    ApplyArgs aa{};
-    aa.p = params; aa.m = adam_m; aa.v = adam_v; aa.p_old = sync_old ? params_old : nullptr;
-    aa.slabs = slabs; aa.partials = partials; aa.tiles = tiles; aa.P = n.P;
-    aa.grad_out = grad_out ? grad_out : (clip ? grad_ws : nullptr);
-    aa.loss_out = loss_out;
-    aa.adam = step && !clip;               // clip_grad_norm_ needs the whole gradient first: the sum here, then ts_adam_step's kernels
-    float sc[2];
-    ts::adam_step_scalars(adam_step, hp->lr, hp->beta1, hp->beta2, sc);
-    aa.lr_step = sc[0]; aa.bc2_sqrt = sc[1];
-    aa.beta2 = (float)hp->beta2; aa.eps = (float)hp->adam_eps;
-    aa.omb1 = (float)(1.0 - hp->beta1); aa.omb2 = (float)(1.0 - hp->beta2);
-    hipLaunchKernelGGL(dqnm_apply_kernel, dim3((unsigned)ts::ceil_div(n.P, THREADS)), dim3(THREADS), 0, s, aa);
-    TS_LAUNCH_CHECK();
-    if (!clip) return TS_OK;
-    return ts::optim_step(s, ts::OptimDesc{}, params, adam_m, adam_v, aa.grad_out, n.P, adam_step, hp->lr, hp->beta1, hp->beta2,
-                          hp->adam_eps, hp->max_grad_norm, norm_part);
+    return apply_tiles(s, u, tiles, n.P, params, sync_old ? params_old : nullptr, adam_m, adam_v, adam_step, hp, grad_out, loss_out);
 }
 
 }  // extern "C"

@@ -162,4 +162,51 @@ __global__ __launch_bounds__(THREADS) void dqnm_apply_kernel(ApplyArgs a) {
     a.v[i] = v;
 }
 
+// ---- host: the workspace of an update and its last launch ---------------------------------------------------------------------------
+
+// slabs [tiles][P] | partials [tiles] | grad_ws [P] (the summed gradient on its way to the clip) | norm_part [1024] (optim_step's
+// scratch); every region but the first starts on a 64-float boundary.  `bytes` is the reserved and reported size: the carve and
+// what is left of the padding the size has always had.
+struct UpdateScratch { float *slabs, *partials, *grad_ws, *norm_part; size_t bytes; };
+
+// base == NULL: only `bytes` is filled
+inline UpdateScratch update_scratch(void* base, int64_t tiles, int64_t P) {
+    auto r64 = [](size_t n) { return (n + 63) / 64 * 64; };
+    const size_t partials = (size_t)tiles * (size_t)P, grad_ws = partials + r64((size_t)tiles), norm_part = grad_ws + r64((size_t)P);
+    UpdateScratch u{};
+    u.bytes = ((size_t)tiles * (size_t)P + (size_t)tiles + (size_t)P) * 4 + 4096 + 1024;
+    static_assert(2 * 63 * 4 <= 1024, "the two roundings fit the padding behind norm_part's 4096 bytes");
+    if (base) {
+        u.slabs = static_cast<float*>(base);
+        u.partials = u.slabs + partials;
+        u.grad_ws = u.slabs + grad_ws;
+        u.norm_part = u.slabs + norm_part;
+    }
+    return u;
+}
+
+// The last launch of ts_{dqn,qrdqn,c51,rainbow,iqn}_mlp_update on the slabs and partials the step kernel left in `u`; `hp` is a
+// ts_dqn_hparams or a ts_distq_hparams (lr < 0: gradient only).  params_old != NULL: this call synchronises the lagged network.
+template <typename HP>
+int apply_tiles(hipStream_t s, const UpdateScratch& u, int tiles, int P, float* params, float* params_old, float* m, float* v,
+                int64_t adam_step, const HP* hp, float* grad_out, float* loss_out) {
+    const bool step = hp->lr >= 0.0, clip = step && hp->max_grad_norm > 0.0;
+    ApplyArgs aa{};
+    aa.p = params; aa.m = m; aa.v = v; aa.p_old = params_old;
+    aa.slabs = u.slabs; aa.partials = u.partials; aa.tiles = tiles; aa.P = P;
+    aa.grad_out = grad_out ? grad_out : (clip ? u.grad_ws : nullptr);
+    aa.loss_out = loss_out;
+    aa.adam = step && !clip;               // clip_grad_norm_ needs the whole gradient first: the sum here, then ts_adam_step's kernels
+    float sc[2];
+    ts::adam_step_scalars(adam_step, hp->lr, hp->beta1, hp->beta2, sc);
+    aa.lr_step = sc[0]; aa.bc2_sqrt = sc[1];
+    aa.beta2 = (float)hp->beta2; aa.eps = (float)hp->adam_eps;
+    aa.omb1 = (float)(1.0 - hp->beta1); aa.omb2 = (float)(1.0 - hp->beta2);
+    hipLaunchKernelGGL(dqnm_apply_kernel, dim3((unsigned)ts::ceil_div(P, THREADS)), dim3(THREADS), 0, s, aa);
+    TS_LAUNCH_CHECK();
+    if (!clip) return TS_OK;
+    return ts::optim_step(s, ts::OptimDesc{}, params, m, v, aa.grad_out, P, adam_step, hp->lr, hp->beta1, hp->beta2, hp->adam_eps,
+                          hp->max_grad_norm, u.norm_part);
+}
+
 }  // namespace

@@ -692,31 +692,12 @@ int ts_rainbow_mlp_update(ts_workspace* ws, float* params, const float* noise, f
     if (int rc = ts::ws_reserve(ws, ws_bytes(n, B))) return rc;
     hipStream_t s = ts::as_stream(stream);
     const int tiles = (int)tiles_of(B);
-    float* slabs = static_cast<float*>(ws->base);
-    float* partials = slabs + (size_t)tiles * n.P;
-    float* grad_ws = partials + ((tiles + 63) / 64) * 64;
-    float* norm_part = grad_ws + ((n.P + 63) / 64) * 64;            // 1024 floats behind it (ws_bytes' tail)
+    const UpdateScratch u = update_scratch(ws->base, tiles, n.P);
     a.support = support; a.v_min = v_min; a.v_max = v_max; a.delta_z = delta_z;
     a.obs = obs; a.obs_next = obs_next; a.returns = returns; a.act = act; a.weight = weight; a.B = B;
-    a.target_out = target_out; a.prio_out = prio_out; a.slabs = slabs; a.partials = partials;
+    a.target_out = target_out; a.prio_out = prio_out; a.slabs = u.slabs; a.partials = u.partials;
     if (int rc = launch<RB_STEP>(rn, a, s)) return rc;
-    const bool step = hp->lr >= 0.0, clip = step && hp->max_grad_norm > 0.0;
-    ApplyArgs aa{};
-    aa.p = params; aa.m = adam_m; aa.v = adam_v; aa.p_old = sync_old ? params_old : nullptr;
-    aa.slabs = slabs; aa.partials = partials; aa.tiles = tiles; aa.P = n.P;
-    aa.grad_out = grad_out ? grad_out : (clip ? grad_ws : nullptr);
-    aa.loss_out = loss_out;
-    aa.adam = step && !clip;               // clip_grad_norm_ needs the whole gradient first: the sum here, then ts_adam_step's kernels
-    float sc[2];
-    ts::adam_step_scalars(adam_step, hp->lr, hp->beta1, hp->beta2, sc);
-    aa.lr_step = sc[0]; aa.bc2_sqrt = sc[1];
-    aa.beta2 = (float)hp->beta2; aa.eps = (float)hp->adam_eps;
-    aa.omb1 = (float)(1.0 - hp->beta1); aa.omb2 = (float)(1.0 - hp->beta2);
-    hipLaunchKernelGGL(dqnm_apply_kernel, dim3((unsigned)ts::ceil_div(n.P, THREADS)), dim3(THREADS), 0, s, aa);
-    TS_LAUNCH_CHECK();
-    if (!clip) return TS_OK;
-    return ts::optim_step(s, ts::OptimDesc{}, params, adam_m, adam_v, aa.grad_out, n.P, adam_step, hp->lr, hp->beta1, hp->beta2,
-                          hp->adam_eps, hp->max_grad_norm, norm_part);
+    return apply_tiles(s, u, tiles, n.P, params, sync_old ? params_old : nullptr, adam_m, adam_v, adam_step, hp, grad_out, loss_out);
 }
 
 }  // extern "C"

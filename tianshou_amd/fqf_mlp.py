@@ -24,12 +24,9 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from . import dqn_mlp as M
 from . import iqn_mlp as I
-from .buffer import _i64_dev, gather_rows
+from . import vecq as V
 from .distq import DistQHParams
-from .drqn import gather_stacked_obs_pair
-from .returns import nstep_coefficients, nstep_indices
 
 MAX_LAST, MIN_FRACTIONS, MAX_FRACTIONS = 3, 2, 64
 ENVELOPE = (f"FullQuantileFunction(preprocess_net=Net, hidden_sizes, num_cosines) + FractionProposalNetwork(num_fractions, F) on "
@@ -38,6 +35,7 @@ ENVELOPE = (f"FullQuantileFunction(preprocess_net=Net, hidden_sizes, num_cosines
             f"layers in `last`; every width and the feature width F multiples of 32 in [32, {I.MAX_WIDTH}]; num_cosines 1 .. "
             f"{I.MAX_COS}; 1 .. {I.MAX_ACTIONS} actions; num_fractions {MIN_FRACTIONS} .. {MAX_FRACTIONS}; the fraction network one "
             f"Linear(F, num_fractions) with bias; the activations and fraction tables of a 32-row tile within 160 KB of LDS")
+_F = V.Family("FQF MLP", ENVELOPE)
 
 
 @dataclass
@@ -72,28 +70,10 @@ class FQFConfig:
         return DistQHParams(-1.0 if grad_only else self.lr, self.betas[0], self.betas[1], self.adam_eps, self.max_grad_norm or 0.0, 0.0, 0.0), fhp
 
 
-def _refused(e: NotImplementedError) -> NotImplementedError:
-    """A refusal of iqn_mlp under this module's name and envelope (IQN's says `last` has 0 .. 2 layers)."""
-    reason = str(e).split("; supported:")[0].removeprefix("FQF MLP: ").replace("IQN MLP", "FQF MLP", 1)
-    return NotImplementedError(f"{reason if reason.startswith('FQF MLP') else 'FQF MLP: ' + reason}; supported: {ENVELOPE}")
-
-
 def make_layers(obs_dim, trunk, feat, n_cos, hidden, n_act, num_fractions=32) -> tuple:
-    """iqn_mlp.make_layers with this module's envelope; raises NotImplementedError, naming the reason, outside it."""
-    hidden = tuple(int(w) for w in hidden)
-    if len(hidden) > MAX_LAST:
-        raise NotImplementedError(f"FQF MLP: {len(hidden)} hidden layers in `last` (0 .. {MAX_LAST}); supported: {ENVELOPE}")
-    if not MIN_FRACTIONS <= int(num_fractions) <= MAX_FRACTIONS:
-        raise NotImplementedError(f"FQF MLP: num_fractions = {num_fractions} is outside [{MIN_FRACTIONS}, {MAX_FRACTIONS}]; supported: "
-                                  f"{ENVELOPE}")
-    try:                                           # everything iqn_mlp refuses (its own LDS check on at most two layers of `last`)
-        head = I.make_layers(obs_dim, trunk, feat, n_cos, hidden[:I.MAX_LAST], n_act)
-    except NotImplementedError as e:
-        raise _refused(e) from None
-    bad = [w for w in hidden[I.MAX_LAST:] if w % 32 or not 32 <= w <= I.MAX_WIDTH]
-    if bad:
-        raise NotImplementedError(f"FQF MLP: hidden width {bad[0]} is no multiple of 32 in [32, {I.MAX_WIDTH}]; supported: {ENVELOPE}")
-    layers = head[:4] + (hidden,) + head[5:]
+    """iqn_mlp's model description under this module's envelope; raises NotImplementedError, naming the reason, outside it."""
+    layers = I._check_layers(_F, MAX_LAST, obs_dim, trunk, feat, n_cos, hidden, n_act)
+    _F.in_range("num_fractions", int(num_fractions), MIN_FRACTIONS, MAX_FRACTIONS)
     layout(layers, num_fractions)                  # the LDS carve of a tile is the library's arithmetic
     return layers
 
@@ -106,14 +86,7 @@ def _desc(layers, num_fractions):
 
 def layout(layers, num_fractions, batch: int = 1) -> dict:
     """ts_fqf_mlp_layout -> {count, fraction_count, lds_bytes, workspace_bytes, F}; NotImplementedError when the tile does not fit."""
-    out = (C.c_int64 * 16)()
-    try:
-        _lib.check(_lib.load().ts_fqf_mlp_layout(_desc(layers, num_fractions), _lib.i64(batch), out))
-    except _lib.EngineError as e:
-        if e.code != _lib.TS_ERR_UNSUPPORTED:
-            raise
-        raise NotImplementedError(f"FQF MLP: {e}; supported: {ENVELOPE}") from None
-    return {"count": int(out[0]), "fraction_count": int(out[1]), "lds_bytes": int(out[2]), "workspace_bytes": int(out[3]), "F": int(out[4])}
+    return _F.layout("ts_fqf_mlp_layout", _desc(layers, num_fractions), batch, fraction_count=1, lds_bytes=2, workspace_bytes=3, F=4)
 
 
 state_dict_keys, flat_from_torch, flat_to_torch = I.state_dict_keys, I.flat_from_torch, I.flat_to_torch      # the model's: iqn_mlp's
@@ -142,47 +115,41 @@ def describe_module(model, fraction_model) -> tuple:
     raises NotImplementedError naming what is not supported."""
     net = getattr(fraction_model, "net", None)
     if not isinstance(net, torch.nn.Linear) or net.bias is None or [k for k, _ in fraction_model.named_parameters()] != FRACTION_KEYS:
-        raise NotImplementedError(f"FQF MLP: the fraction network must be one Linear(F, num_fractions) with bias in `net` (found "
-                                  f"{type(net).__name__}); supported: {ENVELOPE}")
+        raise _F.refuse(f"the fraction network must be one Linear(F, num_fractions) with bias in `net` (found {type(net).__name__})")
     n = int(net.out_features)
-    try:
-        layers = I.describe_module(model, make=lambda *a: make_layers(*a, num_fractions=n))
-    except NotImplementedError as e:
-        raise _refused(e) from None
+    layers = I.describe_module(model, make=lambda *a: make_layers(*a, num_fractions=n), fam=_F)
     feat = layout(layers, n)["F"]
     if int(net.in_features) != feat:
-        raise NotImplementedError(f"FQF MLP: the fraction network reads {net.in_features} features, the model has {feat}; supported: "
-                                  f"{ENVELOPE}")
+        raise _F.refuse(f"the fraction network reads {net.in_features} features, the model has {feat}")
     return layers, n
 
 
-class FQFMlpEngine:
+class FQFMlpEngine(V.VecQEngine):
     """State of one FQF learner on one GPU: the model's flat parameters, lagged copy and Adam moments, the fraction network's flat
     parameters and optimizer state (`f_m`, `f_v`: ts_optim_step's mapping), and the counters."""
 
+    FAMILY = _F
+
     def __init__(self, layers, num_fractions: int, flat_params: torch.Tensor, flat_fraction_params: torch.Tensor, cfg: FQFConfig):
-        if not flat_params.is_cuda or not flat_fraction_params.is_cuda:
-            raise RuntimeError("FQFMlpEngine needs parameters on an MI355X (no CPU fallback)")
+        self._require_device(flat_params, flat_fraction_params)
         self.N = int(num_fractions)
-        self.layers = make_layers(*layers, num_fractions=self.N)
-        self.obs_dim, self.n_act, self.cfg = self.layers[0], self.layers[5], cfg
+        layers = make_layers(*layers, num_fractions=self.N)
         cfg.to_c()                                                       # refuses an unknown fraction optimizer
-        self._d = _desc(self.layers, self.N)
-        lay = layout(self.layers, self.N)
-        self.P, self.P2, self.F = lay["count"], lay["fraction_count"], lay["F"]
-        if flat_params.numel() != self.P or flat_fraction_params.numel() != self.P2:
-            raise ValueError(f"expected {self.P} + {self.P2} parameters, got {flat_params.numel()} + {flat_fraction_params.numel()}")
-        self.device = flat_params.device
-        self.params = flat_params.detach().float().contiguous().clone()
-        self.params_old = self.params.clone() if cfg.target_update_freq > 0 else None    # dqn.py:240-246; no lagged fraction network
-        self.adam_m, self.adam_v = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        lay = layout(layers, self.N)
+        self.P2, self.F = lay["fraction_count"], lay["F"]
+        if flat_params.numel() != lay["count"] or flat_fraction_params.numel() != self.P2:
+            raise ValueError(f"expected {lay['count']} + {self.P2} parameters, got {flat_params.numel()} + {flat_fraction_params.numel()}")
+        super().__init__(layers, _desc(layers, self.N), lay["count"], flat_params, cfg)      # (no lagged fraction network)
+        self.n_act = layers[5]
         self.fparams = flat_fraction_params.detach().float().contiguous().clone()
         self.f_m, self.f_v = torch.zeros_like(self.fparams), torch.zeros_like(self.fparams)
-        self.adam_step = self.f_step = self.iter = 0
+        self.f_step = 0
         self.last_taus = self.last_tau_hats = self.last_entropies = self.last_target_taus = self.last_target_tau_hats = None
-        self._ws = _lib.default_workspace(self.device.index or 0)
 
-    _obs = M.DQNMlpEngine._obs
+    def _stepped(self, apply: bool) -> None:
+        super()._stepped(apply)
+        if apply:
+            self.f_step += 1
 
     def _fractions(self, b):
         return (torch.empty((b, self.N + 1), dtype=torch.float32, device=self.device),
@@ -238,18 +205,7 @@ class FQFMlpEngine:
                             pair=None, coef=None):
         """-> (batch.obs float32[I, obs_dim], returns float32[I, N]): as IQNMlpEngine.preprocess_with_obs (both gathers, the n-step coefficients), then target + returns in
         one launch."""
-        if stack_num != 1:
-            raise NotImplementedError("FQF MLP: frame stacking is not supported (stack_num must be 1)")
-        if pair is None:
-            pair = gather_stacked_obs_pair(obs_rows, buffer, indices, self.cfg.n_step, 1, obs_next_rows)
-        if pair is None:
-            idx = _i64_dev(indices, buffer.device).reshape(-1)
-            after = nstep_indices(buffer, idx, self.cfg.n_step)
-            nxt = gather_rows(obs_rows, buffer.next(after)) if obs_next_rows is None else gather_rows(obs_next_rows, after)
-            pair = (gather_rows(obs_rows, idx), nxt)
-        if coef is None:
-            coef = nstep_coefficients(buffer, indices, self.cfg.gamma, self.cfg.n_step)
-        return self._obs(pair[0]), self.target_returns(pair[1], coef)
+        return self._preprocess(buffer, obs_rows, indices, stack_num, obs_next_rows, pair, coef)
 
     # -- the two halves of an update -------------------------------------------------------------------------------------------------
     def gradient(self, obs, act, returns, weight, grad_out: torch.Tensor, fgrad_out: torch.Tensor):
@@ -262,34 +218,24 @@ class FQFMlpEngine:
         """-> (losses float32[3] device tensor = quantile, fraction, entropy; prio float32[B]); prio is the new batch.weight
         (fqf.py:220).  returns float32[B, N].  The lagged network takes the pre-step parameters inside the call (every
         target_update_freq-th call, the first included).  A refused argument leaves the lagged network and the counters alone."""
-        cfg = self.cfg
         obs = self._obs(obs)
         b = obs.shape[0]
-        act = _i64_dev(act, self.device).reshape(-1)
+        act, weight = self._batch_args(b, act, weight, grad_out)
         returns = torch.as_tensor(returns, device=self.device).to(torch.float32).contiguous()
-        if act.numel() != b or tuple(returns.shape) != (b, self.N):
-            raise ValueError(f"act must hold {b} entries and returns must be [{b}, {self.N}]")
-        if weight is not None:
-            weight = torch.as_tensor(weight, device=self.device).to(torch.float32).reshape(-1).contiguous()
-            if weight.numel() != b:
-                raise ValueError("weight length mismatch")
-        for g, n in ((grad_out, self.P), (fgrad_out, self.P2)):
-            if g is not None and (g.numel() != n or g.dtype != torch.float32):
-                raise ValueError("grad_out / fgrad_out must be float32 vectors of the two networks' sizes")
-        sync = self.params_old is not None and self.iter % cfg.target_update_freq == 0    # dqn.py:283-285
+        if tuple(returns.shape) != (b, self.N):
+            raise ValueError(f"returns must be [{b}, {self.N}]")
+        if fgrad_out is not None and (fgrad_out.numel() != self.P2 or fgrad_out.dtype != torch.float32):
+            raise ValueError("fgrad_out must be a float32 vector of the fraction network's size")
         prio = torch.empty(b, dtype=torch.float32, device=self.device)
         losses = torch.empty(3, dtype=torch.float32, device=self.device)
         taus, tau_hats = self._fractions(b)
-        hp, fhp = cfg.to_c(grad_only=not apply)
-        step = lambda n: _lib.i64(n + 1 if apply else max(n, 1))  # noqa: E731
+        hp, fhp = self.cfg.to_c(grad_only=not apply)
         _lib.check(_lib.load().ts_fqf_mlp_update(
-            self._ws.handle, _lib.ptr(self.params), _lib.ptr(self.params_old), C.c_int32(int(sync)), _lib.ptr(self.adam_m),
-            _lib.ptr(self.adam_v), step(self.adam_step), _lib.ptr(self.fparams), _lib.ptr(self.f_m), _lib.ptr(self.f_v), step(self.f_step),
-            self._d, _lib.ptr(obs), _lib.ptr(act), _lib.ptr(returns), _lib.ptr(weight), _lib.i64(b), C.byref(hp), C.byref(fhp), _lib.ptr(losses),
-            _lib.ptr(prio), _lib.ptr(grad_out), _lib.ptr(fgrad_out), _lib.ptr(taus), _lib.ptr(tau_hats), _lib.current_stream(self.device)))
+            self._ws.handle, _lib.ptr(self.params), _lib.ptr(self.params_old), C.c_int32(int(self._sync_now())), _lib.ptr(self.adam_m),
+            _lib.ptr(self.adam_v), self._adam_arg(apply), _lib.ptr(self.fparams), _lib.ptr(self.f_m), _lib.ptr(self.f_v),
+            _lib.i64(self.f_step + 1 if apply else max(self.f_step, 1)), self._d, _lib.ptr(obs), _lib.ptr(act), _lib.ptr(returns),
+            _lib.ptr(weight), _lib.i64(b), C.byref(hp), C.byref(fhp), _lib.ptr(losses), _lib.ptr(prio), _lib.ptr(grad_out), _lib.ptr(fgrad_out),
+            _lib.ptr(taus), _lib.ptr(tau_hats), _lib.current_stream(self.device)))
         self.last_taus, self.last_tau_hats = taus, tau_hats
-        self.iter += 1
-        if apply:
-            self.adam_step += 1
-            self.f_step += 1
+        self._stepped(apply)
         return losses, prio

@@ -1354,6 +1354,49 @@ def _q_write_back(algo) -> None:
         store_adam_state(sec.optim._optim, params, sec.to_torch(eng.f_m), sec.to_torch(eng.f_v), eng.f_step)
 
 
+class _VecQHooks(_HipGlue):
+    """What the six classes on vector observations share (HipDQNMlp, HipQRDQNMlp, HipC51Mlp, HipRainbowMlp, HipIQNMlp, HipFQFMlp;
+    engines: tianshou_amd.vecq).  A class body sets `_VQ`, its engine module, and keeps what is its own: the `describe_module` call
+    and its cross-check against the algorithm, the config and the engine, what it stores from `preprocess_with_obs`, the one engine
+    call of an update and its stats object."""
+    _VQ = None
+
+    def _vq_init(self, device) -> None:
+        """The end of a constructor, once `_hip_layers` is there."""
+        self._hip_device = torch.device(device)
+        _adam_of(self.optim)
+        self._hip_engine = None
+        self._hip_glue_init()
+
+    def _hip_qstate(self):
+        layers, M = self._hip_layers, self._VQ        # what the engine was built with
+        return _QState(M.state_dict_keys(layers), M.flat_from_torch, M.flat_to_torch, lambda eng: layers)
+
+    def _vq_rows(self, who: str, batch, buffer, indices):
+        """`_preprocess_batch` up to the engine call -> (device mirror, indices on the device, its observation rows as vectors, its
+        obs_next rows or None)."""
+        obs = np.asarray(buffer.obs)
+        if obs.ndim < 2 or int(np.prod(obs.shape[1:])) != self._hip_layers[0] or int(getattr(buffer, "stack_num", 1)) != 1:
+            raise NotImplementedError(f"{who}: the buffer must hold vector observations of the model's state_shape, stack_num 1")
+        m, idx = _q_begin(self, who, batch, buffer, indices)
+        nxt = m.obs_next.reshape(m.obs_next.shape[0], -1) if m.obs_next is not None else None
+        return m, idx, m.obs.reshape(m.obs.shape[0], -1), nxt
+
+    def _vq_act_weight(self, batch):
+        """-> (the batch's actions on the device, its importance weights or None).  With index-only sampling the batch carries no
+        host copy of the actions; the mirror's rows are the same values."""
+        weight = batch.pop("weight", None)
+        act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device) if hasattr(batch, "act") else self._hip_mirror.act[self._hip_idx]
+        return act, weight
+
+    def _vq_finish(self, batch, eng, prio) -> None:
+        self._iter = eng.iter
+        batch.weight = prio                                                       # prio-buffer (qrdqn.py:128, c51.py:157, iqn.py:180, fqf.py:220)
+        self._hip_after_update()                                                  # write-back now ("eager") or when read ("lazy")
+
+    _hip_write_back = _q_write_back
+
+
 # -- what the off-policy actor-critic classes (HipSAC, HipREDQ, HipDiscreteSAC, HipTD3 / HipDDPG / HipTD3BC) share: the same two
 # paths over one `_ACPart` per network (`_ac_load`, `_ac_write_back`), the constructor envelope, the config fields, the preamble --
 class _ACPart(NamedTuple):
@@ -1773,18 +1816,13 @@ def make_hip_dqn_mlp(ref=None):
 
     from . import dqn_mlp as M
 
-    class HipDQNMlp(_HipGlue, DQN):
+    class HipDQNMlp(_VecQHooks, DQN):
+        _VQ = M
+
         def __init__(self, *args, device="cuda", **kwargs):
             super().__init__(*args, **kwargs)
-            self._hip_device = torch.device(device)
             self._hip_layers = M.describe_module(self.policy.model)
-            _adam_of(self.optim)
-            self._hip_engine = None
-            self._hip_glue_init()
-
-        def _hip_qstate(self):
-            layers = self._hip_layers             # what the engine was built with
-            return _QState(M.state_dict_keys(layers), M.flat_from_torch, M.flat_to_torch, lambda eng: layers)
+            self._vq_init(device)
 
         def _engine(self):
             if self._hip_engine is None:
@@ -1793,22 +1831,14 @@ def make_hip_dqn_mlp(ref=None):
             return self._hip_engine
 
         def _preprocess_batch(self, batch, buffer, indices):
-            obs = np.asarray(buffer.obs)
-            if obs.ndim < 2 or int(np.prod(obs.shape[1:])) != self._hip_layers[0] or int(getattr(buffer, "stack_num", 1)) != 1:
-                raise NotImplementedError("HipDQNMlp: the buffer must hold vector observations of the model's state_shape, stack_num 1")
-            m, idx = _q_begin(self, "HipDQNMlp", batch, buffer, indices)
-            eng = self._engine()
-            rows = m.obs.reshape(m.obs.shape[0], -1)
-            nxt = m.obs_next.reshape(m.obs_next.shape[0], -1) if m.obs_next is not None else None
-            self._hip_obs, ret = eng.preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt)
+            m, idx, rows, nxt = self._vq_rows("HipDQNMlp", batch, buffer, indices)
+            self._hip_obs, ret = self._engine().preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt)
             batch.returns = ret.reshape(-1, 1)
             return batch
 
         def _update_with_batch(self, batch):
             self._hip_refresh_lr()
             return _dqn_update(self, batch, SimpleLossTrainingStats)
-
-        _hip_write_back = _q_write_back
 
     return HipDQNMlp
 
@@ -1829,21 +1859,16 @@ def make_hip_qrdqn_mlp(ref=None):
     from . import dqn as D
     from . import qrdqn_mlp as M
 
-    class HipQRDQNMlp(_HipGlue, QRDQN):
+    class HipQRDQNMlp(_VecQHooks, QRDQN):
+        _VQ = M
+
         def __init__(self, *args, device="cuda", **kwargs):
             super().__init__(*args, **kwargs)
-            self._hip_device = torch.device(device)
             self._hip_layers = M.describe_module(self.policy.model)
             if self._hip_layers[3] != int(self.num_quantiles):
                 raise NotImplementedError(f"HipQRDQNMlp: the Net has num_atoms = {self._hip_layers[3]}, the algorithm num_quantiles = "
                                           f"{self.num_quantiles}")
-            _adam_of(self.optim)
-            self._hip_engine = None
-            self._hip_glue_init()
-
-        def _hip_qstate(self):
-            layers = self._hip_layers             # what the engine was built with
-            return _QState(M.state_dict_keys(layers), M.flat_from_torch, M.flat_to_torch, lambda eng: layers)
+            self._vq_init(device)
 
         def _engine(self):
             if self._hip_engine is None:
@@ -1853,28 +1878,17 @@ def make_hip_qrdqn_mlp(ref=None):
             return self._hip_engine
 
         def _preprocess_batch(self, batch, buffer, indices):
-            obs = np.asarray(buffer.obs)
-            if obs.ndim < 2 or int(np.prod(obs.shape[1:])) != self._hip_layers[0] or int(getattr(buffer, "stack_num", 1)) != 1:
-                raise NotImplementedError("HipQRDQNMlp: the buffer must hold vector observations of the model's state_shape, stack_num 1")
-            m, idx = _q_begin(self, "HipQRDQNMlp", batch, buffer, indices)
-            eng = self._engine()
-            rows = m.obs.reshape(m.obs.shape[0], -1)
-            nxt = m.obs_next.reshape(m.obs_next.shape[0], -1) if m.obs_next is not None else None
-            self._hip_obs, batch.returns = eng.preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt)
+            m, idx, rows, nxt = self._vq_rows("HipQRDQNMlp", batch, buffer, indices)
+            self._hip_obs, batch.returns = self._engine().preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt)
             return batch
 
         def _update_with_batch(self, batch):
             self._hip_refresh_lr()
-            eng, m = self._hip_engine, self._hip_mirror
-            weight = batch.pop("weight", None)
-            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device) if hasattr(batch, "act") else m.act[self._hip_idx]
+            eng = self._hip_engine
+            act, weight = self._vq_act_weight(batch)
             loss, prio = eng.update_with_batch(self._hip_obs, act, batch.returns, weight)
-            self._iter = eng.iter
-            batch.weight = prio                                                   # prio-buffer, qrdqn.py:128
-            self._hip_after_update()
+            self._vq_finish(batch, eng, prio)
             return SimpleLossTrainingStats(loss=float(loss.item()))
-
-        _hip_write_back = _q_write_back
 
     return HipQRDQNMlp
 
@@ -1895,21 +1909,16 @@ def make_hip_c51_mlp(ref=None):
     from . import c51_mlp as M
     from . import dqn as D
 
-    class HipC51Mlp(_HipGlue, C51):
+    class HipC51Mlp(_VecQHooks, C51):
+        _VQ = M
+
         def __init__(self, *args, device="cuda", **kwargs):
             super().__init__(*args, **kwargs)
-            self._hip_device = torch.device(device)
             self._hip_layers = M.describe_module(self.policy.model)
             if self._hip_layers[3] != int(self.policy.num_atoms):
                 raise NotImplementedError(f"HipC51Mlp: the Net has num_atoms = {self._hip_layers[3]}, the policy num_atoms = "
                                           f"{self.policy.num_atoms}")
-            _adam_of(self.optim)
-            self._hip_engine = None
-            self._hip_glue_init()
-
-        def _hip_qstate(self):
-            layers = self._hip_layers             # what the engine was built with
-            return _QState(M.state_dict_keys(layers), M.flat_from_torch, M.flat_to_torch, lambda eng: layers)
+            self._vq_init(device)
 
         def _engine(self):
             if self._hip_engine is None:
@@ -1920,28 +1929,17 @@ def make_hip_c51_mlp(ref=None):
             return self._hip_engine
 
         def _preprocess_batch(self, batch, buffer, indices):
-            obs = np.asarray(buffer.obs)
-            if obs.ndim < 2 or int(np.prod(obs.shape[1:])) != self._hip_layers[0] or int(getattr(buffer, "stack_num", 1)) != 1:
-                raise NotImplementedError("HipC51Mlp: the buffer must hold vector observations of the model's state_shape, stack_num 1")
-            m, idx = _q_begin(self, "HipC51Mlp", batch, buffer, indices)
-            eng = self._engine()
-            rows = m.obs.reshape(m.obs.shape[0], -1)
-            nxt = m.obs_next.reshape(m.obs_next.shape[0], -1) if m.obs_next is not None else None
-            self._hip_obs, self._hip_obs_next, batch.returns = eng.preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt)
+            m, idx, rows, nxt = self._vq_rows("HipC51Mlp", batch, buffer, indices)
+            self._hip_obs, self._hip_obs_next, batch.returns = self._engine().preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt)
             return batch
 
         def _update_with_batch(self, batch):
             self._hip_refresh_lr()
-            eng, m = self._hip_engine, self._hip_mirror
-            weight = batch.pop("weight", None)
-            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device) if hasattr(batch, "act") else m.act[self._hip_idx]
+            eng = self._hip_engine
+            act, weight = self._vq_act_weight(batch)
             loss, prio = eng.update_with_batch(self._hip_obs, act, self._hip_obs_next, batch.returns, weight)
-            self._iter = eng.iter
-            batch.weight = prio                                                   # prio-buffer, c51.py:157
-            self._hip_after_update()
+            self._vq_finish(batch, eng, prio)
             return LossSequenceTrainingStats(loss=float(loss.item()))            # as c51.py:160
-
-        _hip_write_back = _q_write_back
 
     return HipC51Mlp
 
@@ -2199,26 +2197,21 @@ def make_hip_iqn_mlp(ref=None):
     from . import iqn as I
     from . import iqn_mlp as M
 
-    class HipIQNMlp(_HipGlue, IQN):
+    class HipIQNMlp(_VecQHooks, IQN):
+        _VQ = M
+
         def __init__(self, *args, device="cuda", hip_taus=None, hip_seed=0, **kwargs):
             super().__init__(*args, **kwargs)
-            self._hip_device = torch.device(device)
             self._hip_layers = M.describe_module(self.policy.model)
             for name in ("online_sample_size", "target_sample_size"):
                 if not 2 <= int(getattr(self.policy, name)) <= M.MAX_SAMPLES:
                     raise NotImplementedError(f"HipIQNMlp: policy.{name} = {getattr(self.policy, name)} is outside [2, {M.MAX_SAMPLES}]")
-            _adam_of(self.optim)
             self._hip_taus = hip_taus
             self._hip_seed = int(hip_seed)
             self._hip_tau_counter = 0
-            self._hip_engine = None
-            self._hip_glue_init()
+            self._vq_init(device)
 
         hip_extra_state, load_hip_extra_state, _hip_next_tau = HipIQN.hip_extra_state, HipIQN.load_hip_extra_state, HipIQN._hip_next_tau
-
-        def _hip_qstate(self):
-            layers = self._hip_layers             # what the engine was built with
-            return _QState(M.state_dict_keys(layers), M.flat_from_torch, M.flat_to_torch, lambda eng: layers)
 
         def _engine(self):
             if self._hip_engine is None:
@@ -2233,13 +2226,8 @@ def make_hip_iqn_mlp(ref=None):
             return self._hip_engine
 
         def _preprocess_batch(self, batch, buffer, indices):
-            obs = np.asarray(buffer.obs)
-            if obs.ndim < 2 or int(np.prod(obs.shape[1:])) != self._hip_layers[0] or int(getattr(buffer, "stack_num", 1)) != 1:
-                raise NotImplementedError("HipIQNMlp: the buffer must hold vector observations of the model's state_shape, stack_num 1")
-            m, idx = _q_begin(self, "HipIQNMlp", batch, buffer, indices)
+            m, idx, rows, nxt = self._vq_rows("HipIQNMlp", batch, buffer, indices)
             eng = self._engine()
-            rows = m.obs.reshape(m.obs.shape[0], -1)
-            nxt = m.obs_next.reshape(m.obs_next.shape[0], -1) if m.obs_next is not None else None
             tau_online = self._hip_next_tau()                                    # qrdqn.py:100 / :103
             tau_target = self._hip_next_tau() if eng.params_old is not None else None      # qrdqn.py:101
             self._hip_obs, batch.returns = eng.preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt, tau_online=tau_online,
@@ -2249,17 +2237,12 @@ def make_hip_iqn_mlp(ref=None):
 
         def _update_with_batch(self, batch):
             self._hip_refresh_lr()
-            eng, m = self._hip_engine, self._hip_mirror
-            weight = batch.pop("weight", None)
-            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device) if hasattr(batch, "act") else m.act[self._hip_idx]
+            eng = self._hip_engine
+            act, weight = self._vq_act_weight(batch)
             loss, prio = eng.update_with_batch(self._hip_obs, act, batch.returns, weight, tau=self._hip_next_tau())      # iqn.py:162
-            self._iter = eng.iter
             self._hip_tau_counter = eng.tau_counter
-            batch.weight = prio                                                   # prio-buffer, iqn.py:180
-            self._hip_after_update()
+            self._vq_finish(batch, eng, prio)
             return SimpleLossTrainingStats(loss=float(loss.item()))
-
-        _hip_write_back = _q_write_back
 
     return HipIQNMlp
 
@@ -2287,24 +2270,22 @@ def make_hip_fqf_mlp(ref=None):
                     f_weight_decay=of["weight_decay"], f_rms_alpha=of.get("rms_alpha", 0.99), f_rms_momentum=of.get("rms_momentum", 0.0),
                     f_rms_centered=of.get("rms_centered", False))
 
-    class HipFQFMlp(_HipGlue, FQF):
+    class HipFQFMlp(_VecQHooks, FQF):
+        _VQ = M
         _HIP_LR = (("lr", "optim"), ("f_lr", "fraction_optim"))
 
         def __init__(self, *args, device="cuda", **kwargs):
             super().__init__(*args, **kwargs)
-            self._hip_device = torch.device(device)
             self._hip_layers, self._hip_fractions = M.describe_module(self.policy.model, self.policy.fraction_model)
-            _adam_of(self.optim)
             _fraction_fields(self.fraction_optim._optim)
-            self._hip_engine = None
-            self._hip_glue_init()
+            self._vq_init(device)
 
         def _hip_qstate(self):
             layers, n = self._hip_layers, self._hip_fractions             # what the engine was built with
             feat, dev = M.layout(layers, n)["F"], self._hip_device
             second = _QSecond(self.policy.fraction_model, self.fraction_optim, M.FRACTION_KEYS,
                               lambda t: M.fraction_from_torch(t, feat, n, dev), lambda f: M.fraction_to_torch(f, feat, n))
-            return _QState(M.state_dict_keys(layers), M.flat_from_torch, M.flat_to_torch, lambda eng: layers, second)
+            return super()._hip_qstate()._replace(second=second)
 
         def _engine(self):
             if self._hip_engine is None:
@@ -2315,29 +2296,19 @@ def make_hip_fqf_mlp(ref=None):
             return self._hip_engine
 
         def _preprocess_batch(self, batch, buffer, indices):
-            obs = np.asarray(buffer.obs)
-            if obs.ndim < 2 or int(np.prod(obs.shape[1:])) != self._hip_layers[0] or int(getattr(buffer, "stack_num", 1)) != 1:
-                raise NotImplementedError("HipFQFMlp: the buffer must hold vector observations of the model's state_shape, stack_num 1")
-            m, idx = _q_begin(self, "HipFQFMlp", batch, buffer, indices)
-            rows = m.obs.reshape(m.obs.shape[0], -1)
-            nxt = m.obs_next.reshape(m.obs_next.shape[0], -1) if m.obs_next is not None else None
+            m, idx, rows, nxt = self._vq_rows("HipFQFMlp", batch, buffer, indices)
             self._hip_obs, batch.returns = self._engine().preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt)
             return batch
 
         def _update_with_batch(self, batch):
             self._hip_refresh_lr()
-            eng, m = self._hip_engine, self._hip_mirror
+            eng = self._hip_engine
             eng.cfg.ent_coef = float(self.ent_coef)
-            weight = batch.pop("weight", None)
-            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device) if hasattr(batch, "act") else m.act[self._hip_idx]
+            act, weight = self._vq_act_weight(batch)
             losses, prio = eng.update_with_batch(self._hip_obs, act, batch.returns, weight)
-            self._iter = eng.iter
-            batch.weight = prio                                                   # prio-buffer, fqf.py:220
-            self._hip_after_update()
+            self._vq_finish(batch, eng, prio)
             ql, fl, el = (float(x) for x in losses.tolist())                      # one synchronisation for the three
             return FQFTrainingStats(loss=ql + (fl - eng.cfg.ent_coef * el), quantile_loss=ql, fraction_loss=fl, entropy_loss=el)
-
-        _hip_write_back = _q_write_back
 
     return HipFQFMlp
 
@@ -2719,25 +2690,20 @@ def make_hip_rainbow_mlp(ref=None):
     from . import dqn as D
     from . import rainbow_mlp as M
 
-    class HipRainbowMlp(_HipGlue, RainbowDQN):
+    class HipRainbowMlp(_VecQHooks, RainbowDQN):
+        _VQ = M
+
         def __init__(self, *args, device="cuda", **kwargs):
             super().__init__(*args, **kwargs)
-            self._hip_device = torch.device(device)
             self._hip_layers = M.describe_module(self.policy.model)
             if self._hip_layers[5] != int(self.policy.num_atoms):
                 raise NotImplementedError(f"HipRainbowMlp: the Net has num_atoms = {self._hip_layers[5]}, the policy num_atoms = "
                                           f"{self.policy.num_atoms}")
-            _adam_of(self.optim)
-            self._hip_engine = None
-            self._hip_glue_init()
+            self._vq_init(device)
 
         def _noise_of(self, model):
             sd = model.state_dict()
             return M.noise_from_torch([sd[k] for k in M.noise_keys(self._hip_layers)], *self._hip_layers, self._hip_device)
-
-        def _hip_qstate(self):
-            layers = self._hip_layers             # what the engine was built with
-            return _QState(M.state_dict_keys(layers), M.flat_from_torch, M.flat_to_torch, lambda eng: layers)
 
         def _engine(self):
             if self._hip_engine is None:
@@ -2748,31 +2714,22 @@ def make_hip_rainbow_mlp(ref=None):
             return self._hip_engine
 
         def _preprocess_batch(self, batch, buffer, indices):
-            obs = np.asarray(buffer.obs)
-            if obs.ndim < 2 or int(np.prod(obs.shape[1:])) != self._hip_layers[0] or int(getattr(buffer, "stack_num", 1)) != 1:
-                raise NotImplementedError("HipRainbowMlp: the buffer must hold vector observations of the model's state_shape, stack_num 1")
-            m, idx = _q_begin(self, "HipRainbowMlp", batch, buffer, indices)
-            eng = self._engine()
-            rows = m.obs.reshape(m.obs.shape[0], -1)
-            nxt = m.obs_next.reshape(m.obs_next.shape[0], -1) if m.obs_next is not None else None
-            self._hip_obs, self._hip_obs_next, batch.returns = eng.preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt)
+            m, idx, rows, nxt = self._vq_rows("HipRainbowMlp", batch, buffer, indices)
+            self._hip_obs, self._hip_obs_next, batch.returns = self._engine().preprocess_with_obs(m, rows, idx, 1, obs_next_rows=nxt)
             return batch
 
         def _update_with_batch(self, batch):
             self._hip_refresh_lr()
-            eng, m = self._hip_engine, self._hip_mirror
+            eng = self._hip_engine
             self._sample_noise(self.policy.model)                                 # rainbow.py:97-100
             noise_old = None
             if self.use_target_network:
                 self._sample_noise(self.model_old)
                 noise_old = self._noise_of(self.model_old)
             eng.set_noise(self._noise_of(self.policy.model), noise_old)
-            weight = batch.pop("weight", None)
-            act = torch.as_tensor(np.asarray(batch.act), device=self._hip_device) if hasattr(batch, "act") else m.act[self._hip_idx]
+            act, weight = self._vq_act_weight(batch)
             loss, prio = eng.update_with_batch(self._hip_obs, act, self._hip_obs_next, batch.returns, weight)
-            self._iter = eng.iter
-            batch.weight = prio                                                   # prio-buffer, c51.py:157
-            self._hip_after_update()
+            self._vq_finish(batch, eng, prio)
             return LossSequenceTrainingStats(loss=float(loss.item()))            # as c51.py:160
 
         def _hip_write_back(self) -> None:

@@ -25,13 +25,11 @@ import ctypes as C
 import torch
 
 from . import _lib
-from . import dqn_mlp as M
-from .buffer import DeviceReplayBuffer, _i64_dev, gather_rows
-from .drqn import gather_stacked_obs_pair
+from . import vecq as V
+from .buffer import DeviceReplayBuffer
 from .iqn import IQNConfig, IQNEngine
-from .returns import nstep_coefficients, nstep_indices
 
-MAX_OBS, MAX_TRUNK, MAX_LAST, MAX_WIDTH, MAX_ACTIONS, MAX_COS, MAX_SAMPLES, MAX_BATCH = 256, 4, 2, 256, 32, 64, 64, 4096
+MAX_OBS, MAX_TRUNK, MAX_LAST, MAX_WIDTH, MAX_ACTIONS, MAX_COS, MAX_SAMPLES, MAX_BATCH = 256, 4, 2, 256, 32, 64, 64, V.MAX_BATCH
 ENVELOPE = (f"ImplicitQuantileNetwork(preprocess_net=Net, hidden_sizes, num_cosines) on vector observations of 1 .. {MAX_OBS} entries; "
             f"the Net with 1 .. {MAX_TRUNK} hidden layers, ReLU, no norm_layer, no dueling_param, softmax=False, num_atoms=1, "
             f"concat=False, with or without a Linear output layer; 0 .. {MAX_LAST} hidden layers in `last`; every width and the feature "
@@ -39,26 +37,27 @@ ENVELOPE = (f"ImplicitQuantileNetwork(preprocess_net=Net, hidden_sizes, num_cosi
             f"{MAX_SAMPLES}; the activations and sample tables of a 32-row tile within 160 KB of LDS")
 
 
-def make_layers(obs_dim, trunk, feat, n_cos, hidden, n_act) -> tuple:
-    """The model description every function here takes; raises NotImplementedError, naming the reason, outside the envelope."""
+_F = V.Family("IQN MLP", ENVELOPE)
+
+
+def _check_layers(fam: V.Family, max_last: int, obs_dim, trunk, feat, n_cos, hidden, n_act) -> tuple:
+    """The envelope of a family on this module's network (here and fqf_mlp, whose `last` may be deeper), before the LDS check."""
     obs_dim, trunk, feat, n_cos = int(obs_dim), tuple(int(w) for w in trunk), int(feat or 0), int(n_cos)
     hidden, n_act = tuple(int(w) for w in hidden), int(n_act)
-    if not 1 <= obs_dim <= MAX_OBS:
-        raise NotImplementedError(f"IQN MLP: obs_dim = {obs_dim} is outside [1, {MAX_OBS}]; supported: {ENVELOPE}")
-    if not 1 <= len(trunk) <= MAX_TRUNK:
-        raise NotImplementedError(f"IQN MLP: {len(trunk)} hidden layers in the Net (1 .. {MAX_TRUNK}); supported: {ENVELOPE}")
-    if len(hidden) > MAX_LAST:
-        raise NotImplementedError(f"IQN MLP: {len(hidden)} hidden layers in `last` (0 .. {MAX_LAST}); supported: {ENVELOPE}")
-    bad = [w for w in trunk + hidden if w % 32 or not 32 <= w <= MAX_WIDTH]
-    if bad:
-        raise NotImplementedError(f"IQN MLP: hidden width {bad[0]} is no multiple of 32 in [32, {MAX_WIDTH}]; supported: {ENVELOPE}")
-    if feat and (feat % 32 or not 32 <= feat <= MAX_WIDTH):
-        raise NotImplementedError(f"IQN MLP: feature width {feat} is no multiple of 32 in [32, {MAX_WIDTH}]; supported: {ENVELOPE}")
-    if not 1 <= n_cos <= MAX_COS:
-        raise NotImplementedError(f"IQN MLP: num_cosines = {n_cos} is outside [1, {MAX_COS}]; supported: {ENVELOPE}")
-    if not 1 <= n_act <= MAX_ACTIONS:
-        raise NotImplementedError(f"IQN MLP: {n_act} actions (1 .. {MAX_ACTIONS}); supported: {ENVELOPE}")
-    layers = (obs_dim, trunk, feat, n_cos, hidden, n_act)
+    fam.in_range("obs_dim", obs_dim, 1, MAX_OBS)
+    fam.count(len(trunk), "hidden layers in the Net", 1, MAX_TRUNK)
+    fam.count(len(hidden), "hidden layers in `last`", 0, max_last)
+    fam.widths(trunk + hidden, MAX_WIDTH)
+    if feat:
+        fam.widths((feat,), MAX_WIDTH, "feature width")
+    fam.in_range("num_cosines", n_cos, 1, MAX_COS)
+    fam.count(n_act, "actions", 1, MAX_ACTIONS)
+    return obs_dim, trunk, feat, n_cos, hidden, n_act
+
+
+def make_layers(obs_dim, trunk, feat, n_cos, hidden, n_act) -> tuple:
+    """The model description every function here takes; raises NotImplementedError, naming the reason, outside the envelope."""
+    layers = _check_layers(_F, MAX_LAST, obs_dim, trunk, feat, n_cos, hidden, n_act)
     layout(layers)                                     # the LDS carve of a tile is the library's arithmetic
     return layers
 
@@ -71,14 +70,7 @@ def _desc(layers):
 
 def layout(layers, batch: int = 1) -> dict:
     """ts_iqn_mlp_layout -> {count, lds_bytes, workspace_bytes, F}; NotImplementedError when the tile does not fit the LDS."""
-    out = (C.c_int64 * 16)()
-    try:
-        _lib.check(_lib.load().ts_iqn_mlp_layout(_desc(layers), _lib.i64(batch), out))
-    except _lib.EngineError as e:
-        if e.code != _lib.TS_ERR_UNSUPPORTED:
-            raise
-        raise NotImplementedError(f"IQN MLP: {e}; supported: {ENVELOPE}") from None
-    return {"count": int(out[0]), "lds_bytes": int(out[1]), "workspace_bytes": int(out[2]), "F": int(out[12])}
+    return _F.layout("ts_iqn_mlp_layout", _desc(layers), batch, F=12)
 
 
 def _blocks(layers):
@@ -104,111 +96,60 @@ def state_dict_keys(layers) -> list[str]:
 def flat_from_torch(tensors, *layers_and_device) -> torch.Tensor:
     """[w, b, ...] in `state_dict_keys` order (nn.Linear layout; parameters or their moments) -> the flat vector."""
     *layers, device = layers_and_device
-    flat, order = _blocks(tuple(layers))
-    t = list(tensors)
-    if len(t) != 2 * len(order):
-        raise ValueError(f"IQN MLP: expected {2 * len(order)} tensors, got {len(t)}")
-    given = {p: (t[2 * i], t[2 * i + 1]) for i, p in enumerate(order)}
-    parts = []
-    for prefix, k, n in flat:
-        w, b = given[prefix]
-        if tuple(w.shape) != (n, k) or b.numel() != n:
-            raise ValueError(f"IQN MLP: {prefix} must be Linear({k}, {n}), got weight {tuple(w.shape)} and {b.numel()} biases")
-        parts += [w.detach().float().cpu().t().reshape(-1), b.detach().float().cpu().reshape(-1)]
-    return torch.cat(parts).to(device).contiguous()
+    return _F.flat_from_torch(tensors, *_blocks(tuple(layers)), device)
 
 
 def flat_to_torch(flat: torch.Tensor, *layers) -> list[torch.Tensor]:
     """Inverse of flat_from_torch -> tensors in `state_dict_keys` order (on flat's device)."""
-    blocks, order = _blocks(tuple(layers))
-    f, off, got = flat.detach(), 0, {}
-    for prefix, k, n in blocks:
-        got[prefix] = (f[off:off + k * n].reshape(k, n).t().contiguous(), f[off + k * n:off + (k + 1) * n].clone())
-        off += (k + 1) * n
-    if off != f.numel():
-        raise ValueError(f"IQN MLP: the flat vector has {f.numel()} entries, the layout {off}")
-    return [x for p in order for x in got[p]]
+    return _F.flat_to_torch(flat, *_blocks(tuple(layers)))
 
 
-def _chain(seq, who: str):
-    """Sequential(Linear, ReLU, Linear, ReLU, ...(, Linear)) -> ([hidden Linear], last Linear or None)."""
-    mods = list(seq.children())
-    for j, m in enumerate(mods):
-        if j % 2 == 0 and (not isinstance(m, torch.nn.Linear) or m.bias is None):
-            raise NotImplementedError(f"IQN MLP {who}: Linear layers with bias followed by ReLU only, no norm_layer (found "
-                                      f"{type(m).__name__}); supported: {ENVELOPE}")
-        if j % 2 == 1 and not isinstance(m, torch.nn.ReLU):
-            raise NotImplementedError(f"IQN MLP {who}: the activation must be ReLU, with no norm_layer before it (found "
-                                      f"{type(m).__name__}); supported: {ENVELOPE}")
-    lin = mods[0::2]
-    return (lin[:-1], lin[-1]) if len(mods) % 2 else (lin, None)
-
-
-def describe_module(model, make=None) -> tuple:
+def describe_module(model, make=None, fam: V.Family = _F) -> tuple:
     """-> `layers` of an ImplicitQuantileNetwork-shaped module (`preprocess` = a Net, `last`, `embed_model`; discrete.py:163-198),
-    or raises NotImplementedError naming what is not supported.  `make`: the envelope check of a sibling with the same module
-    shape (tianshou_amd.fqf_mlp), in place of `make_layers`."""
+    or raises NotImplementedError naming what is not supported.  `make`, `fam`: the envelope check and the Family of a sibling with
+    the same module shape (tianshou_amd.fqf_mlp), in place of `make_layers` and this module's."""
     for name in ("preprocess", "last", "embed_model"):
         if not hasattr(model, name):
-            raise NotImplementedError(f"IQN MLP: an ImplicitQuantileNetwork is needed (found {type(model).__name__} without `{name}`); "
-                                      f"supported: {ENVELOPE}")
+            raise fam.refuse(f"an ImplicitQuantileNetwork is needed (found {type(model).__name__} without `{name}`)")
     net = model.preprocess
-    for name in ("model", "use_dueling", "softmax", "num_atoms"):
-        if not hasattr(net, name):
-            raise NotImplementedError(f"IQN MLP: the preprocess_net must be a Net (found {type(net).__name__} without `{name}`; the "
-                                      f"Atari trunk is tianshou_amd.iqn's); supported: {ENVELOPE}")
+    fam.require_net(net, need="the preprocess_net must be a Net", hint="; the Atari trunk is tianshou_amd.iqn's")
     if net.softmax:
-        raise NotImplementedError(f"IQN MLP: softmax=True is not supported; supported: {ENVELOPE}")
+        raise fam.refuse("softmax=True is not supported")
     if net.use_dueling:
-        raise NotImplementedError(f"IQN MLP: dueling_param is not supported; supported: {ENVELOPE}")
+        raise fam.refuse("dueling_param is not supported")
     if int(net.num_atoms) != 1:
-        raise NotImplementedError(f"IQN MLP: num_atoms = {net.num_atoms} is not supported; supported: {ENVELOPE}")
-    trunk, out = _chain(net.model.model, "preprocess_net")
+        raise fam.refuse(f"num_atoms = {net.num_atoms} is not supported")
+    trunk, out = fam.chain(net.model.model, "preprocess_net")
     if not trunk:
-        raise NotImplementedError(f"IQN MLP: the Net needs at least one hidden layer; supported: {ENVELOPE}")
-    hidden, head = _chain(model.last.model, "last")
+        raise fam.refuse("the Net needs at least one hidden layer")
+    hidden, head = fam.chain(model.last.model, "last")
     if head is None:
-        raise NotImplementedError(f"IQN MLP: `last` must end in a Linear onto the actions; supported: {ENVELOPE}")
+        raise fam.refuse("`last` must end in a Linear onto the actions")
     emb = list(model.embed_model.net.children())
     if len(emb) != 2 or not isinstance(emb[0], torch.nn.Linear) or not isinstance(emb[1], torch.nn.ReLU):
-        raise NotImplementedError(f"IQN MLP: embed_model.net must be Sequential(Linear, ReLU); supported: {ENVELOPE}")
+        raise fam.refuse("embed_model.net must be Sequential(Linear, ReLU)")
     layers = (make or make_layers)(trunk[0].in_features, [l.out_features for l in trunk], out.out_features if out is not None else 0,
                                    emb[0].in_features, [l.out_features for l in hidden], head.out_features)
-    have = [k for k, _ in model.named_parameters()]
-    if have != state_dict_keys(layers):
-        raise NotImplementedError(f"IQN MLP: the model's parameters {have} are not those of an ImplicitQuantileNetwork on a Net, "
-                                  f"{state_dict_keys(layers)} (concat=True is not supported); supported: {ENVELOPE}")
+    fam.same_parameters(model, state_dict_keys(layers), "those of an ImplicitQuantileNetwork on a Net (concat=True is not supported),")
     return layers
 
 
-class IQNMlpEngine:
+class IQNMlpEngine(V.VecQEngine):
     """State of one IQN learner on one GPU: flat parameters, lagged copy, Adam moments, counters (the fraction counter included).
     `cfg` is tianshou_amd.iqn's IQNConfig (`n_cos` is not read: the layers carry it)."""
 
+    FAMILY = _F
+
     def __init__(self, layers, flat_params: torch.Tensor, cfg: IQNConfig):
-        if not flat_params.is_cuda:
-            raise RuntimeError("IQNMlpEngine needs parameters on an MI355X (no CPU fallback)")
+        self._require_device(flat_params)
         for name in ("sample_size", "online_sample_size", "target_sample_size"):
-            if not 2 <= getattr(cfg, name) <= MAX_SAMPLES:
-                raise NotImplementedError(f"IQN MLP: {name} = {getattr(cfg, name)} is outside [2, {MAX_SAMPLES}]; supported: {ENVELOPE}")
-        self.layers = make_layers(*layers)
-        self.obs_dim, self.n_act, self.cfg = self.layers[0], self.layers[5], cfg
-        self._d = _desc(self.layers)
-        self.P = layout(self.layers)["count"]
-        if flat_params.numel() != self.P:
-            raise ValueError(f"expected {self.P} parameters, got {flat_params.numel()}")
-        self.device = flat_params.device
-        self.params = flat_params.detach().float().contiguous().clone()
-        self.params_old = self.params.clone() if cfg.target_update_freq > 0 else None    # dqn.py:240-246
-        self.adam_m, self.adam_v = torch.zeros_like(self.params), torch.zeros_like(self.params)
-        self.adam_step = 0
-        self.iter = 0
+            _F.in_range(name, getattr(cfg, name), 2, MAX_SAMPLES)
+        layers = make_layers(*layers)
+        super().__init__(layers, _desc(layers), layout(layers)["count"], flat_params, cfg)
+        self.n_act = layers[5]
         self.tau_counter = 0
         self.last_tau = self.last_tau_online = self.last_tau_target = None
-        self._ws = _lib.default_workspace(self.device.index or 0)
 
-    _obs = M.DQNMlpEngine._obs
-    apply_gradient = M.DQNMlpEngine.apply_gradient
     draw, _tau, extra_state, load_extra_state = IQNEngine.draw, IQNEngine._tau, IQNEngine.extra_state, IQNEngine.load_extra_state
 
     # -- ImplicitQuantileNetwork.forward + IQNPolicy.forward ------------------------------------------------------------------------
@@ -257,18 +198,7 @@ class IQNMlpEngine:
                             tau_online=None, tau_target=None):
         """-> (batch.obs float32[I, obs_dim], returns float32[I, N']): as DQNMlpEngine.preprocess_with_obs (both observation gathers
         from one launch, the n-step coefficients, then target + returns in one launch)."""
-        if stack_num != 1:
-            raise NotImplementedError("IQN MLP: frame stacking is not supported (stack_num must be 1)")
-        if pair is None:
-            pair = gather_stacked_obs_pair(obs_rows, buffer, indices, self.cfg.n_step, 1, obs_next_rows)
-        if pair is None:
-            idx = _i64_dev(indices, buffer.device).reshape(-1)
-            after = nstep_indices(buffer, idx, self.cfg.n_step)
-            nxt = gather_rows(obs_rows, buffer.next(after)) if obs_next_rows is None else gather_rows(obs_next_rows, after)
-            pair = (gather_rows(obs_rows, idx), nxt)
-        if coef is None:
-            coef = nstep_coefficients(buffer, indices, self.cfg.gamma, self.cfg.n_step)
-        return self._obs(pair[0]), self.target_returns(pair[1], coef, tau_online, tau_target)
+        return self._preprocess(buffer, obs_rows, indices, stack_num, obs_next_rows, pair, coef, tau_online, tau_target)
 
     # -- the two halves of an update -------------------------------------------------------------------------------------------------
     def gradient(self, obs, act, returns, weight, grad_out: torch.Tensor, tau=None):
@@ -281,31 +211,21 @@ class IQNMlpEngine:
         tau float32[B, N] (None: drawn, N = cfg.online_sample_size).  The lagged network takes the pre-step parameters inside the
         call (every target_update_freq-th call, the first included).  A refused argument leaves the lagged network and the
         counters alone."""
-        cfg = self.cfg
         obs = self._obs(obs)
         b = obs.shape[0]
-        act = _i64_dev(act, self.device).reshape(-1)
+        act, weight = self._batch_args(b, act, weight, grad_out)
         returns = torch.as_tensor(returns, device=self.device).to(torch.float32).contiguous()
-        if act.numel() != b or returns.dim() != 2 or returns.shape[0] != b or not 2 <= returns.shape[1] <= MAX_SAMPLES:
-            raise ValueError(f"act must hold {b} entries and returns must be [{b}, N'], 2 <= N' <= {MAX_SAMPLES}")
-        if weight is not None:
-            weight = torch.as_tensor(weight, device=self.device).to(torch.float32).reshape(-1).contiguous()
-            if weight.numel() != b:
-                raise ValueError("weight length mismatch")
-        if grad_out is not None and (grad_out.numel() != self.P or grad_out.dtype != torch.float32):
-            raise ValueError("grad_out must be a float32 vector of the model's size")
-        tau = self._tau(tau, b, None if tau is not None else cfg.online_sample_size)
-        sync = self.params_old is not None and self.iter % cfg.target_update_freq == 0    # dqn.py:283-285
+        if returns.dim() != 2 or returns.shape[0] != b or not 2 <= returns.shape[1] <= MAX_SAMPLES:
+            raise ValueError(f"returns must be [{b}, N'], 2 <= N' <= {MAX_SAMPLES}")
+        tau = self._tau(tau, b, None if tau is not None else self.cfg.online_sample_size)
         prio = torch.empty(b, dtype=torch.float32, device=self.device)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        hp = cfg.to_c(grad_only=not apply)
+        hp = self.cfg.to_c(grad_only=not apply)
         _lib.check(_lib.load().ts_iqn_mlp_update(
-            self._ws.handle, _lib.ptr(self.params), _lib.ptr(self.params_old), C.c_int32(int(sync)), _lib.ptr(self.adam_m),
-            _lib.ptr(self.adam_v), _lib.i64(self.adam_step + 1 if apply else max(self.adam_step, 1)), self._d, _lib.ptr(obs), _lib.ptr(act),
-            _lib.ptr(tau), _lib.i64(tau.shape[1]), _lib.ptr(returns), _lib.i64(returns.shape[1]), _lib.ptr(weight), _lib.i64(b),
-            C.byref(hp), _lib.ptr(loss), _lib.ptr(prio), _lib.ptr(grad_out), _lib.current_stream(self.device)))
+            self._ws.handle, _lib.ptr(self.params), _lib.ptr(self.params_old), C.c_int32(int(self._sync_now())), _lib.ptr(self.adam_m),
+            _lib.ptr(self.adam_v), self._adam_arg(apply), self._d, _lib.ptr(obs), _lib.ptr(act), _lib.ptr(tau), _lib.i64(tau.shape[1]),
+            _lib.ptr(returns), _lib.i64(returns.shape[1]), _lib.ptr(weight), _lib.i64(b), C.byref(hp), _lib.ptr(loss), _lib.ptr(prio),
+            _lib.ptr(grad_out), _lib.current_stream(self.device)))
         self.last_tau = tau
-        self.iter += 1
-        if apply:
-            self.adam_step += 1
+        self._stepped(apply)
         return loss, prio

@@ -10,7 +10,7 @@ CPU path: every function calls libtsengine.so.
 
 `layers` = (obs_dim, trunk widths, n_act, n_atoms) describes the model everywhere.  Flat layout (ts_qrdqn_mlp_layout): per layer
 [K + 1, width], row K the bias; the hidden layers, then the head [top + 1, n_act * n_atoms] -- dqn_mlp's layout of the plain Net
-whose last Linear has n_act * n_atoms outputs, so its converters serve here.
+whose last Linear has n_act * n_atoms outputs (`_plain`), so its blocks and converters serve here.
 """
 from __future__ import annotations
 
@@ -20,34 +20,33 @@ import torch
 
 from . import _lib
 from . import dqn_mlp as M
-from .buffer import DeviceReplayBuffer, _i64_dev, gather_rows
+from . import vecq as V
+from .buffer import DeviceReplayBuffer
 from .dqn import DQNConfig
-from .drqn import gather_stacked_obs_pair
-from .returns import nstep_coefficients, nstep_indices
 
-MAX_OBS, MAX_TRUNK, MAX_WIDTH, MAX_ACTIONS, MAX_ATOMS, MAX_BATCH = 256, 4, 256, 32, 256, 4096
+MAX_OBS, MAX_TRUNK, MAX_WIDTH, MAX_ACTIONS, MAX_ATOMS, MAX_BATCH = 256, 4, 256, 32, 256, V.MAX_BATCH
 ENVELOPE = (f"Net on vector observations of 1 .. {MAX_OBS} entries, 1 .. {MAX_TRUNK} hidden layers, widths multiples of 32 in "
             f"[32, {MAX_WIDTH}], ReLU, no norm_layer, no dueling_param, softmax=False, concat=False, 1 .. {MAX_ACTIONS} actions, "
             f"num_atoms 2 .. {MAX_ATOMS}, the activations and quantile tables of a 32-row tile within 160 KB of LDS")
+_F = V.Family("QRDQN MLP", ENVELOPE)
+
+
+def _make_layers(fam: V.Family, layout_of, obs_dim, trunk, n_act, n_atoms) -> tuple:
+    """`make_layers` of a family on the plain Net with n_atoms outputs per action (here and c51_mlp)."""
+    obs_dim, trunk, n_act, n_atoms = int(obs_dim), tuple(int(w) for w in trunk), int(n_act), int(n_atoms)
+    fam.in_range("obs_dim", obs_dim, 1, MAX_OBS)
+    fam.count(len(trunk), "hidden layers", 1, MAX_TRUNK)
+    fam.widths(trunk, MAX_WIDTH)
+    fam.count(n_act, "actions", 1, MAX_ACTIONS)
+    fam.in_range("num_atoms", n_atoms, 2, MAX_ATOMS)
+    layers = (obs_dim, trunk, n_act, n_atoms)
+    layout_of(layers)                                  # the LDS carve of a tile is the library's arithmetic
+    return layers
 
 
 def make_layers(obs_dim, trunk, n_act, n_atoms) -> tuple:
     """The model description every function here takes; raises NotImplementedError, naming the reason, outside the envelope."""
-    obs_dim, trunk, n_act, n_atoms = int(obs_dim), tuple(int(w) for w in trunk), int(n_act), int(n_atoms)
-    if not 1 <= obs_dim <= MAX_OBS:
-        raise NotImplementedError(f"QRDQN MLP: obs_dim = {obs_dim} is outside [1, {MAX_OBS}]; supported: {ENVELOPE}")
-    if not 1 <= len(trunk) <= MAX_TRUNK:
-        raise NotImplementedError(f"QRDQN MLP: {len(trunk)} hidden layers (1 .. {MAX_TRUNK}); supported: {ENVELOPE}")
-    bad = [w for w in trunk if w % 32 or not 32 <= w <= MAX_WIDTH]
-    if bad:
-        raise NotImplementedError(f"QRDQN MLP: hidden width {bad[0]} is no multiple of 32 in [32, {MAX_WIDTH}]; supported: {ENVELOPE}")
-    if not 1 <= n_act <= MAX_ACTIONS:
-        raise NotImplementedError(f"QRDQN MLP: {n_act} actions (1 .. {MAX_ACTIONS}); supported: {ENVELOPE}")
-    if not 2 <= n_atoms <= MAX_ATOMS:
-        raise NotImplementedError(f"QRDQN MLP: num_atoms = {n_atoms} is outside [2, {MAX_ATOMS}]; supported: {ENVELOPE}")
-    layers = (obs_dim, trunk, n_act, n_atoms)
-    layout(layers)                                     # the LDS carve of a tile is the library's arithmetic
-    return layers
+    return _make_layers(_F, layout, obs_dim, trunk, n_act, n_atoms)
 
 
 def _desc(layers):
@@ -63,14 +62,7 @@ def _plain(layers) -> tuple:
 
 def layout(layers, batch: int = 1) -> dict:
     """ts_qrdqn_mlp_layout -> {count, lds_bytes, workspace_bytes}; NotImplementedError when the tile does not fit the LDS."""
-    out = (C.c_int64 * 16)()
-    try:
-        _lib.check(_lib.load().ts_qrdqn_mlp_layout(_desc(layers), _lib.i64(batch), out))
-    except _lib.EngineError as e:
-        if e.code != _lib.TS_ERR_UNSUPPORTED:
-            raise
-        raise NotImplementedError(f"QRDQN MLP: {e}; supported: {ENVELOPE}") from None
-    return {"count": int(out[0]), "lds_bytes": int(out[1]), "workspace_bytes": int(out[2])}
+    return _F.layout("ts_qrdqn_mlp_layout", _desc(layers), batch)
 
 
 def state_dict_keys(layers) -> list[str]:
@@ -94,66 +86,45 @@ def tau_hat(n_atoms: int, device) -> torch.Tensor:
     return ((tau[:-1] + tau[1:]) / 2).to(device).contiguous()
 
 
-def describe_module(net) -> tuple:
-    """-> `layers` of a Net-shaped module (`model`, `use_dueling`, `softmax`, `num_atoms`; common.py:286-341), or raises
-    NotImplementedError naming what is not supported."""
-    for name in ("model", "use_dueling", "softmax", "num_atoms"):
-        if not hasattr(net, name):
-            raise NotImplementedError(f"QRDQN MLP: a Net is needed (found {type(net).__name__} without `{name}`); supported: {ENVELOPE}")
-    if net.softmax:
-        raise NotImplementedError(f"QRDQN MLP: softmax=True is not supported; supported: {ENVELOPE}")
-    if net.use_dueling:
-        raise NotImplementedError(f"QRDQN MLP: dueling_param with quantiles is not supported; supported: {ENVELOPE}")
-    n_atoms = int(net.num_atoms)
-    if not 2 <= n_atoms <= MAX_ATOMS:
-        raise NotImplementedError(f"QRDQN MLP: num_atoms = {n_atoms} is outside [2, {MAX_ATOMS}]"
-                                  + (" (DQN on a Net is dqn_mlp's)" if n_atoms == 1 else "") + f"; supported: {ENVELOPE}")
-    mods = list(net.model.model.children())
-    for j, m in enumerate(mods):
-        if j % 2 == 0 and (not isinstance(m, torch.nn.Linear) or m.bias is None):
-            raise NotImplementedError(f"QRDQN MLP: Linear layers with bias followed by ReLU only, no norm_layer (found {type(m).__name__}); "
-                                      f"supported: {ENVELOPE}")
-        if j % 2 == 1 and not isinstance(m, torch.nn.ReLU):
-            raise NotImplementedError(f"QRDQN MLP: the activation must be ReLU (found {type(m).__name__}); supported: {ENVELOPE}")
-    if len(mods) % 2 == 0 or len(mods) < 3:
-        raise NotImplementedError(f"QRDQN MLP: at least one hidden layer and a last Linear onto the outputs are needed (concat=True is "
-                                  f"not supported); supported: {ENVELOPE}")
-    lin = mods[0::2]
-    if lin[-1].out_features % n_atoms:
-        raise NotImplementedError(f"QRDQN MLP: {lin[-1].out_features} outputs are no multiple of num_atoms = {n_atoms}; supported: {ENVELOPE}")
-    layers = make_layers(lin[0].in_features, [l.out_features for l in lin[:-1]], lin[-1].out_features // n_atoms, n_atoms)
-    have = [k for k, _ in net.named_parameters()]
-    if have != state_dict_keys(layers):
-        raise NotImplementedError(f"QRDQN MLP: the model's parameters {have} are not a Net's {state_dict_keys(layers)}; supported: {ENVELOPE}")
+def _describe_plain(fam: V.Family, make, net, n_atoms: int) -> tuple:
+    """The walk of `describe_module` over a plain Net with n_atoms outputs per action, once the family's own checks of
+    `softmax`, `use_dueling` and `num_atoms` are through (here and c51_mlp)."""
+    hidden, last = fam.chain(net.model.model)
+    if last is None or not hidden:
+        raise fam.refuse("at least one hidden layer and a last Linear onto the outputs are needed (concat=True is not supported)")
+    if last.out_features % n_atoms:
+        raise fam.refuse(f"{last.out_features} outputs are no multiple of num_atoms = {n_atoms}")
+    layers = make(hidden[0].in_features, [l.out_features for l in hidden], last.out_features // n_atoms, n_atoms)
+    fam.same_parameters(net, state_dict_keys(layers), "a Net's")
     return layers
 
 
-class QRDQNMlpEngine:
+def describe_module(net) -> tuple:
+    """-> `layers` of a Net-shaped module (`model`, `use_dueling`, `softmax`, `num_atoms`; common.py:286-341), or raises
+    NotImplementedError naming what is not supported."""
+    _F.require_net(net)
+    if net.softmax:
+        raise _F.refuse("softmax=True is not supported")
+    if net.use_dueling:
+        raise _F.refuse("dueling_param with quantiles is not supported")
+    n_atoms = int(net.num_atoms)
+    _F.in_range("num_atoms", n_atoms, 2, MAX_ATOMS, " (DQN on a Net is dqn_mlp's)" if n_atoms == 1 else "")
+    return _describe_plain(_F, make_layers, net, n_atoms)
+
+
+class QRDQNMlpEngine(V.VecQEngine):
     """State of one QRDQN learner on one GPU: flat parameters, lagged copy, Adam moments, counters.  `cfg` is a DQNConfig
     (`is_double`: the online network selects the action read from the lagged one, as the reference always does; `huber_delta` is
     not read: the quantile Huber loss has kappa = 1)."""
 
-    def __init__(self, layers, flat_params: torch.Tensor, cfg: DQNConfig):
-        if not flat_params.is_cuda:
-            raise RuntimeError("QRDQNMlpEngine needs parameters on an MI355X (no CPU fallback)")
-        self.layers = make_layers(*layers)
-        self.obs_dim, _, self.n_act, self.n_atoms = self.layers
-        self.cfg = cfg
-        self._d = _desc(self.layers)
-        self.P = layout(self.layers)["count"]
-        if flat_params.numel() != self.P:
-            raise ValueError(f"expected {self.P} parameters, got {flat_params.numel()}")
-        self.device = flat_params.device
-        self.params = flat_params.detach().float().contiguous().clone()
-        self.params_old = self.params.clone() if cfg.target_update_freq > 0 else None    # dqn.py:240-246
-        self.adam_m, self.adam_v = torch.zeros_like(self.params), torch.zeros_like(self.params)
-        self.adam_step = 0
-        self.iter = 0
-        self.tau_hat = tau_hat(self.n_atoms, self.device)
-        self._ws = _lib.default_workspace(self.device.index or 0)
+    FAMILY = _F
 
-    _obs = M.DQNMlpEngine._obs
-    apply_gradient = M.DQNMlpEngine.apply_gradient
+    def __init__(self, layers, flat_params: torch.Tensor, cfg: DQNConfig):
+        self._require_device(flat_params)
+        layers = make_layers(*layers)
+        super().__init__(layers, _desc(layers), layout(layers)["count"], flat_params, cfg)
+        _, _, self.n_act, self.n_atoms = layers
+        self.tau_hat = tau_hat(self.n_atoms, self.device)
 
     # -- Net.forward + QRDQNPolicy.compute_q_value + the greedy action ----------------------------------------------------------
     def forward(self, obs, params: torch.Tensor | None = None):
@@ -188,18 +159,7 @@ class QRDQNMlpEngine:
                             obs_next_rows: torch.Tensor | None = None, prefetch: bool = False, pair=None, coef=None):
         """-> (batch.obs float32[I, obs_dim], returns float32[I, N]): as DQNMlpEngine.preprocess_with_obs (both observation gathers
         from one launch, the n-step coefficients, then target + returns in one launch)."""
-        if stack_num != 1:
-            raise NotImplementedError("QRDQN MLP: frame stacking is not supported (stack_num must be 1)")
-        if pair is None:
-            pair = gather_stacked_obs_pair(obs_rows, buffer, indices, self.cfg.n_step, 1, obs_next_rows)
-        if pair is None:
-            idx = _i64_dev(indices, buffer.device).reshape(-1)
-            after = nstep_indices(buffer, idx, self.cfg.n_step)
-            nxt = gather_rows(obs_rows, buffer.next(after)) if obs_next_rows is None else gather_rows(obs_next_rows, after)
-            pair = (gather_rows(obs_rows, idx), nxt)
-        if coef is None:
-            coef = nstep_coefficients(buffer, indices, self.cfg.gamma, self.cfg.n_step)
-        return self._obs(pair[0]), self.target_returns(pair[1], coef)
+        return self._preprocess(buffer, obs_rows, indices, stack_num, obs_next_rows, pair, coef)
 
     # -- the two halves of an update ---------------------------------------------------------------------------------------------
     def gradient(self, obs, act, returns, weight, grad_out: torch.Tensor):
@@ -211,29 +171,19 @@ class QRDQNMlpEngine:
         """-> (loss float32[1] device tensor, prio float32[B]); prio is the new batch.weight (qrdqn.py:128).  The lagged network
         takes the pre-step parameters inside the call (every target_update_freq-th call, the first included).  A refused argument
         leaves the lagged network and both counters alone."""
-        cfg = self.cfg
         obs = self._obs(obs)
         b = obs.shape[0]
-        act = _i64_dev(act, self.device).reshape(-1)
+        act, weight = self._batch_args(b, act, weight, grad_out)
         returns = torch.as_tensor(returns, device=self.device).to(torch.float32).contiguous()
-        if act.numel() != b or tuple(returns.shape) != (b, self.n_atoms):
-            raise ValueError(f"act must hold {b} entries and returns must be [{b}, {self.n_atoms}]")
-        if weight is not None:
-            weight = torch.as_tensor(weight, device=self.device).to(torch.float32).reshape(-1).contiguous()
-            if weight.numel() != b:
-                raise ValueError("weight length mismatch")
-        if grad_out is not None and (grad_out.numel() != self.P or grad_out.dtype != torch.float32):
-            raise ValueError("grad_out must be a float32 vector of the model's size")
-        sync = self.params_old is not None and self.iter % cfg.target_update_freq == 0    # dqn.py:283-285
+        if tuple(returns.shape) != (b, self.n_atoms):
+            raise ValueError(f"returns must be [{b}, {self.n_atoms}]")
         prio = torch.empty(b, dtype=torch.float32, device=self.device)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        hp = cfg.to_c(grad_only=not apply)
+        hp = self.cfg.to_c(grad_only=not apply)
         _lib.check(_lib.load().ts_qrdqn_mlp_update(
-            self._ws.handle, _lib.ptr(self.params), _lib.ptr(self.params_old), C.c_int32(int(sync)), _lib.ptr(self.adam_m),
-            _lib.ptr(self.adam_v), _lib.i64(self.adam_step + 1 if apply else max(self.adam_step, 1)), self._d, _lib.ptr(obs), _lib.ptr(act),
-            _lib.ptr(returns), _lib.ptr(weight), _lib.ptr(self.tau_hat), _lib.i64(b), C.byref(hp), _lib.ptr(loss), _lib.ptr(prio),
-            _lib.ptr(grad_out), _lib.current_stream(self.device)))
-        self.iter += 1
-        if apply:
-            self.adam_step += 1
+            self._ws.handle, _lib.ptr(self.params), _lib.ptr(self.params_old), C.c_int32(int(self._sync_now())), _lib.ptr(self.adam_m),
+            _lib.ptr(self.adam_v), self._adam_arg(apply), self._d, _lib.ptr(obs), _lib.ptr(act), _lib.ptr(returns), _lib.ptr(weight),
+            _lib.ptr(self.tau_hat), _lib.i64(b), C.byref(hp), _lib.ptr(loss), _lib.ptr(prio), _lib.ptr(grad_out),
+            _lib.current_stream(self.device)))
+        self._stepped(apply)
         return loss, prio

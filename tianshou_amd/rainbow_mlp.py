@@ -22,7 +22,7 @@ import torch
 from . import _lib
 from . import c51_mlp as C5
 from . import qrdqn_mlp as Q
-from .buffer import _i64_dev
+from . import vecq as V
 from .dqn import DQNConfig
 
 MAX_ATOMS, MAX_STREAM = Q.MAX_ATOMS, 1
@@ -30,6 +30,7 @@ ENVELOPE = (f"Net on vector observations of 1 .. {Q.MAX_OBS} entries, 1 .. {Q.MA
             f"{MAX_STREAM} hidden layer in each of Q and V, both streams all NoisyLinear or all nn.Linear, widths multiples of 32 in "
             f"[32, {Q.MAX_WIDTH}], ReLU, no norm_layer, softmax=True, concat=False, 1 .. {Q.MAX_ACTIONS} actions, num_atoms 2 .. "
             f"{MAX_ATOMS}, the activations, four atom tables and staged noise of a 32-row tile within 160 KB of LDS")
+_F = V.Family("Rainbow MLP", ENVELOPE)
 _NOISY, _PLAIN = ("mu_W", "sigma_W", "mu_bias", "sigma_bias"), ("weight", "bias")
 
 support = C5.support
@@ -39,19 +40,13 @@ def make_layers(obs_dim, trunk, q_hidden, v_hidden, n_act, n_atoms, noisy) -> tu
     """The model description every function here takes; raises NotImplementedError, naming the reason, outside the envelope."""
     trunk, q, v = (tuple(int(w) for w in t) for t in (trunk, q_hidden, v_hidden))
     obs_dim, n_act, n_atoms = int(obs_dim), int(n_act), int(n_atoms)
-    if not 1 <= obs_dim <= Q.MAX_OBS:
-        raise NotImplementedError(f"Rainbow MLP: obs_dim = {obs_dim} is outside [1, {Q.MAX_OBS}]; supported: {ENVELOPE}")
-    if not 1 <= len(trunk) <= Q.MAX_TRUNK:
-        raise NotImplementedError(f"Rainbow MLP: {len(trunk)} trunk hidden layers (1 .. {Q.MAX_TRUNK}); supported: {ENVELOPE}")
+    _F.in_range("obs_dim", obs_dim, 1, Q.MAX_OBS)
+    _F.count(len(trunk), "trunk hidden layers", 1, Q.MAX_TRUNK)
     if len(q) > MAX_STREAM or len(v) > MAX_STREAM:
-        raise NotImplementedError(f"Rainbow MLP: Q / V streams with {len(q)} / {len(v)} hidden layers (0 .. {MAX_STREAM}); supported: {ENVELOPE}")
-    bad = [w for w in trunk + q + v if w % 32 or not 32 <= w <= Q.MAX_WIDTH]
-    if bad:
-        raise NotImplementedError(f"Rainbow MLP: hidden width {bad[0]} is no multiple of 32 in [32, {Q.MAX_WIDTH}]; supported: {ENVELOPE}")
-    if not 1 <= n_act <= Q.MAX_ACTIONS:
-        raise NotImplementedError(f"Rainbow MLP: {n_act} actions (1 .. {Q.MAX_ACTIONS}); supported: {ENVELOPE}")
-    if not 2 <= n_atoms <= MAX_ATOMS:
-        raise NotImplementedError(f"Rainbow MLP: num_atoms = {n_atoms} is outside [2, {MAX_ATOMS}]; supported: {ENVELOPE}")
+        raise _F.refuse(f"Q / V streams with {len(q)} / {len(v)} hidden layers (0 .. {MAX_STREAM})")
+    _F.widths(trunk + q + v, Q.MAX_WIDTH)
+    _F.count(n_act, "actions", 1, Q.MAX_ACTIONS)
+    _F.in_range("num_atoms", n_atoms, 2, MAX_ATOMS)
     layers = (obs_dim, trunk, q, v, n_act, n_atoms, bool(noisy))
     layout(layers)                                     # the LDS carve of a tile is the library's arithmetic
     return layers
@@ -65,14 +60,7 @@ def _desc(layers):
 
 def layout(layers, batch: int = 1) -> dict:
     """ts_rainbow_mlp_layout -> {count, lds_bytes, workspace_bytes, noise_count}; NotImplementedError when the tile does not fit the LDS."""
-    out = (C.c_int64 * 16)()
-    try:
-        _lib.check(_lib.load().ts_rainbow_mlp_layout(_desc(layers), _lib.i64(batch), out))
-    except _lib.EngineError as e:
-        if e.code != _lib.TS_ERR_UNSUPPORTED:
-            raise
-        raise NotImplementedError(f"Rainbow MLP: {e}; supported: {ENVELOPE}") from None
-    return {"count": int(out[0]), "lds_bytes": int(out[1]), "workspace_bytes": int(out[2]), "noise_count": int(out[11])}
+    return _F.layout("ts_rainbow_mlp_layout", _desc(layers), batch, noise_count=11)
 
 
 def _blocks(layers) -> list:
@@ -143,16 +131,13 @@ def noise_from_torch(tensors, *layers_and_device) -> torch.Tensor:
 def describe_module(net) -> tuple:
     """-> `layers` of a Net-shaped module with `softmax=True` and `dueling_param` (common.py:286-341), or raises NotImplementedError
     naming what is not supported."""
-    for name in ("model", "Q", "V", "use_dueling", "softmax", "num_atoms"):
-        if not hasattr(net, name):
-            raise NotImplementedError(f"Rainbow MLP: a Net is needed (found {type(net).__name__} without `{name}`); supported: {ENVELOPE}")
+    _F.require_net(net, extra=("Q", "V"))
     if not net.softmax:
-        raise NotImplementedError(f"Rainbow MLP: softmax=True is needed (dueling DQN on a Net is dqn_mlp's); supported: {ENVELOPE}")
+        raise _F.refuse("softmax=True is needed (dueling DQN on a Net is dqn_mlp's)")
     if not net.use_dueling:
-        raise NotImplementedError(f"Rainbow MLP: dueling_param is needed (C51 on a plain Net is c51_mlp's); supported: {ENVELOPE}")
+        raise _F.refuse("dueling_param is needed (C51 on a plain Net is c51_mlp's)")
     n_atoms = int(net.num_atoms)
-    if not 2 <= n_atoms <= MAX_ATOMS:
-        raise NotImplementedError(f"Rainbow MLP: num_atoms = {n_atoms} is outside [2, {MAX_ATOMS}]; supported: {ENVELOPE}")
+    _F.in_range("num_atoms", n_atoms, 2, MAX_ATOMS)
 
     def chain(mlp, who, ends_linear, kinds):
         """[layer, ReLU, layer, ReLU, ...(, layer)] -> [(in, out)] of the layers; `kinds`: the layer classes' names seen."""
@@ -160,34 +145,30 @@ def describe_module(net) -> tuple:
         for j, m in enumerate(mods):
             if j % 2 == 1:
                 if not isinstance(m, torch.nn.ReLU):
-                    raise NotImplementedError(f"Rainbow MLP {who}: the activation must be ReLU (found {type(m).__name__}); supported: {ENVELOPE}")
+                    raise _F.refuse(f"the activation must be ReLU (found {type(m).__name__})", who)
             elif (isinstance(m, torch.nn.Linear) and m.bias is not None) or (who != "model" and hasattr(m, "mu_W") and hasattr(m, "eps_q")):
                 kinds.add("noisy" if hasattr(m, "mu_W") else "plain")
                 dims.append((m.in_features, m.out_features))
             else:
-                raise NotImplementedError(f"Rainbow MLP {who}: " + ("Linear layers with bias" if who == "model" else "NoisyLinear or Linear layers with bias")
-                                          + f" followed by ReLU only, no norm_layer (found {type(m).__name__}); supported: {ENVELOPE}")
+                raise _F.refuse(("Linear layers with bias" if who == "model" else "NoisyLinear or Linear layers with bias")
+                                + f" followed by ReLU only, no norm_layer (found {type(m).__name__})", who)
         if ends_linear != (len(mods) % 2 == 1):
-            raise NotImplementedError(f"Rainbow MLP {who}: " + ("the last layer must map onto the outputs (concat=True is not supported)"
-                                                                if ends_linear else "the trunk of a dueling Net ends in its last hidden layer")
-                                      + f"; supported: {ENVELOPE}")
+            raise _F.refuse("the last layer must map onto the outputs (concat=True is not supported)" if ends_linear
+                            else "the trunk of a dueling Net ends in its last hidden layer", who)
         return dims
 
     kinds: set = set()
     trunk = chain(net.model, "model", False, set())
     if not trunk:
-        raise NotImplementedError(f"Rainbow MLP: at least one trunk hidden layer is needed; supported: {ENVELOPE}")
+        raise _F.refuse("at least one trunk hidden layer is needed")
     q, v = chain(net.Q, "Q", True, kinds), chain(net.V, "V", True, kinds)
     if len(kinds) != 1:
-        raise NotImplementedError(f"Rainbow MLP: both streams all NoisyLinear or all nn.Linear (found a mix); supported: {ENVELOPE}")
+        raise _F.refuse("both streams all NoisyLinear or all nn.Linear (found a mix)")
     if q[-1][1] % n_atoms or v[-1][1] != n_atoms:
-        raise NotImplementedError(f"Rainbow MLP: Q must end in n_act * {n_atoms} outputs and V in {n_atoms}, found {q[-1][1]} and {v[-1][1]}; "
-                                  f"supported: {ENVELOPE}")
+        raise _F.refuse(f"Q must end in n_act * {n_atoms} outputs and V in {n_atoms}, found {q[-1][1]} and {v[-1][1]}")
     layers = make_layers(trunk[0][0], [d[1] for d in trunk], [d[1] for d in q[:-1]], [d[1] for d in v[:-1]], q[-1][1] // n_atoms, n_atoms,
                          kinds == {"noisy"})
-    have = [k for k, p in net.named_parameters() if p.requires_grad]
-    if have != state_dict_keys(layers):
-        raise NotImplementedError(f"Rainbow MLP: the model's parameters {have} are not a Net's {state_dict_keys(layers)}; supported: {ENVELOPE}")
+    _F.same_parameters(net, state_dict_keys(layers), "a Net's", trainable_only=True)
     return layers
 
 
@@ -195,35 +176,22 @@ class RainbowMlpEngine(C5.C51MlpEngine):
     """State of one Rainbow learner on one GPU: C51MlpEngine's surface (flat parameters, lagged copy, Adam moments, counters, the
     support) plus one noise vector per network, set by `set_noise` before every update (rainbow.py:97-100)."""
 
+    FAMILY = _F
+
     def __init__(self, layers, flat_params: torch.Tensor, noise: torch.Tensor | None, cfg: DQNConfig, v_min: float = -10.0, v_max: float = 10.0):
-        if not flat_params.is_cuda:
-            raise RuntimeError("RainbowMlpEngine needs parameters on an MI355X (no CPU fallback)")
-        if not v_min < v_max:
-            raise ValueError(f"v_max must be larger than v_min, got {v_min=} and {v_max=}")
-        self.layers = make_layers(*layers)
-        self.obs_dim, self.n_act, self.n_atoms, self.noisy = self.layers[0], self.layers[4], self.layers[5], self.layers[6]
-        self.cfg = cfg
-        self._d = _desc(self.layers)
-        lay = layout(self.layers)
-        self.P, self.n_noise = lay["count"], lay["noise_count"]
-        if flat_params.numel() != self.P:
-            raise ValueError(f"expected {self.P} parameters, got {flat_params.numel()}")
-        self.device = flat_params.device
-        self.params = flat_params.detach().float().contiguous().clone()
-        self.params_old = self.params.clone() if cfg.target_update_freq > 0 else None    # dqn.py:240-246 (deepcopy: weights and noise)
+        self._require_device(flat_params)
+        self._check_support(v_min, v_max)
+        layers = make_layers(*layers)
+        lay = layout(layers)
+        V.VecQEngine.__init__(self, layers, _desc(layers), lay["count"], flat_params, cfg)      # (lagged: deepcopy, weights and noise)
+        self.n_act, self.n_atoms, self.noisy, self.n_noise = layers[4], layers[5], layers[6], lay["noise_count"]
         self.noise = self.noise_old = None
         if self.noisy:
             if noise is None or noise.numel() != self.n_noise:
                 raise ValueError(f"expected a noise vector of {self.n_noise} entries")
             self.noise = noise.detach().float().to(self.device).contiguous().clone()
             self.noise_old = self.noise.clone() if self.params_old is not None else None
-        self.adam_m, self.adam_v = torch.zeros_like(self.params), torch.zeros_like(self.params)
-        self.adam_step = 0
-        self.iter = 0
-        self.v_min, self.v_max = float(v_min), float(v_max)
-        self.delta_z = (self.v_max - self.v_min) / (self.n_atoms - 1)                      # c51.py:118
-        self.support = support(self.v_min, self.v_max, self.n_atoms, self.device)
-        self._ws = _lib.default_workspace(self.device.index or 0)
+        self._set_support(v_min, v_max)
 
     def set_noise(self, noise: torch.Tensor, noise_old: torch.Tensor | None = None) -> None:
         """The result of RainbowDQN._sample_noise on the online (and the lagged) network; nothing to set for plain streams."""
@@ -256,7 +224,7 @@ class RainbowMlpEngine(C5.C51MlpEngine):
         out = torch.empty((b, self.n_atoms), dtype=torch.float32, device=self.device)
         z, v_min, v_max, dz = self._z()
         _lib.check(_lib.load().ts_rainbow_mlp_target_dist(
-            _lib.ptr(self.params), _lib.ptr(self.noise), _lib.ptr(self._lagged()[1]), _lib.ptr(self.noise_old), self._d, z, v_min, v_max, dz,
+            _lib.ptr(self.params), _lib.ptr(self.noise), _lib.ptr(self._lagged()), _lib.ptr(self.noise_old), self._d, z, v_min, v_max, dz,
             _lib.ptr(obs_next), _lib.ptr(returns), _lib.i64(b), _lib.ptr(out), _lib.current_stream(self.device)))
         return out
 
@@ -265,35 +233,18 @@ class RainbowMlpEngine(C5.C51MlpEngine):
                           target_out: torch.Tensor | None = None):
         """As C51MlpEngine.update_with_batch.  On a sync iteration the lagged network takes the pre-step parameters inside the call
         and the lagged noise takes the online noise (load_state_dict copies the eps vectors too)."""
-        obs, obs_next = self._obs(obs), self._obs(obs_next)
-        b = obs.shape[0]
-        act = _i64_dev(act, self.device).reshape(-1)
-        returns = self._returns(returns, b)
-        if act.numel() != b or obs_next.shape[0] != b:
-            raise ValueError(f"act and obs_next must hold {b} rows")
-        if weight is not None:
-            weight = torch.as_tensor(weight, device=self.device).to(torch.float32).reshape(-1).contiguous()
-            if weight.numel() != b:
-                raise ValueError("weight length mismatch")
-        if grad_out is not None and (grad_out.numel() != self.P or grad_out.dtype != torch.float32):
-            raise ValueError("grad_out must be a float32 vector of the model's size")
-        if target_out is not None and (tuple(target_out.shape) != (b, self.n_atoms) or target_out.dtype != torch.float32
-                                       or not target_out.is_contiguous()):
-            raise ValueError(f"target_out must be a contiguous float32 [{b}, {self.n_atoms}]")
-        sync, _ = self._lagged()
+        obs, act, obs_next, returns, weight = self._update_args(obs, act, obs_next, returns, weight, grad_out, target_out)
+        b, sync = obs.shape[0], self._sync_now()
         prio = torch.empty(b, dtype=torch.float32, device=self.device)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
         hp = self.cfg.to_c(grad_only=not apply)
         z, v_min, v_max, dz = self._z()
         _lib.check(_lib.load().ts_rainbow_mlp_update(
             self._ws.handle, _lib.ptr(self.params), _lib.ptr(self.noise), _lib.ptr(self.params_old), _lib.ptr(self.noise_old),
-            C.c_int32(int(sync)), _lib.ptr(self.adam_m), _lib.ptr(self.adam_v),
-            _lib.i64(self.adam_step + 1 if apply else max(self.adam_step, 1)), self._d, z, v_min, v_max, dz, _lib.ptr(obs), _lib.ptr(act),
-            _lib.ptr(obs_next), _lib.ptr(returns), _lib.ptr(weight), _lib.i64(b), C.byref(hp), _lib.ptr(loss), _lib.ptr(prio),
-            _lib.ptr(grad_out), _lib.ptr(target_out), _lib.current_stream(self.device)))
+            C.c_int32(int(sync)), _lib.ptr(self.adam_m), _lib.ptr(self.adam_v), self._adam_arg(apply), self._d, z, v_min, v_max, dz,
+            _lib.ptr(obs), _lib.ptr(act), _lib.ptr(obs_next), _lib.ptr(returns), _lib.ptr(weight), _lib.i64(b), C.byref(hp), _lib.ptr(loss),
+            _lib.ptr(prio), _lib.ptr(grad_out), _lib.ptr(target_out), _lib.current_stream(self.device)))
         if sync and self.noise_old is not None:
             self.noise_old.copy_(self.noise)
-        self.iter += 1
-        if apply:
-            self.adam_step += 1
+        self._stepped(apply)
         return loss, prio
